@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- M2Trans x4 train-step throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype bf16|fp32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype bf16|fp32] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (forward, L1 loss, backward, gradient all-reduce when
 N > 1, fused Adam) over one batch of synthetic 128x128 LR / 512x512 HR patches that are already
@@ -10,8 +10,16 @@ torch.distributed.run, or -- `python bench.py --gpus N` alone -- by this script,
 launcher as a CHILD process before touching the GPU and exits with its status.  Per-GPU batch is
 fixed (weak scaling); value = patches of ALL ranks / max-over-ranks time.
 
-Rank 0 prints ONE JSON line (metric/value/... + "roofline" for the dominant kernel measured
-with HIP events inside the timed region + "cpu_baseline": the CPU oracle timed on the host).
+Rank 0 prints ONE JSON line (metric/value/unit/higher_is_better/dtype/ms_per_step/...).  A plain run does only
+what that line needs: set up, warm up, time exactly K steps, write the outputs (--dump-outputs DIR), print.
+--full adds everything else the line used to carry: "roofline" for the dominant kernel measured with HIP events
+inside the timed region (and `others` from two extra all-event steps), the short runs of the other BASELINE
+workloads in `also`, and "cpu_baseline": the CPU oracle timed on the host.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step handed its caller as float32
+.npy files: loss.npy (the step's loss), params.npy (the flat parameter buffer after the Adam update) and
+grads.npy (the flat gradient buffer of that step); ~29 MB in all for the x4 model.  Inputs and initial weights
+are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -35,7 +43,7 @@ PRESETS = {1: dict(batch=16, lr_size=128, scale=4, sem=False), 2: dict(batch=32,
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", type=int, default=None, choices=[1, 2, 3, 4],
                     help="BASELINE.json configs[i] preset: 1 = x4 128x128 batch 16/GPU L1 only (the headline; default at every --gpus N); "
@@ -45,9 +53,14 @@ def parse():
     ap.add_argument("--lr-size", type=int, default=None)
     ap.add_argument("--scale", type=int, default=None)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-events", action="store_true", help="do not record per-kernel HIP events")
-    ap.add_argument("--all-kernel-events", action="store_true", help="time every kernel category in the timed region (adds ~8%% overhead)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the roofline of the dominant kernel (HIP events in the timed region "
+                         "and two extra all-event steps), the `also` runs of the other BASELINE workloads, and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write loss / params / grads of the last timed step to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-kernel-events", action="store_true", help="with --full: do not record per-kernel HIP events (a plain run records none)")
+    ap.add_argument("--all-kernel-events", action="store_true", help="with --full: time every kernel category in the timed region (adds ~8%% overhead)")
     ap.add_argument("--kernel-event-stride", type=int, default=3,
                     help="HIP events ride on every n-th launch of the dominant kernel (an event-carrying dispatch costs ~10 us: "
                          "16 per step = +2.3%% on the step; 1 = every launch)")
@@ -65,9 +78,9 @@ def parse():
                     help="BASELINE configs[2]: add the MedCLIP(Swin-T) image-text regulariser (random-init tower, hash text features)")
     ap.add_argument("--cpu-baseline-batch", type=int, default=None)
     ap.add_argument("--no-also", action="store_true",
-                    help="default run only: skip the short runs of the other BASELINE workloads that fill the line's `also` list")
+                    help="with --full, default run only: skip the short runs of the other BASELINE workloads that fill the line's `also` list")
     ap.add_argument("--also-steps", type=int, default=6, help="timed steps of each `also` run (>= 5)")
-    ap.add_argument("--also-list", default=None, metavar="NAME,NAME", help="which `also` workloads to run and in which order (default: all four; diagnosis)")
+    ap.add_argument("--also-list", default=None, metavar="NAME,NAME", help="with --full: which `also` workloads to run and in which order (default: all four; diagnosis)")
     ap.add_argument("--selftest-shared-device", action="store_true",
                     help="HARNESS SELF-TEST on a 1-GPU box: the N ranks of --gpus N all compute on device 0 and exchange over gloo, so that the "
                          "REAL N-rank control flow (headline, extra timing steps, `also` workload, collectives in every step) runs end to end; "
@@ -79,6 +92,12 @@ def parse():
                     help="HARNESS SELF-TEST on CPU: run this script's N-rank control flow with gloo and a sleeping stand-in for the step; "
                          "prints an `invalid` line with no throughput")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if not args.full:
+        for flag, given in (("--all-kernel-events", args.all_kernel_events), ("--also-list", args.also_list is not None)):
+            if given:
+                ap.error(f"{flag} needs --full")
     # presets = BASELINE.json configs[i]; configs[0] (x2 64x64 CPU forward) is a parity case, not a bench line
     if args.config is None:
         # the SAME per-GPU workload at every N (weak scaling: 16 patches per GPU, BASELINE configs[1]), so that the driver's 1 -> N efficiency
@@ -117,6 +136,15 @@ def synthetic_batch(B, h, scale, rank, step, device):
     lr = torch.rand(B, 3, h, h, generator=g, device=device)
     hr = torch.rand(B, 3, h * scale, h * scale, generator=g, device=device)
     return lr, hr
+
+
+def dump_outputs(out_dir: str, ts) -> None:
+    """What the last timed step handed its caller, as float32 .npy: the loss, the updated flat parameters, the flat gradients."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": ts.loss.detach().reshape(-1), "params": ts.model.flat_params.detach(), "grads": ts.grads.detach()}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.float().cpu().numpy())
 
 
 def usable_cores() -> int:
@@ -389,7 +417,8 @@ def run_workload(args, device, rank: int, world: int, backend, grp: dict, cpu_ba
         if key not in _MAIN_STREAMS:
             _MAIN_STREAMS[key] = torch.cuda.Stream(device=device, priority=main_priority)
         torch.cuda.set_stream(_MAIN_STREAMS[key])
-    events_on = rank == 0 and not args.no_kernel_events
+    kernel_events = args.full and not args.no_kernel_events
+    events_on = rank == 0 and kernel_events
     for s in range(args.warmup):
         if events_on and s == args.warmup - 1:
             m2t_profile.enable()      # last warm-up step: time every category to find the dominant kernel
@@ -427,6 +456,8 @@ def run_workload(args, device, rank: int, world: int, backend, grp: dict, cpu_ba
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt, exposed_ms = float(t[0]), float(t[1])
     loss = float(ts.loss)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, ts)       # before the extra steps below change the parameters
     roofline = None
     if events_on:
         pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json" if args.config == 1 else f"pmc_traffic_config{args.config}.json")
@@ -442,7 +473,7 @@ def run_workload(args, device, rank: int, world: int, backend, grp: dict, cpu_ba
     # The other categories (side-stream weight-gradient GEMMs included) are timed AFTER the timed region, on every launch of two extra
     # steps, so that the step the value is quoted on carries events on one kernel only.  EVERY rank runs these two steps -- a step contains
     # the gradient all-reduce, and a collective that only rank 0 enters never returns -- whatever rank 0's report came out as.
-    if not args.no_kernel_events and not args.all_kernel_events:
+    if kernel_events and not args.all_kernel_events:
         if events_on:
             m2t_profile.enable(m2t_profile.ALL_MASK, sample_every=1)
         for s in range(2):
@@ -617,6 +648,7 @@ def also_args(args, config: int, dtype: str):
     a.preset_overridden = False
     a.steps, a.warmup = max(5, args.also_steps), 2
     a.cpu_baseline_batch = 2 if a.lr_size <= 128 else 1
+    a.dump_outputs = None
     return a
 
 
@@ -664,7 +696,7 @@ def main():
     plain_multi = (world > 1 and args.config == 1 and not args.preset_overridden and args.dtype == "bf16" and not args.option
                    and not any((args.no_side_stream, args.null_stream, args.no_overlap_comm, args.all_kernel_events, args.no_overlap_semantic,
                                 args.debug_skip_side, args.no_kernel_events)))
-    if plain_multi and not args.no_also:
+    if plain_multi and args.full and not args.no_also:
         # N > 1: EVERY rank runs configs[3]'s per-GPU share behind the headline (the collectives need all of them); rank 0 reports it.
         # A rank that raises inside it (out of memory, a plan error) leaves the others blocked in a collective it never enters: every
         # rank therefore watches the rendezvous store while the extra workload runs (AlsoWatch), and when ANY rank has failed rank 0
@@ -686,7 +718,7 @@ def main():
             watch.fail(f"{type(e).__name__}: {e}"[:300])          # (does not return when other ranks may be inside a collective)
             if rank == 0:
                 out["also"] = [{"workload": "config3", "error": f"{type(e).__name__}: {e}"[:300]}]
-    if (plain_default or args.also_list) and not args.no_also and rank == 0 and world == 1:
+    if args.full and (plain_default or args.also_list) and not args.no_also and rank == 0 and world == 1:
         also = []
         runs = ALSO_RUNS if not args.also_list else [(n, dict(ALSO_RUNS)[n]) for n in args.also_list.split(",")]
         for name, kw in runs:
@@ -710,7 +742,7 @@ def main():
         if args.selftest_shared_device:
             out["invalid"] = True           # harness self-test: the ranks shared one device
             out["value"] = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(finalize_line(out)), flush=True)
     if torch.distributed.is_initialized():

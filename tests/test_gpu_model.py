@@ -1270,8 +1270,10 @@ def test_bench_two_rank_control_flow_on_one_device():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--selftest-shared-device", "--steps", "3", "--warmup", "2"],
+    # GPU_MAX_HW_QUEUES is dropped as well: the line must show the value bench.py itself sets for its ranks, not an inherited one
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "GPU_MAX_HW_QUEUES")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--selftest-shared-device", "--steps", "3", "--warmup", "2",
+                        "--full"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -1283,3 +1285,28 @@ def test_bench_two_rank_control_flow_on_one_device():
     assert d["roofline"] is not None and len(d["roofline"]["others"]) == 5                   # the extra steps ran (on both ranks) and returned
     (a,) = d["also"]
     assert a["workload"] == "config3" and a["n_gpus"] == 2 and a["per_gpu_batch"] == 32 and a["global_batch"] == 64 and a["ms_per_step"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_k_steps_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` run: exactly --steps timed steps, `ms_per_step` consistent with `value`, none of the --full extras
+    (roofline, `also`, cpu_baseline), and --dump-outputs writes the loss, parameters and gradients of the last timed step as
+    float32 .npy files (the loss agrees with the line's final_loss)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["dtype"] == "bf16" and d["higher_is_better"] is True
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 16 * 1000.0 / d["ms_per_step"]) < 0.01 * d["value"]
+    assert d["roofline"] is None and "also" not in d and "cpu_baseline" not in d
+    loss, params, grads = (np.load(os.path.join(tmp_path, f"{n}.npy")) for n in ("loss", "params", "grads"))
+    assert loss.dtype == params.dtype == grads.dtype == np.float32
+    assert loss.shape == (1,) and params.shape == grads.shape and params.size > 1_000_000
+    assert np.isfinite(params).all() and np.isfinite(grads).all() and np.abs(grads).max() > 0
+    assert abs(float(loss[0]) - d["config"]["final_loss"]) < 1e-5
+    assert loss.nbytes + params.nbytes + grads.nbytes < 64 * 2 ** 20

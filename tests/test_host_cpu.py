@@ -556,6 +556,18 @@ def test_bench_plain_multi_gpu_launch_builds_the_torchrun_child():
     assert "torch.cuda" not in launch_src and "visible_gpu_count()" in launch_src
 
 
+def test_bench_refuses_full_only_options_and_zero_steps_before_touching_the_gpu():
+    """The per-kernel and extra-workload options belong to `--full`; without it they are an error, not silently ignored, and
+    `--steps` must be positive.  All of it is rejected while parsing, before the GPU is touched."""
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    for extra, msg in ((["--all-kernel-events"], "--all-kernel-events needs --full"), (["--also-list", "config3"], "--also-list needs --full"),
+                       (["--steps", "0"], "--steps must be >= 1")):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True, env=env, timeout=300)
+        assert r.returncode == 2 and msg in r.stderr and "{" not in r.stdout, (extra, r.stderr[-500:])
+
+
 def test_bench_visible_gpu_count_reads_kfd_topology(tmp_path, monkeypatch):
     """GPUs = KFD topology nodes with SIMDs (CPU nodes have none), narrowed by the *_VISIBLE_DEVICES lists."""
     import bench
