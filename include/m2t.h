@@ -151,6 +151,12 @@ int m2t_l1_loss_deferred(m2t_plan* p, const float* hr, float lambda_l1, double d
                          float* loss_out, void* workspace, void* stream);
 /* alternative seed: an arbitrary upstream gradient g_sr [B,3,H0*s,W0*s] (torch autograd). */
 int m2t_set_output_grad(m2t_plan* p, const float* g_sr, float rgb_range, void* workspace, void* stream);
+/* adds scale * g into the seed already materialised by m2t_l1_loss or m2t_set_output_grad (the opt-in differentiable
+ * SemanticLoss): g [B,3,gh,gw] float32; sample b's block lands at crops_host int[B][2] = (row0, col0) of the SR image, or at
+ * (0, 0) for every sample when crops_host is NULL; the same clamp mask and padded layout as m2t_set_output_grad.
+ * M2T_ERR_STATE without a seed or after m2t_l1_loss_deferred (no materialised seed); M2T_ERR_ARG for a block outside the image. */
+int m2t_add_output_grad(m2t_plan* p, const float* g, int gh, int gw, const int* crops_host, float scale, float rgb_range,
+                        void* workspace, void* stream);
 /* loss.backward() (train.py:209) restricted to the model: fills grads (flat, same layout as
  * params; every element is written). */
 int m2t_backward(m2t_plan* p, const float* params, const float* x, float* grads, void* workspace,
@@ -194,8 +200,12 @@ int m2t_window_attention_bwd(int dtype, const void* qkv, const float* rel_h, con
                              void* stream);
 
 /* ---- SemanticLoss (losses.py:18-81): MedCLIP image tower = Swin-T 224 forward + the loss value ----
- * Forward only: the reference evaluates it under torch.no_grad() (losses.py:63), so it contributes a
- * constant to the logged loss and no gradient.  Weights: ONE flat float32 buffer in the order reported
+ * Forward only by default; opt-in gradient.  The reference evaluates it under torch.no_grad() (losses.py:63), so by
+ * default it contributes a constant to the logged loss and no gradient.  The opt-in differentiable mode (SemanticLoss(...,
+ * differentiable=True)) gives d total / d sr for total = sum_i |a_i - b_i| / N, a_i = <e(x_i), t^_i>, b_i the same for
+ * the HR crop, e = normalise(P . mean_tokens(LN(Swin(.)))): sign(a_i - b_i) / N . J_e(x_i)^T t^_i (sign(0) = 0), taken back
+ * through the last random crop (a paste) or, for N = 1, through the adjoint of the bicubic resize.  The tower is frozen:
+ * data gradients only.  Weights: ONE flat float32 buffer in the order reported
  * by m2t_swin_param_name() (HF swin-tiny checkpoint names of transformers 4.24 + "projection_head.weight"
  * [512,768], the MedCLIP vision projection). */
 typedef struct m2t_swin m2t_swin;
@@ -221,6 +231,23 @@ int m2t_semantic_loss(const float* emb, const float* text, int B, int n_patches,
                       void* stream);
 /* F.interpolate(mode='bicubic', align_corners=True) (losses.py:53-54): src [NC,Hin,Win] -> dst [NC,Hout,Wout]. */
 int m2t_bicubic_resize(const float* src, float* dst, int NC, int Hin, int Win, int Hout, int Wout, void* stream);
+/* opt-in gradient.  Grad workspace for n_grad crops: transposed weights of the data-gradient GEMMs, the activation stash of
+ * n_grad crops (13.7 M elements of the compute type per crop) and the backward's scratch. */
+long long m2t_swin_grad_workspace_bytes(m2t_swin* p, int n_grad);
+/* m2t_swin_encode_pair that also stashes what the backward needs for crops [0, n_grad) (the SR crops come first).  fp32: emb
+ * bit-identical to m2t_swin_encode_pair; bf16: the MLP of stages 1 / 2 runs unfused (it stores gelu'), within the bf16
+ * tolerance of the forward.  grad_ws: at least m2t_swin_grad_workspace_bytes(p, n_grad) bytes. */
+int m2t_swin_encode_grad(m2t_swin* p, const float* src_a, int n_a, const float* src_b, int n_b, int Hs, int Ws,
+                         const int* crops_host, int n, int n_grad, float* emb, void* workspace, void* grad_ws, void* stream);
+/* d total / d emb of the SR half: g_emb[B,512] = sign(a_i - b_i) / n_patches . t_i / |t_i| (emb, text as m2t_semantic_loss). */
+int m2t_semantic_loss_backward(const float* emb, const float* text, int B, int n_patches, float* g_emb, void* stream);
+/* vector-Jacobian product of encode_image for the n_grad crops of the last m2t_swin_encode_grad (same n_grad and grad_ws,
+ * else M2T_ERR_STATE): g_emb [n_grad,512] -> g_crops [n_grad,3,224,224] float32 (overwritten).  The residual-stream gradient is
+ * fp32 in both modes; in bf16 the GEMM operands are rounded to bf16. */
+int m2t_swin_backward(m2t_swin* p, const float* g_emb, int n_grad, float* g_crops, void* workspace, void* grad_ws, void* stream);
+/* the exact adjoint of m2t_bicubic_resize, a deterministic gather (no atomics): g_dst [NC,Hout,Wout] -> g_src [NC,Hin,Win]
+ * (overwritten). */
+int m2t_bicubic_resize_backward(const float* g_dst, float* g_src, int NC, int Hin, int Win, int Hout, int Wout, void* stream);
 
 /* ---- SemanticLoss text tower (losses.py:22-25,64-65,74): medmodel.encode_text ---------------------------------
  * BERT-base forward (Bio_ClinicalBERT geometry: 12 layers x 768, 12 heads, 3072 intermediate, vocab 28 996, LayerNorm eps

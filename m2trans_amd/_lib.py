@@ -29,6 +29,7 @@ SIGNATURES = {
     "m2t_l1_loss": (_i, [_vp, _vp, _f, _d, _f, _vp, _vp, _vp]),
     "m2t_l1_loss_deferred": (_i, [_vp, _vp, _f, _d, _f, _vp, _vp, _vp]),
     "m2t_set_output_grad": (_i, [_vp, _vp, _f, _vp, _vp]),
+    "m2t_add_output_grad": (_i, [_vp, _vp, _i, _i, C.POINTER(_i), _f, _f, _vp, _vp]),
     "m2t_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "m2t_adam_step": (_i, [_vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _i, _f, _vp]),
     "m2t_profile_enable": (_i, [C.c_ulonglong]),
@@ -43,6 +44,11 @@ SIGNATURES = {
     "m2t_swin_encode_pair": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, C.POINTER(_i), _i, _vp, _vp, _vp]),
     "m2t_semantic_loss": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "m2t_bicubic_resize": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "m2t_swin_grad_workspace_bytes": (_ll, [_vp, _i]),
+    "m2t_swin_encode_grad": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, C.POINTER(_i), _i, _i, _vp, _vp, _vp, _vp]),
+    "m2t_semantic_loss_backward": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "m2t_swin_backward": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "m2t_bicubic_resize_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "m2t_text_create": (_i, [C.POINTER(_vp), _i, _i, _i]),
     "m2t_text_destroy": (None, [_vp]),
     "m2t_text_query": (_ll, [_vp, C.c_char_p]),

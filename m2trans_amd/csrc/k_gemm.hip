@@ -385,6 +385,7 @@ static int launch_gemm_nt_t(int amode, int emode, const m2t_gemm_args& a, hipStr
   else if (amode == M2T_A_PLAIN && emode == M2T_E_BIAS_GELU) GO(M2T_A_PLAIN, M2T_E_BIAS_GELU);
   else if (amode == M2T_A_PLAIN && emode == M2T_E_BIAS_RESID) GO(M2T_A_PLAIN, M2T_E_BIAS_RESID);
   else if (amode == M2T_A_PLAIN && emode == M2T_E_BIAS_RELU) GO(M2T_A_PLAIN, M2T_E_BIAS_RELU);
+  else if (amode == M2T_A_PLAIN && emode == M2T_E_GELU_GRAD) GO(M2T_A_PLAIN, M2T_E_GELU_GRAD);   // Swin MLP data gradient (k_swin_bwd.hip)
   else if (amode == M2T_A_UNSHUF && emode == M2T_E_PLAIN) GO(M2T_A_UNSHUF, M2T_E_PLAIN);
   else if (amode == M2T_A_UNSHUF && emode == M2T_E_GELU_GRAD) GO(M2T_A_UNSHUF, M2T_E_GELU_GRAD);
   else return m2t_set_error(-2, "gemm_nt: unsupported (A mode, epilogue) combination");

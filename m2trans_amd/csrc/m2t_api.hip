@@ -704,6 +704,31 @@ extern "C" int m2t_set_output_grad(m2t_plan* p, const float* g_sr, float rgb_ran
   return 0;
 }
 
+// adds scale * g into the materialised seed: sample b's [3][gh][gw] block lands at its crop origin (crops_host int[B][2] = (row0, col0), or
+// NULL: (0, 0)), through the same clamp mask and padded layout as m2t_set_output_grad (the opt-in differentiable SemanticLoss)
+extern "C" int m2t_add_output_grad(m2t_plan* p, const float* g, int gh, int gw, const int* crops_host, float scale, float rgb_range,
+                                   void* workspace, void* stream) {
+  if (!p || !g || !workspace || gh < 1 || gw < 1) return m2t_set_error(M2T_ERR_ARG, "m2t_add_output_grad: null / bad argument");
+  if (!p->have_acts || !p->have_seed || p->l1_deferred)
+    return m2t_set_error(M2T_ERR_STATE, "m2t_add_output_grad: needs a materialised seed (m2t_l1_loss or m2t_set_output_grad)");
+  for (int b = 0; b < p->B; ++b) {
+    const int y0 = crops_host ? crops_host[2 * b] : 0, x0 = crops_host ? crops_host[2 * b + 1] : 0;
+    if (y0 < 0 || x0 < 0 || y0 + gh > p->Hs || x0 + gw > p->Ws) return m2t_set_error(M2T_ERR_ARG, "m2t_add_output_grad: block outside the image");
+  }
+  const long long img = 3LL * p->Hsp * p->Wsp, blk = 3LL * gh * gw;
+  for (int b0 = 0; b0 < p->B; b0 += 64) {
+    const int nb = std::min(64, p->B - b0);
+    M2TCropOrigins org{};
+    for (int b = 0; b < nb; ++b) {
+      org.y0[b] = crops_host ? crops_host[2 * (b0 + b)] : 0;
+      org.x0[b] = crops_host ? crops_host[2 * (b0 + b) + 1] : 0;
+    }
+    CK(launch_add_output_grad((const float*)WSP("srpre") + b0 * img, g + b0 * blk, (float*)WSP("gpre") + b0 * img, nb, p->Hsp, p->Wsp, gh, gw,
+                              org, scale, rgb_range, (hipStream_t)stream));
+  }
+  return 0;
+}
+
 // Two-stream backward.  The data-gradient chain (what the next kernel needs) runs on the
 // caller's stream; everything that only produces PARAMETER gradients (weight/bias gradients,
 // slab reductions, rel-pos reductions) runs on the plan's side stream, forked/joined with

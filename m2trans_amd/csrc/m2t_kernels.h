@@ -293,3 +293,17 @@ int launch_swin_head(int dt, const void* x, const float* proj, float* emb, int n
 int launch_semantic_loss(const float* emb, const float* text, int B, int n_patches, float* per_sample, float* total, hipStream_t st);
 int launch_bicubic_resize(const float* src, float* dst, int NC, int Hin, int Win, int Hout, int Wout, hipStream_t st);
 int launch_convert(int dt, const float* src, void* dst, long long n, hipStream_t st);
+// ---- k_swin_bwd.hip (data gradient of the image tower: the opt-in differentiable SemanticLoss) ----------
+struct M2TCropOrigins { int y0[64], x0[64]; };   // per-sample block origins of one add_output_grad launch (<= 64 samples)
+int launch_semantic_loss_bwd(const float* emb, const float* text, int B, int n_patches, float* g_emb, hipStream_t st);
+int launch_swin_head_bwd(int dt, const void* hn, const float* proj, const float* g_emb, void* g_hn, int nimg, hipStream_t st);
+int launch_layernorm_bwd(int dt, const void* x, const void* g, const float* gamma, const float* resid, float* out_f, void* out_t,
+                         long long M, int C, hipStream_t st, float eps = 1e-5f, const float* g_f = nullptr);
+int launch_swin_attn_bwd(int dt, const void* qkv, const float* bias_table, const void* gout, void* gqkv, int nimg, int H, int W, int C,
+                         int heads, int shift, hipStream_t st);
+int launch_swin_merge_scatter(int dt, const float* gy, float* gx, void* gxt, int nimg, int H, int W, int C, hipStream_t st);
+int launch_swin_embed_bwd(const float* ge, const float* wpe, float* g_crops, int nimg, hipStream_t st);
+int launch_transpose_convert(int dt, const float* src, void* dst, int N, int K, int ldd, int col0, hipStream_t st);
+int launch_bicubic_resize_bwd(const float* gdst, float* gsrc, int NC, int Hin, int Win, int Hout, int Wout, hipStream_t st);
+int launch_add_output_grad(const float* pre, const float* g, float* gpre, int B, int Hp, int Wp, int gh, int gw, const M2TCropOrigins& org,
+                           float scale, float R, hipStream_t st);

@@ -1,7 +1,8 @@
 // m2t_swin.hip -- C ABI of the MedCLIP image tower (Swin-T 224) + the SemanticLoss value
 // (include/m2t.h, "SemanticLoss" section).  Restates the arithmetic behind losses.py:53-79;
-// forward only (the reference runs it under torch.no_grad()).  Host code; kernels in k_swin.hip
-// and k_gemm.hip.
+// forward only by default (the reference runs it under torch.no_grad()); the opt-in data gradient
+// (m2t_swin_encode_grad / m2t_swin_backward) has its kernels in k_swin_bwd.hip.  Host code; forward
+// kernels in k_swin.hip and k_gemm.hip.
 #include <map>
 #include <string>
 #include <vector>
@@ -36,6 +37,19 @@ struct m2t_swin {
   hipEvent_t pin_ev[NPIN] = {};            // slot k's copy has been consumed
   bool pin_used[NPIN] = {};
   int pin_next = 0;
+  // opt-in data gradient (m2t_swin_encode_grad / m2t_swin_backward): the grad workspace's layout for grad_n crops, the
+  // workspace whose transposed weights are current, and the crop count of the last stash
+  std::map<std::string, Ws> gws;
+  size_t gws_bytes = 0;
+  int gws_n = -1;
+  const void* gws_packed = nullptr;
+  int grad_n = 0;
+  const void* grad_ws = nullptr;
+  void add_gws(const std::string& n, size_t elems, size_t es) {
+    gws_bytes = (gws_bytes + 255) & ~(size_t)255;
+    gws[n] = Ws{gws_bytes, elems};
+    gws_bytes += elems * es;
+  }
   bool fused_mlp = true;                   // bf16, stages 1 / 2: LayerNorm + fc1 + GELU + fc2 + residual in one kernel (k_swin.hip)
   void add_param(const std::string& n, long long c) { pnames.push_back(n); poff[n] = nparams; pnum[n] = c; nparams += c; }
   void add_pack(const std::string& n, long long c) { npacked = (npacked + 7) & ~7LL; pk[n] = npacked; npacked += c; }
@@ -148,6 +162,7 @@ extern "C" int m2t_swin_load_weights(m2t_swin* p, const float* weights, void* wo
   hipStream_t st = (hipStream_t)stream;
   const int dt = p->dt;
   p->weights = weights;
+  p->gws_packed = nullptr;                 // the transposed weights of a grad workspace are re-derived on its next use
   float* fbias = (float*)SWP("fbias");
   CKS(launch_convert(dt, weights + p->poff.at("embeddings.patch_embeddings.projection.weight"), spk(p, workspace, "pe"), 96 * 48, st));
   for (int s = 0; s < 4; ++s) {
@@ -195,8 +210,98 @@ extern "C" int m2t_swin_encode(m2t_swin* p, const float* src, int n_src, int Hs,
 
 // the same with the source images in TWO tensors (indices 0 .. n_a - 1 in src_a, n_a .. n_a + n_b - 1 in src_b): the SR and
 // HR batches of SemanticLoss.batch are encoded in one pass without concatenating them first
+static int encode_impl(m2t_swin* p, const float* src, int n_a, const float* src_b, int n_b, int Hs, int Ws, const int* crops_host, int n,
+                       float* emb, void* workspace, int n_grad, void* grad_ws, hipStream_t st);
 extern "C" int m2t_swin_encode_pair(m2t_swin* p, const float* src, int n_a, const float* src_b, int n_b, int Hs, int Ws,
                                     const int* crops_host, int n, float* emb, void* workspace, void* stream) {
+  return encode_impl(p, src, n_a, src_b, n_b, Hs, Ws, crops_host, n, emb, workspace, 0, nullptr, (hipStream_t)stream);
+}
+
+// ---- opt-in data gradient: grad workspace layout -------------------------------------------------------------------------
+// [transposed weights of the data-gradient GEMMs | fp32 scratch of the backward | stash of n_grad crops | gelu' of the forward]
+// stash per crop (elements of the storage type): e0 = 3136 x 96 (embedding before its LayerNorm); per block of stage s
+// (T_s = 3136 / 4^s tokens, C_s = 96 2^s): xin, xmid (the two LayerNorm inputs) 2 T_s C_s, qkv 3 T_s C_s, gelu'(fc1) 4 T_s C_s;
+// per patch merging the gathered rows T_s C_s; the final LayerNorm's input and output 2 x 49 x 768.  13.7 M elements per crop.
+static void grad_layout(m2t_swin* p, int ng) {
+  if (p->gws_n == ng) return;
+  p->gws.clear();
+  p->gws_bytes = 0;
+  const size_t es = p->esz, g = (size_t)ng, tok = g * 3136 * 96;
+  for (int s = 0; s < 4; ++s) {
+    const size_t C = 96u << s;
+    for (int j = 0; j < DEPTHS[s]; ++j) {
+      const std::string b = "encoder.layers." + std::to_string(s) + ".blocks." + std::to_string(j) + ".";
+      p->add_gws(b + "qkvT", 3 * C * C, es);
+      p->add_gws(b + "oT", C * C, es);
+      p->add_gws(b + "fc1T", 4 * C * C, es);
+      p->add_gws(b + "fc2T", 4 * C * C, es);
+    }
+    if (s < 3) p->add_gws("encoder.layers." + std::to_string(s) + ".downsample.redT", 8 * C * C, es);
+  }
+  p->add_gws("gR", tok, 4);            // residual-stream gradient (fp32 in both modes)
+  p->add_gws("gF", tok, 4);            // fp32 LayerNorm-gradient scratch (merge, embedding)
+  p->add_gws("gT", tok, es);           // storage-type copy of gR: the operand of the next data-gradient GEMM
+  p->add_gws("gC", tok, es);
+  p->add_gws("gQ", tok * 3, es);
+  p->add_gws("gA", tok * 4, es);
+  p->add_gws("e0", tok, es);
+  for (int s = 0; s < 4; ++s) {
+    const size_t tc = tok >> s;        // tokens x channels of stage s
+    for (int j = 0; j < DEPTHS[s]; ++j) {
+      const std::string b = "s" + std::to_string(s) + "b" + std::to_string(j) + ".";
+      p->add_gws(b + "xin", tc, es);
+      p->add_gws(b + "xmid", tc, es);
+      p->add_gws(b + "qkv", 3 * tc, es);
+      p->add_gws(b + "gder", 4 * tc, es);
+    }
+    if (s < 3) p->add_gws("m" + std::to_string(s), tc, es);
+  }
+  p->add_gws("xf", g * 49 * 768, es);
+  p->add_gws("hnf", g * 49 * 768, es);
+  p->add_gws("MD", (size_t)p->max_images * 3136 * 96 * 4, es);   // gelu'(fc1) of every crop of the call (stash keeps the first n_grad)
+  p->gws_bytes = (p->gws_bytes + 255) & ~(size_t)255;
+  p->gws_n = ng;
+}
+#define GWP(name) ((char*)grad_ws + p->gws.at(name).off)
+
+extern "C" long long m2t_swin_grad_workspace_bytes(m2t_swin* p, int n_grad) {
+  if (!p || n_grad < 1 || n_grad > p->max_images) return m2t_set_error(M2T_ERR_ARG, "m2t_swin_grad_workspace_bytes: n_grad out of range");
+  grad_layout(p, n_grad);
+  return (long long)p->gws_bytes;
+}
+
+static int pack_grad_weights(m2t_swin* p, void* grad_ws, hipStream_t st) {
+  const int dt = p->dt;
+  const float* wt = p->weights;
+  for (int s = 0; s < 4; ++s) {
+    const int C = 96 << s;
+    for (int j = 0; j < DEPTHS[s]; ++j) {
+      const std::string b = "encoder.layers." + std::to_string(s) + ".blocks." + std::to_string(j) + ".";
+      int part = 0;
+      for (const char* nm : {"query", "key", "value"})
+        CKS(launch_transpose_convert(dt, wt + p->poff.at(b + "attention.self." + nm + ".weight"), GWP(b + "qkvT"), C, C, 3 * C, C * part++, st));
+      CKS(launch_transpose_convert(dt, wt + p->poff.at(b + "attention.output.dense.weight"), GWP(b + "oT"), C, C, C, 0, st));
+      CKS(launch_transpose_convert(dt, wt + p->poff.at(b + "intermediate.dense.weight"), GWP(b + "fc1T"), 4 * C, C, 4 * C, 0, st));
+      CKS(launch_transpose_convert(dt, wt + p->poff.at(b + "output.dense.weight"), GWP(b + "fc2T"), C, 4 * C, C, 0, st));
+    }
+    if (s < 3) {
+      const std::string d = "encoder.layers." + std::to_string(s) + ".downsample.";
+      CKS(launch_transpose_convert(dt, wt + p->poff.at(d + "reduction.weight"), GWP(d + "redT"), 2 * C, 4 * C, 2 * C, 0, st));
+    }
+  }
+  p->gws_packed = grad_ws;
+  return 0;
+}
+
+extern "C" int m2t_swin_encode_grad(m2t_swin* p, const float* src_a, int n_a, const float* src_b, int n_b, int Hs, int Ws,
+                                    const int* crops_host, int n, int n_grad, float* emb, void* workspace, void* grad_ws, void* stream) {
+  if (!p || !grad_ws) return m2t_set_error(M2T_ERR_ARG, "m2t_swin_encode_grad: null");
+  if (n_grad < 1 || n_grad > n) return m2t_set_error(M2T_ERR_ARG, "m2t_swin_encode_grad: n_grad must be in [1, n]");
+  return encode_impl(p, src_a, n_a, src_b, n_b, Hs, Ws, crops_host, n, emb, workspace, n_grad, grad_ws, (hipStream_t)stream);
+}
+
+static int encode_impl(m2t_swin* p, const float* src, int n_a, const float* src_b, int n_b, int Hs, int Ws, const int* crops_host, int n,
+                       float* emb, void* workspace, int n_grad, void* grad_ws, hipStream_t st) {
   const int n_src = n_a + n_b;
   if (!p || !src || !crops_host || !emb || !workspace || n_a < 1 || n_b < 0 || (n_b > 0 && !src_b))
     return m2t_set_error(M2T_ERR_ARG, "m2t_swin_encode: null / bad source counts");
@@ -207,7 +312,19 @@ extern "C" int m2t_swin_encode_pair(m2t_swin* p, const float* src, int n_a, cons
     if (si < 0 || si >= n_src || y0 < 0 || x0 < 0 || y0 + 224 > Hs || x0 + 224 > Ws)
       return m2t_set_error(M2T_ERR_ARG, "m2t_swin_encode: crop outside its source image");
   }
-  hipStream_t st = (hipStream_t)stream;
+  const bool G = grad_ws != nullptr;
+  if (G) {
+    grad_layout(p, n_grad);
+    if (p->gws_packed != grad_ws) CKS(pack_grad_weights(p, grad_ws, st));
+    p->grad_n = 0;                     // until the stash below is complete
+    p->grad_ws = grad_ws;
+  }
+  // grad mode: the first n_grad crops' copy of a token tensor (contiguous rows at the front of the batch) into the stash
+  auto stash = [&](const void* from, const std::string& to, size_t elems_per_crop) -> int {
+    if (!G) return 0;
+    const hipError_t e2 = hipMemcpyAsync(GWP(to), from, elems_per_crop * n_grad * p->esz, hipMemcpyDeviceToDevice, st);
+    return e2 == hipSuccess ? 0 : m2t_set_hip_error(e2, __FILE__, __LINE__);
+  };
   const int dt = p->dt;
   const float* wt = p->weights;
   hipError_t e = hipSuccess;
@@ -238,6 +355,7 @@ extern "C" int m2t_swin_encode_pair(m2t_swin* p, const float* src, int n_a, cons
   long long M = (long long)n * 3136;
   CKS(swin_gemm(dt, M2T_E_BIAS, SWP("A0"), 48, spk(p, workspace, "pe"), X, 96, M,
                 wt + p->poff.at("embeddings.patch_embeddings.projection.bias"), nullptr, st));
+  CKS(stash(X, "e0", 3136 * 96));
   CKS(launch_layernorm(dt, X, wt + p->poff.at("embeddings.norm.weight"), wt + p->poff.at("embeddings.norm.bias"), X, M, 96, st));
   int H = 56;
   for (int s = 0; s < 4; ++s) {
@@ -245,10 +363,28 @@ extern "C" int m2t_swin_encode_pair(m2t_swin* p, const float* src, int n_a, cons
     for (int j = 0; j < DEPTHS[s]; ++j) {
       const std::string b = "encoder.layers." + std::to_string(s) + ".blocks." + std::to_string(j) + ".";
       const int shift = (j % 2 == 0 || H <= 7) ? 0 : 3;
+      const std::string sb = "s" + std::to_string(s) + "b" + std::to_string(j) + ".";
+      const size_t tc = (size_t)(H * H) * C;
+      CKS(stash(X, sb + "xin", tc));
       CKS(launch_layernorm(dt, X, wt + p->poff.at(b + "layernorm_before.weight"), wt + p->poff.at(b + "layernorm_before.bias"), Hn, M, C, st));
       CKS(swin_gemm(dt, M2T_E_BIAS, Hn, C, spk(p, workspace, b + "qkv"), QKV, 3 * C, M, fbias + p->fb.at(b + "qkv_bias"), nullptr, st));
+      CKS(stash(QKV, sb + "qkv", 3 * tc));
       CKS(launch_swin_attn(dt, QKV, wt + p->poff.at(b + "attention.self.relative_position_bias_table"), AO, n, H, H, C, HEADS[s], shift, st));
       CKS(swin_gemm(dt, M2T_E_BIAS_RESID, AO, C, spk(p, workspace, b + "o"), X, C, M, wt + p->poff.at(b + "attention.output.dense.bias"), X, st));
+      CKS(stash(X, sb + "xmid", tc));
+      if (G) {
+        // fc1 + bias + GELU storing gelu'(t) beside gelu(t) (the bias / GELU / derivative epilogue of gemm_nt with a trivial
+        // 1 x 1 shuffle; fp32: the same accumulation and the same erf GELU as M2T_E_BIAS_GELU, so emb is bit-identical)
+        CKS(launch_layernorm(dt, X, wt + p->poff.at(b + "layernorm_after.weight"), wt + p->poff.at(b + "layernorm_after.bias"), Hn, M, C, st));
+        m2t_gemm_args ga{};
+        ga.A = Hn; ga.lda = C; ga.W = spk(p, workspace, b + "fc1"); ga.Y = MH; ga.ldy = 4 * C; ga.Y2 = GWP("MD");
+        ga.bias = wt + p->poff.at(b + "intermediate.dense.bias"); ga.M = M; ga.N = 4 * C; ga.K = C;
+        ga.H = 1; ga.Wd = 1; ga.r = 1; ga.C = 4 * C;
+        CKS(launch_gemm_nt(dt, M2T_A_PLAIN, M2T_E_BIAS_SHUF, ga, st));
+        CKS(stash(GWP("MD"), sb + "gder", 4 * tc));
+        CKS(swin_gemm(dt, M2T_E_BIAS_RESID, MH, 4 * C, spk(p, workspace, b + "fc2"), X, C, M, wt + p->poff.at(b + "output.dense.bias"), X, st));
+        continue;
+      }
       if (dt != M2T_F32 && s < 2 && p->fused_mlp) {
         // LayerNorm + fc1 + GELU + fc2 + residual in one kernel: the 4C-wide hidden tensor stays in LDS
         CKS(launch_swin_mlp_fused(X, wt + p->poff.at(b + "layernorm_after.weight"), wt + p->poff.at(b + "layernorm_after.bias"),
@@ -263,14 +399,84 @@ extern "C" int m2t_swin_encode_pair(m2t_swin* p, const float* src, int n_a, cons
     if (s < 3) {
       const std::string d = "encoder.layers." + std::to_string(s) + ".downsample.";
       CKS(launch_swin_merge_gather(dt, X, Hn, n, H, H, C, st));
+      CKS(stash(Hn, "m" + std::to_string(s), (size_t)(H * H) * C));
       M /= 4; H /= 2;
       CKS(launch_layernorm(dt, Hn, wt + p->poff.at(d + "norm.weight"), wt + p->poff.at(d + "norm.bias"), Hn, M, 4 * C, st));
       CKS(swin_gemm(dt, M2T_E_PLAIN, Hn, 4 * C, spk(p, workspace, d + "red"), X, 2 * C, M, nullptr, nullptr, st));
     }
   }
+  CKS(stash(X, "xf", 49 * 768));
   CKS(launch_layernorm(dt, X, wt + p->poff.at("layernorm.weight"), wt + p->poff.at("layernorm.bias"), Hn, M, 768, st));
+  CKS(stash(Hn, "hnf", 49 * 768));
   CKS(launch_swin_head(dt, Hn, wt + p->poff.at("projection_head.weight"), emb, n, st));
+  if (G) p->grad_n = n_grad;
   return 0;
+}
+
+static int swin_gemm_g(int dt, int emode, const void* A, int K, const void* W, void* Y, int N, long long M, const void* aux, hipStream_t st) {
+  m2t_gemm_args ga{};
+  ga.A = A; ga.lda = K; ga.W = W; ga.Y = Y; ga.ldy = N; ga.aux = aux; ga.ldaux = N;
+  ga.M = M; ga.N = N; ga.K = K; ga.H = 1; ga.Wd = 1; ga.r = 1; ga.C = 64;
+  return launch_gemm_nt(dt, M2T_A_PLAIN, emode, ga, st);
+}
+
+// vector-Jacobian product of encode_image for the n_grad crops stashed by the last m2t_swin_encode_grad:
+// g_emb [n_grad,512] -> g_crops [n_grad,3,224,224] fp32 (overwritten)
+extern "C" int m2t_swin_backward(m2t_swin* p, const float* g_emb, int n_grad, float* g_crops, void* workspace, void* grad_ws, void* stream) {
+  if (!p || !g_emb || !g_crops || !workspace || !grad_ws) return m2t_set_error(M2T_ERR_ARG, "m2t_swin_backward: null");
+  if (!p->weights) return m2t_set_error(M2T_ERR_STATE, "m2t_swin_backward: call m2t_swin_load_weights first");
+  if (p->grad_n < 1 || p->grad_n != n_grad || p->grad_ws != grad_ws || p->gws_packed != grad_ws)
+    return m2t_set_error(M2T_ERR_STATE, "m2t_swin_backward: needs m2t_swin_encode_grad with the same n_grad and grad workspace first");
+  grad_layout(p, n_grad);
+  hipStream_t st = (hipStream_t)stream;
+  const int dt = p->dt;
+  const float* wt = p->weights;
+  float *gR = (float*)GWP("gR"), *gF = (float*)GWP("gF");
+  void *gT = GWP("gT"), *gC = GWP("gC"), *gQ = GWP("gQ"), *gA = GWP("gA");
+  const int ng = n_grad;
+  CKS(launch_swin_head_bwd(dt, GWP("hnf"), wt + p->poff.at("projection_head.weight"), g_emb, gC, ng, st));
+  CKS(launch_layernorm_bwd(dt, GWP("xf"), gC, wt + p->poff.at("layernorm.weight"), nullptr, gR, gT, (long long)ng * 49, 768, st));
+  for (int s = 3; s >= 0; --s) {
+    const int H = 56 >> s, C = 96 << s;
+    const long long M = (long long)ng * H * H;
+    for (int j = DEPTHS[s] - 1; j >= 0; --j) {
+      const std::string b = "encoder.layers." + std::to_string(s) + ".blocks." + std::to_string(j) + ".";
+      const std::string sb = "s" + std::to_string(s) + "b" + std::to_string(j) + ".";
+      const int shift = (j % 2 == 0 || H <= 7) ? 0 : 3;
+      // MLP: d(fc1 out) = (g W2) o gelu'(t); d(LN2 out) = that W1; + LayerNorm backward into the residual stream
+      CKS(swin_gemm_g(dt, M2T_E_GELU_GRAD, gT, C, GWP(b + "fc2T"), gA, 4 * C, M, GWP(sb + "gder"), st));
+      CKS(swin_gemm_g(dt, M2T_E_PLAIN, gA, 4 * C, GWP(b + "fc1T"), gC, C, M, nullptr, st));
+      CKS(launch_layernorm_bwd(dt, GWP(sb + "xmid"), gC, wt + p->poff.at(b + "layernorm_after.weight"), gR, gR, gT, M, C, st));
+      // attention: o_proj^T, window attention, qkv^T, LayerNorm backward into the residual stream
+      CKS(swin_gemm_g(dt, M2T_E_PLAIN, gT, C, GWP(b + "oT"), gC, C, M, nullptr, st));
+      CKS(launch_swin_attn_bwd(dt, GWP(sb + "qkv"), wt + p->poff.at(b + "attention.self.relative_position_bias_table"), gC, gQ, ng, H, H, C,
+                               HEADS[s], shift, st));
+      CKS(swin_gemm_g(dt, M2T_E_PLAIN, gQ, 3 * C, GWP(b + "qkvT"), gC, C, M, nullptr, st));
+      CKS(launch_layernorm_bwd(dt, GWP(sb + "xin"), gC, wt + p->poff.at(b + "layernorm_before.weight"), gR, gR, gT, M, C, st));
+    }
+    if (s > 0) {
+      // patch merging of stage s - 1 (C' = C / 2 channels at 2H x 2H): reduction^T, LayerNorm backward (4 C'), scatter
+      const std::string d = "encoder.layers." + std::to_string(s - 1) + ".downsample.";
+      CKS(swin_gemm_g(dt, M2T_E_PLAIN, gT, C, GWP(d + "redT"), gC, 2 * C, M, nullptr, st));
+      CKS(launch_layernorm_bwd(dt, GWP("m" + std::to_string(s - 1)), gC, wt + p->poff.at(d + "norm.weight"), nullptr, gF, nullptr, M, 2 * C, st));
+      CKS(launch_swin_merge_scatter(dt, gF, gR, gT, ng, 2 * H, 2 * H, C / 2, st));
+    }
+  }
+  // embedding LayerNorm (its incoming gradient is the fp32 residual stream) and the patch projection^T + patchify adjoint, fp32
+  CKS(launch_layernorm_bwd(dt, GWP("e0"), nullptr, wt + p->poff.at("embeddings.norm.weight"), nullptr, gF, nullptr, (long long)ng * 3136, 96, st,
+                           1e-5f, gR));
+  CKS(launch_swin_embed_bwd(gF, wt + p->poff.at("embeddings.patch_embeddings.projection.weight"), g_crops, ng, st));
+  return 0;
+}
+
+extern "C" int m2t_semantic_loss_backward(const float* emb, const float* text, int B, int n_patches, float* g_emb, void* stream) {
+  if (!emb || !text || !g_emb || B < 1 || n_patches < 1) return m2t_set_error(M2T_ERR_ARG, "m2t_semantic_loss_backward: bad argument");
+  return launch_semantic_loss_bwd(emb, text, B, n_patches, g_emb, (hipStream_t)stream);
+}
+extern "C" int m2t_bicubic_resize_backward(const float* g_dst, float* g_src, int NC, int Hin, int Win, int Hout, int Wout, void* stream) {
+  if (!g_dst || !g_src || NC < 1 || Hin < 1 || Win < 1 || Hout < 1 || Wout < 1)
+    return m2t_set_error(M2T_ERR_ARG, "m2t_bicubic_resize_backward: bad argument");
+  return launch_bicubic_resize_bwd(g_dst, g_src, NC, Hin, Win, Hout, Wout, (hipStream_t)stream);
 }
 
 extern "C" int m2t_semantic_loss(const float* emb, const float* text, int B, int n_patches, float* per_sample, float* total,

@@ -57,6 +57,7 @@ class SwinEncoder:
             self.slots[n] = (self.query("param:" + n), self.query("numel:" + n))
         self.flat = torch.zeros(self.query("num_params"), dtype=torch.float32, device=device)
         self.workspace = torch.empty(self.query("workspace_bytes"), dtype=torch.uint8, device=device)
+        self.grad_workspace = None         # allocated on the first encode_grad (differentiable SemanticLoss only)
         self.loaded = False
 
     def query(self, key: str) -> int:
@@ -115,6 +116,39 @@ class SwinEncoder:
                                                         src_a.shape[2], src_a.shape[3], arr, n, _lib.ptr(emb), _lib.ptr(self.workspace),
                                                         _lib.stream_ptr()), "m2t_swin_encode_pair")
         return emb
+
+    def encode_grad(self, src_a: torch.Tensor, src_b: Optional[torch.Tensor], crops: Sequence[Sequence[int]], n_grad: int) -> torch.Tensor:
+        """``encode_pair`` that also keeps what ``backward`` needs for the first ``n_grad`` crops (src_b may be None)."""
+        if not self.loaded:
+            raise M2TError("SwinEncoder: weights not loaded")
+        lib = _lib.load()
+        if self.grad_workspace is None:
+            self.grad_workspace = torch.empty(int(lib.m2t_swin_grad_workspace_bytes(self.handle, self.max_images // 2)),
+                                              dtype=torch.uint8, device=self.device)
+        if not 1 <= n_grad <= self.max_images // 2:
+            raise M2TError(f"SwinEncoder.encode_grad: n_grad {n_grad} outside [1, {self.max_images // 2}]")
+        src_a = src_a.contiguous().float()
+        n_b = 0
+        if src_b is not None:
+            src_b = src_b.contiguous().float()
+            n_b = src_b.shape[0]
+        n = len(crops)
+        arr = (C.c_int * (3 * n))(*[int(v) for c in crops for v in c])
+        emb = torch.empty(n, 512, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(lib.m2t_swin_encode_grad(self.handle, _lib.ptr(src_a), src_a.shape[0], _lib.ptr(src_b), n_b, src_a.shape[2],
+                                                src_a.shape[3], arr, n, n_grad, _lib.ptr(emb), _lib.ptr(self.workspace),
+                                                _lib.ptr(self.grad_workspace), _lib.stream_ptr()), "m2t_swin_encode_grad")
+        return emb
+
+    def backward(self, g_emb: torch.Tensor, n_grad: int) -> torch.Tensor:
+        """vector-Jacobian product of the last ``encode_grad``: g_emb [n_grad,512] -> g_crops [n_grad,3,224,224] fp32"""
+        g_emb = g_emb.contiguous().float()
+        g = torch.empty(n_grad, 3, 224, 224, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().m2t_swin_backward(self.handle, _lib.ptr(g_emb), n_grad, _lib.ptr(g), _lib.ptr(self.workspace),
+                                                     _lib.ptr(self.grad_workspace), _lib.stream_ptr()), "m2t_swin_backward")
+        return g
 
     def __del__(self):
         try:
@@ -211,8 +245,12 @@ def hash_text_feature(caption: str) -> torch.Tensor:
 
 class SemanticLoss(nn.Module):
     def __init__(self, criterion: str = "l1", N_patches: int = 3, device=None, compute_dtype: str = "fp32",
-                 max_batch: int = 32, synthetic_text: bool = False):
+                 max_batch: int = 32, synthetic_text: bool = False, differentiable: bool = False):
         super().__init__()
+        # differentiable=True (opt-in): batch() / __call__ return a tensor connected to `sr` (when sr.requires_grad), with the gradient
+        # the paper's regulariser needs -- the reference's no_grad term (losses.py:63) taken out of no_grad.  The value, the RNG
+        # consumption and the last-patch quirk are unchanged; the MedCLIP towers stay frozen (data gradient only).
+        self.differentiable = bool(differentiable)
         # synthetic_text=True (benchmarks / tests with no MedCLIP weights): a caption without an injected text feature
         # gets a deterministic hash embedding.  The default is to RAISE: a silent stand-in behind a drop-in surface
         # would log a wrong regulariser value (the reference loads the real text tower itself, losses.py:22-23).
@@ -221,6 +259,8 @@ class SemanticLoss(nn.Module):
         self.N_patches = int(N_patches)
         self.compute_dtype = compute_dtype
         self.max_batch = int(max_batch)
+        if self.differentiable and self.device.type != "cuda":
+            raise M2TError("SemanticLoss(differentiable=True) needs a HIP device: the Swin-T data gradient has no CPU implementation")
         self._enc: Optional[SwinEncoder] = None
         self._state: Optional[Dict[str, torch.Tensor]] = None
         self._text: Dict[str, torch.Tensor] = {}
@@ -320,7 +360,25 @@ class SemanticLoss(nn.Module):
 
     def batch(self, sr: torch.Tensor, hr: torch.Tensor, captions: Iterable[str]) -> torch.Tensor:
         """Sum over the batch of loss_clip(sr[i], hr[i], captions[i]) (train.py:203-205, without the
-        lambda_clip factor) -> Tensor[1]; also leaves the per-sample values in ``self.last_per_sample``."""
+        lambda_clip factor) -> Tensor[1]; also leaves the per-sample values in ``self.last_per_sample``.
+        With ``differentiable=True`` and ``sr.requires_grad`` the result is connected to ``sr``: d total / d sr is computed
+        here (an eager vector-Jacobian product: the output is a scalar), and the autograd backward only scales and returns it."""
+        if self.differentiable and sr.requires_grad and torch.is_grad_enabled():
+            tot, g, origins = self._value_and_grad(sr, hr, captions)
+            return _SemanticLossGrad.apply(sr, tot, g, origins)
+        tot, _, _ = self._run(sr, hr, captions, want_grad=False)
+        return tot
+
+    def _value_and_grad(self, sr: torch.Tensor, hr: torch.Tensor, captions):
+        """(total [1], g, origins): d total / d sr as g [B,C,gh,gw] with per-sample (row0, col0) origins (the last random crop),
+        or the dense gradient and origins None (N_patches == 1).  A 1-channel sr is differentiated through the channel repeat."""
+        c = sr.shape[1]
+        tot, g, origins = self._run(sr, hr, captions, want_grad=True)
+        if c != 3:
+            g = g.sum(dim=1, keepdim=True)
+        return tot, g, origins
+
+    def _run(self, sr: torch.Tensor, hr: torch.Tensor, captions, want_grad: bool):
         captions = list(captions)
         B = sr.shape[0]
         if len(captions) != B or tuple(sr.shape) != tuple(hr.shape):
@@ -331,20 +389,28 @@ class SemanticLoss(nn.Module):
         if 2 * B > enc.max_images:
             raise M2TError(f"batch {B} exceeds max_batch {self.max_batch}")
         hs, ws = sr.shape[2], sr.shape[3]
+        g, origins = None, None
         with torch.no_grad():
             if self.N_patches > 1:
                 last = []
                 for _ in range(B):                                       # same RNG order as B sequential calls
                     last.append(self.createNRandompatches(hs, ws, self.N_patches - 1)[-1])
                 crops = [(i, last[i][0], last[i][1]) for i in range(B)] + [(B + i, last[i][0], last[i][1]) for i in range(B)]
-                emb = enc.encode_pair(sr.detach(), hr.detach(), crops)   # SR crops then HR crops, no torch.cat of the batches
+                if want_grad:
+                    emb = enc.encode_grad(sr.detach(), hr.detach(), crops, B)
+                    origins = [(int(last[i][0]), int(last[i][1])) for i in range(B)]
+                else:
+                    emb = enc.encode_pair(sr.detach(), hr.detach(), crops)   # SR crops then HR crops, no torch.cat of the batches
             else:
                 src = torch.cat((sr.detach().float(), hr.detach().float()), dim=0).contiguous()
                 small = torch.empty(2 * B, 3, 224, 224, dtype=torch.float32, device=sr.device)
                 with torch.cuda.device(sr.device):
                     _lib.check(_lib.load().m2t_bicubic_resize(_lib.ptr(src), _lib.ptr(small), 2 * B * 3, hs, ws, 224, 224,
                                                               _lib.stream_ptr()), "m2t_bicubic_resize")
-                emb = enc.encode(small, [(i, 0, 0) for i in range(2 * B)])
+                if want_grad:
+                    emb = enc.encode_grad(small, None, [(i, 0, 0) for i in range(2 * B)], B)
+                else:
+                    emb = enc.encode(small, [(i, 0, 0) for i in range(2 * B)])
             dev = sr.device
             key = tuple(captions)
             if self._text_dev is None or self._text_dev[0] != key or self._text_dev[1].device != dev:
@@ -356,10 +422,50 @@ class SemanticLoss(nn.Module):
             with torch.cuda.device(dev):
                 _lib.check(_lib.load().m2t_semantic_loss(_lib.ptr(emb), _lib.ptr(text), B, self.N_patches, _lib.ptr(per),
                                                          _lib.ptr(tot), _lib.stream_ptr()), "m2t_semantic_loss")
+                if want_grad:
+                    lib = _lib.load()
+                    g_emb = torch.empty(B, 512, dtype=torch.float32, device=dev)
+                    _lib.check(lib.m2t_semantic_loss_backward(_lib.ptr(emb), _lib.ptr(text), B, self.N_patches, _lib.ptr(g_emb),
+                                                              _lib.stream_ptr()), "m2t_semantic_loss_backward")
+                    g_crops = enc.backward(g_emb, B)
+                    if self.N_patches > 1:
+                        g = g_crops
+                    else:
+                        g = torch.empty(B, 3, hs, ws, dtype=torch.float32, device=dev)
+                        _lib.check(lib.m2t_bicubic_resize_backward(_lib.ptr(g_crops), _lib.ptr(g), B * 3, hs, ws, 224, 224,
+                                                                   _lib.stream_ptr()), "m2t_bicubic_resize_backward")
         self.last_per_sample = per
         self.last_embeddings = emb            # [2B,512]: SR rows then HR rows, unit norm (kept for inspection)
-        return tot
+        return tot, g, origins
 
     def __call__(self, x: torch.Tensor, y: torch.Tensor, batch_tokens: str) -> torch.Tensor:
         """Single sample, as called by train.py:205: x, y [3,Hs,Ws] (or [1,Hs,Ws]) -> Tensor[1]."""
         return self.batch(x.unsqueeze(0).to(self.device), y.unsqueeze(0).to(self.device), [batch_tokens])
+
+
+def paste_crops(g: torch.Tensor, origins, shape) -> torch.Tensor:
+    """Dense [B,C,H,W] gradient from per-sample blocks g [B,C,gh,gw] at (row0, col0) origins (None: g is dense already)."""
+    if origins is None:
+        return g
+    out = torch.zeros(shape, dtype=g.dtype, device=g.device)
+    gh, gw = g.shape[2], g.shape[3]
+    for i, (y0, x0) in enumerate(origins):
+        out[i, :, y0:y0 + gh, x0:x0 + gw] = g[i]
+    return out
+
+
+class _SemanticLossGrad(torch.autograd.Function):
+    """Edge from the SemanticLoss total to sr.  The gradient was computed eagerly with the value (a scalar output: one
+    vector-Jacobian product), so nothing of the encoder is kept across calls; backward scales it by the upstream gradient."""
+
+    @staticmethod
+    def forward(ctx, sr, tot, g, origins):
+        ctx.origins = origins
+        ctx.shape = tuple(sr.shape)
+        ctx.save_for_backward(g)
+        return tot.clone()
+
+    @staticmethod
+    def backward(ctx, go):
+        (g,) = ctx.saved_tensors
+        return paste_crops(g * go.reshape(()), ctx.origins, ctx.shape).to(go.dtype), None, None, None

@@ -18,6 +18,7 @@ count, so SUM-all-reduced gradients equal the full-batch gradient (SURVEY sectio
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 from typing import Optional
 
@@ -60,7 +61,8 @@ class TrainStep:
         self.betas = (float(betas[0]), float(betas[1]))
         self.eps = float(eps)
         self.lambda_l1 = float(lambda_l1)
-        # the MedCLIP regulariser (train.py:78,203-205): a no-grad constant added to the logged loss
+        # the MedCLIP regulariser (train.py:78,203-205): a no-grad constant added to the logged loss, or -- with
+        # SemanticLoss(differentiable=True) -- a term whose gradient reaches the weights (_forward_backward_semantic_grad)
         self.semantic_loss = semantic_loss
         self.lambda_clip = float(lambda_clip)
         self.clip_loss = None
@@ -108,6 +110,8 @@ class TrainStep:
             raise _lib.M2TError("hr shape must be [B,3,H*scale,W*scale]")
         divisor = global_divisor(hr_img.numel(), self.world_size)      # global mean (equal shards)
         use_clip = self.semantic_loss is not None and self.lambda_clip > 0 and captions is not None
+        if use_clip and getattr(self.semantic_loss, "differentiable", False):
+            return self._forward_backward_semantic_grad(m, lib, plan, lr_img, hr_img, captions, divisor)
         sr = torch.empty_like(hr_img) if use_clip else None
         plan.gen += 1
         plan.trained = True              # (the plan LRU of the model keeps training plans while forward-only ones remain)
@@ -142,6 +146,37 @@ class TrainStep:
             self.loss = self.l1_loss + self.clip_loss
         else:
             self.loss = self.l1_loss
+        return self.loss
+
+    def _forward_backward_semantic_grad(self, m, lib, plan, lr_img, hr_img, captions, divisor):
+        """The route of a differentiable SemanticLoss: forward -> semantic encode (the SR crops stash what the encoder's backward
+        needs, the HR crops do not) -> its vector-Jacobian product -> m2t_l1_loss (a MATERIALISED seed: the fused-L1 seed of the
+        default route, m2t_l1_loss_deferred, does not apply here) -> m2t_add_output_grad(lambda_clip) -> m2t_backward.  HIP kernels
+        only, one stream.  The semantic term is a per-sample SUM on every rank, so a SUM all-reduce of the gradients equals the
+        gradient of the global-batch sum without rescaling (as the reference's DataParallel gather)."""
+        sl = self.semantic_loss
+        sr = torch.empty_like(hr_img)
+        plan.gen += 1
+        plan.trained = True
+        self._last_plan = plan
+        with torch.cuda.device(lr_img.device):
+            st = _lib.stream_ptr()
+            ws = _lib.ptr(plan.workspace)
+            _lib.check(lib.m2t_forward(plan.handle, _lib.ptr(m.flat_params), _lib.ptr(lr_img), _lib.ptr(sr),
+                                       float(m.rgb_range), 1, ws, st), "m2t_forward")
+            tot, g, origins = sl._value_and_grad(sr, hr_img, captions)
+            _lib.check(lib.m2t_l1_loss(plan.handle, _lib.ptr(hr_img), self.lambda_l1, divisor, float(m.rgb_range),
+                                       _lib.ptr(self.l1_loss), ws, st), "m2t_l1_loss")
+            g = g.contiguous()
+            arr = None
+            if origins is not None:
+                arr = (C.c_int * (2 * len(origins)))(*[int(v) for o in origins for v in o])
+            _lib.check(lib.m2t_add_output_grad(plan.handle, _lib.ptr(g), g.shape[2], g.shape[3], arr, self.lambda_clip,
+                                               float(m.rgb_range), ws, st), "m2t_add_output_grad")
+            _lib.check(lib.m2t_backward(plan.handle, _lib.ptr(m.flat_params), _lib.ptr(lr_img), _lib.ptr(self.grads),
+                                        ws, st), "m2t_backward")
+        self.clip_loss = tot * self.lambda_clip
+        self.loss = self.l1_loss + self.clip_loss
         return self.loss
 
     def all_reduce_grads(self):
