@@ -126,7 +126,8 @@ int m2t_set_option(m2t_plan* p, const char* key, long long value);
  * m2t_backward completes the flat gradient buffer in "grad_buckets" contiguous ranges, in this order: tail, block
  * pairs from the last to the first, head.  m2t_plan_query("grad_bucket_lo:<i>" / "grad_bucket_hi:<i>") give bucket
  * i's float range; after m2t_backward has been ENQUEUED, m2t_stream_wait_bucket makes `stream` wait until bucket i
- * is final, so an all-reduce of that range can run under the rest of the backward pass. */
+ * is final, so an all-reduce of that range can run under the rest of the backward pass.  After an m2t_backward_ex pass with
+ * some stage flag clear, every bucket event marks the end of that whole pass. */
 int m2t_stream_wait_bucket(m2t_plan* p, int bucket, void* stream);
 /* one-time initialisation of the workspace (uploads the weight-packing table). */
 int m2t_plan_init_workspace(m2t_plan* p, void* workspace, void* stream);
@@ -161,6 +162,19 @@ int m2t_add_output_grad(m2t_plan* p, const float* g, int gh, int gw, const int* 
  * params; every element is written). */
 int m2t_backward(m2t_plan* p, const float* params, const float* x, float* grads, void* workspace,
                  void* stream);
+/* m2t_backward with a choice of outputs (torch's requires_grad on the input and on whole stages of the model).
+ * need_stage: host array of n_blocks + 2 flags in state_dict order -- [0] head, [1 + b] body.b, [n_blocks + 1] tail -- or NULL =
+ * every stage.  A stage's contiguous range of grads is written iff its flag is set (other ranges are not touched); grads may be
+ * NULL when no flag is set.  x is read only when the head's flag is set.  gx: NULL, or the gradient with respect to the input,
+ * fp32 NCHW [B,3,H0,W0] (every element written; deterministic).  The data-gradient chain runs from the tail down to the lowest
+ * stage that is needed, or to the input when gx != NULL.  need_stage = NULL and gx = NULL launch exactly what m2t_backward
+ * launches.  A pass with some flag clear never changes the plan's reduction table (the first pass with a given set of flags
+ * uploads a table of its own, so it cannot be captured into a graph; later ones can); after it, every gradient bucket event is
+ * recorded at its end: m2t_stream_wait_bucket then waits for the whole pass.  No flag set: no side-stream work at all.
+ * M2T_ERR_ARG: nothing requested (no flag, gx NULL), a flag set with grads NULL, the head's flag set with x NULL;
+ * M2T_ERR_STATE: no forward with saved activations or no seed (the seed is consumed, as by m2t_backward). */
+int m2t_backward_ex(m2t_plan* p, const float* params, const float* x, float* grads, float* gx,
+                    const unsigned char* need_stage, void* workspace, void* stream);
 /* torch.optim.Adam(lr, betas, eps, weight_decay=0).step() (train.py:81,210), fused over the flat
  * buffers; step = 1-based count; grad_scale multiplies g first (1/world_size after a SUM all-reduce). */
 int m2t_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n,

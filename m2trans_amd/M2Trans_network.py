@@ -28,6 +28,7 @@ from typing import Dict, List, Tuple
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import M2TError
@@ -98,7 +99,9 @@ class Plan:
 
 class _M2TransFunction(torch.autograd.Function):
     """One autograd node around the whole network: forward = m2t_forward, backward =
-    m2t_set_output_grad + m2t_backward (hand-written kernels, no autograd graph inside)."""
+    m2t_set_output_grad + m2t_backward (hand-written kernels, no autograd graph inside).
+    When the input requires grad or some stage of the model is frozen (no parameter of it requires grad), the backward is
+    m2t_backward_ex: frozen stages do no parameter-gradient work, and the input gradient comes from the head conv's adjoint."""
 
     @staticmethod
     def forward(ctx, x, model, *params):
@@ -113,6 +116,7 @@ class _M2TransFunction(torch.autograd.Function):
         return sr
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_sr):
         model, plan = ctx.model, ctx.plan
         if ctx.gen != plan.gen:
@@ -120,19 +124,30 @@ class _M2TransFunction(torch.autograd.Function):
                            "call backward before the next forward of the same shape")
         (x,) = ctx.saved_tensors
         lib = _lib.load()
+        need_x = bool(ctx.needs_input_grad[0])
+        need_p = ctx.needs_input_grad[2:]
+        stages = model.stage_flags(need_p)
         g_sr = g_sr.contiguous().float()
+        gx = None
         with torch.cuda.device(x.device):
             st = _lib.stream_ptr()
             _lib.check(lib.m2t_set_output_grad(plan.handle, _lib.ptr(g_sr), float(model.rgb_range),
                                                _lib.ptr(plan.workspace), st), "m2t_set_output_grad")
-            grads = torch.empty_like(model.flat_params)
-            _lib.check(lib.m2t_backward(plan.handle, _lib.ptr(model.flat_params), _lib.ptr(x), _lib.ptr(grads),
-                                        _lib.ptr(plan.workspace), st), "m2t_backward")
-        plan.trained = True
+            grads = torch.empty_like(model.flat_params) if any(stages) else None
+            if all(stages) and not need_x:
+                _lib.check(lib.m2t_backward(plan.handle, _lib.ptr(model.flat_params), _lib.ptr(x), _lib.ptr(grads),
+                                            _lib.ptr(plan.workspace), st), "m2t_backward")
+            else:
+                gx = torch.empty(x.shape, dtype=torch.float32, device=x.device) if need_x else None
+                flags = (C.c_ubyte * len(stages))(*[1 if f else 0 for f in stages])
+                _lib.check(lib.m2t_backward_ex(plan.handle, _lib.ptr(model.flat_params), _lib.ptr(x), _lib.ptr(grads),
+                                               _lib.ptr(gx), flags, _lib.ptr(plan.workspace), st), "m2t_backward_ex")
+        if grads is not None:
+            plan.trained = True
         if model._dp_master is not None:
             model._dp_release()
-        outs = [grads[o: o + n].view(s) for (o, n, s) in model._slots]
-        return (None, None, *outs)
+        outs = [grads[o: o + n].view(s) if need else None for (o, n, s), need in zip(model._slots, need_p)]
+        return (gx, None, *outs)
 
 
 class _ReplicaState:
@@ -353,6 +368,42 @@ class M2Trans(nn.Module):
                 p.grad = self.flat_grads[o: o + k].view(s)
         return self.flat_grads
 
+    def stage_flags(self, requires=None) -> List[bool]:
+        """The stage flags of m2t_backward_ex -- [head, body.0 .. body.{n_blocks-1}, tail] -- from one requires-grad flag per trainable
+        parameter (state_dict order; default: each parameter's ``requires_grad``).  A stage is needed if any of its parameters is."""
+        if requires is None:
+            requires = [p.requires_grad for _, p in self._trainable()]
+        flags = [False] * (self.n_blocks + 2)
+        for n, r in zip(self._names, requires):
+            if not r:
+                continue
+            if n.startswith("head."):
+                flags[0] = True
+            elif n.startswith("body."):
+                flags[1 + int(n.split(".")[1])] = True
+            else:
+                flags[self.n_blocks + 1] = True
+        return flags
+
+    # ------------------------------------------------------------------ copy.deepcopy / pickle (torch.save(model))
+    _UNCOPIED = ("_dp_lock", "_dp_pool", "_plans", "_dp_master", "_dp_params", "_dp_release", "flat_params", "flat_grads")
+
+    def __getstate__(self):
+        """A copy shares nothing that belongs to the device state of this module: no lock, no plans (a shared plan's C handle
+        would be destroyed twice), no DataParallel pool.  The flat buffer is rebuilt from the copied parameters."""
+        state = self.__dict__.copy()
+        for k in self._UNCOPIED:
+            state.pop(k, None)
+        return state
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self._dp_master = None
+        self._dp_params = None
+        self._dp_release = None
+        self._dp_lock = threading.Lock()
+        self._flatten()                                      # parameters become views of the copy's own flat buffer; no plans
+
     def param_offsets(self) -> Dict[str, Tuple[int, int]]:
         return {n: (o, k) for n, (o, k, _) in zip(self._names, self._slots)}
 
@@ -450,7 +501,7 @@ class M2Trans(nn.Module):
             self._bind_replica(x)
         if torch.is_grad_enabled():                          # (the parameter walk only where an autograd edge may be needed)
             params = self._dp_params if self._dp_master is not None else [p for _, p in self._trainable()]
-            if any(p.requires_grad for p in params):
+            if x.requires_grad or any(p.requires_grad for p in params):
                 return _M2TransFunction.apply(x, self, *params)
         sr = self._run_forward(self._plan_for(x), x, keep=False)
         if self._dp_master is not None:

@@ -31,6 +31,7 @@ SIGNATURES = {
     "m2t_set_output_grad": (_i, [_vp, _vp, _f, _vp, _vp]),
     "m2t_add_output_grad": (_i, [_vp, _vp, _i, _i, C.POINTER(_i), _f, _f, _vp, _vp]),
     "m2t_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "m2t_backward_ex": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_ubyte), _vp, _vp]),
     "m2t_adam_step": (_i, [_vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _i, _f, _vp]),
     "m2t_profile_enable": (_i, [C.c_ulonglong]),
     "m2t_profile_read": (_i, [_i, C.POINTER(_d), C.POINTER(_ll)]),

@@ -132,6 +132,112 @@ int launch_head_im2col(int dt, const float* x, void* cols, int B, int H0, int W0
 }
 
 // =======================================================================================
+// head conv input gradient: the adjoint of res = head(reflect_pad_1(check_image_size(x))) (the only use of x)
+// g_res: P64 (T) [4][B*H*W][16] -> gx: fp32 NCHW [B][3][H0][W0].
+// A gather: source row sy collects every padded index i in [-1, H] with head_src(i, H, H0) == sy -- itself, its mirror
+// 2 H0 - 2 - sy through the pad to H (when that lies in [H0, H)), -1 (the conv's reflect: row 1) and H (reflects to H - 2) --
+// likewise for columns; every (row, column) preimage pair adds its 3 x 3 x 64 products of head.weight with g_res.  The pair
+// (sy, sx) itself reads g_res from an LDS tile (one 16-channel plane at a time, 1-pixel halo: g_res is read once); the other
+// pairs exist only near the borders and read global memory afterwards.  Fixed order per output, fp32, no atomics.
+// =======================================================================================
+#define HDG_TY 8
+#define HDG_TX 64          // a thread owns two pixels of a row, 32 apart: 8 x 32 threads
+#define HDG_CS 20          // LDS floats per pixel (16 channels + 4): lanes of a row read 80 bytes apart, no b128 bank conflicts
+__device__ __forceinline__ int head_preimages(int s, int n, int n0, int (&o)[4]) {
+  int k = 0;
+  o[k++] = s;
+  const int m = 2 * n0 - 2 - s;
+  if (m >= n0 && m < n) o[k++] = m;
+  if (head_src(-1, n, n0) == s) o[k++] = -1;
+  if (head_src(n, n, n0) == s) o[k++] = n;
+  return k;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) head_conv_dgrad_kernel(const T* __restrict__ g, const float* __restrict__ w,
+                                                              float* __restrict__ gx, int B, int H0, int W0, int H, int W) {
+  __shared__ f32x4 wsh[9][64];                          // [tap][oc] = (w[oc][0][tap], w[oc][1][tap], w[oc][2][tap], 0)
+  __shared__ float gs[HDG_TY + 2][HDG_TX + 2][HDG_CS];  // one 16-channel plane of g_res over the tile + halo
+  const int b = blockIdx.z, y0 = blockIdx.y * HDG_TY, x0 = blockIdx.x * HDG_TX;
+  for (int i = threadIdx.x; i < 9 * 64; i += 256) {
+    const int oc = i / 9, tap = i - 9 * oc;
+    wsh[tap][oc] = (f32x4){w[oc * 27 + tap], w[oc * 27 + 9 + tap], w[oc * 27 + 18 + tap], 0.f};
+  }
+  const int ty = threadIdx.x >> 5, tx = threadIdx.x & 31;
+  const int sy = y0 + ty, sx = x0 + tx;
+  const long long npix = (long long)B * H * W;
+  float acc[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+  for (int q = 0; q < 4; ++q) {
+    __syncthreads();                                    // weights staged / the previous plane consumed
+    const T* gq = g + (long long)q * npix * 16;
+    for (int i = threadIdx.x; i < (HDG_TY + 2) * (HDG_TX + 2) * 4; i += 256) {
+      const int c4 = i & 3, pix = i >> 2;
+      const int r = pix / (HDG_TX + 2), c = pix - (HDG_TX + 2) * r;
+      const int yy = y0 - 1 + r, xx = x0 - 1 + c;
+      float v[4] = {0.f, 0.f, 0.f, 0.f};
+      if (yy >= 0 && yy < H && xx >= 0 && xx < W) load4(gq + (((long long)b * H + yy) * W + xx) * 16 + 4 * c4, v);
+      *(f32x4*)&gs[r][c][4 * c4] = (f32x4){v[0], v[1], v[2], v[3]};
+    }
+    __syncthreads();
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const float* g0 = gs[ty + 2 - ky][tx + 2 - kx];   // padded row sy + 1 - ky, column sx + 1 - kx (and sx + 33 - kx)
+        const float* g1 = gs[ty + 2 - ky][tx + 34 - kx];
+        const f32x4* wr = &wsh[ky * 3 + kx][q * 16];
+#pragma unroll
+        for (int ch = 0; ch < 16; ++ch) {
+          const f32x4 wv = wr[ch];
+          const float a0 = g0[ch], a1 = g1[ch];
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            acc[0][c] = fmaf(wv[c], a0, acc[0][c]);
+            acc[1][c] = fmaf(wv[c], a1, acc[1][c]);
+          }
+        }
+      }
+  }
+  for (int p = 0; p < 2; ++p) {
+    const int px = sx + 32 * p;
+    if (sy >= H0 || px >= W0) continue;
+    int ry[4], rx[4];
+    const int ny = head_preimages(sy, H, H0, ry), nx = head_preimages(px, W, W0, rx);
+    float a[3] = {acc[p][0], acc[p][1], acc[p][2]};
+    for (int u = 0; u < ny; ++u)
+      for (int v = 0; v < nx; ++v) {
+        if (u == 0 && v == 0) continue;                  // (sy, px) itself: the LDS pass above
+        for (int ky = 0; ky < 3; ++ky)
+          for (int kx = 0; kx < 3; ++kx) {
+            const int yy = ry[u] + 1 - ky, xx = rx[v] + 1 - kx;
+            if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
+            const long long pix = ((long long)b * H + yy) * W + xx;
+            for (int q = 0; q < 4; ++q) {
+              float gv[16];
+              load16f(g + ((long long)q * npix + pix) * 16, gv);
+              const f32x4* wr = &wsh[ky * 3 + kx][q * 16];
+#pragma unroll
+              for (int ch = 0; ch < 16; ++ch) {
+                const f32x4 wv = wr[ch];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) a[c] = fmaf(wv[c], gv[ch], a[c]);
+              }
+            }
+          }
+      }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) gx[(((long long)b * 3 + c) * H0 + sy) * W0 + px] = a[c];
+  }
+}
+int launch_head_conv_dgrad(int dt, const void* g, const float* w, float* gx, int B, int H0, int W0, int H, int W, hipStream_t st) {
+  const dim3 grid(ceil_div(W0, HDG_TX), ceil_div(H0, HDG_TY), B);
+  if (dt == M2T_F32) hipLaunchKernelGGL(head_conv_dgrad_kernel<float>, grid, dim3(256), 0, st, (const float*)g, w, gx, B, H0, W0, H, W);
+  else hipLaunchKernelGGL(head_conv_dgrad_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)g, w, gx, B, H0, W0, H, W);
+  M2T_LAUNCH_CHECK();
+  return 0;
+}
+
+// =======================================================================================
 // 64 -> 64 3x3 conv, zero padding: implicit GEMM on the matrix cores.  All feature maps are P64.
 // Workgroup = 8 x 16 output pixels x 64 output channels; 4 waves, wave w owns pixel rows
 // 2w, 2w+1 (two 16-pixel m-tiles) x 4 channel tiles.  LDS: input halo tile 10x18x64 and the

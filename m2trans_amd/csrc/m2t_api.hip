@@ -217,6 +217,10 @@ struct m2t_plan {
   // region; the descriptor table is identical every step, so it is uploaded once
   std::vector<m2t_red_desc> red_descs;
   bool red_uploaded = false;
+  // m2t_backward_ex with some stages frozen: such a pass never publishes or checks the table above; it reduces everything once at
+  // its end through a table of its own stage mask, uploaded on the first pass with that mask into a plan-owned device buffer
+  struct MaskTable { std::vector<m2t_red_desc> descs; void* dev = nullptr; bool uploaded = false; };
+  std::map<std::vector<unsigned char>, MaskTable> mask_tables;
   size_t arena_floats = 0;
   hipStream_t side = nullptr;
   // gradient buckets: [lo, hi) float ranges of the flat gradient buffer in the order m2t_backward completes them
@@ -245,6 +249,7 @@ struct m2t_plan {
     for (auto e : bucket_events) if (e) (void)hipEventDestroy(e);
     // the caller releases the workspace right after this: nothing of the plan's own stream may still be running in it
     if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
+    for (auto& kv : mask_tables) if (kv.second.dev) (void)hipFree(kv.second.dev);
   }
 
   void add_param(const std::string& n, long long cnt) { pnames.push_back(n); poff[n] = nparams; pnum[n] = cnt; nparams += cnt; }
@@ -736,16 +741,31 @@ extern "C" int m2t_add_output_grad(m2t_plan* p, const float* g, int gh, int gw, 
 // Hazards are closed explicitly: gqkv/relw are double-buffered and re-used only after the
 // side stream's consumer of two branches ago has finished; a block's gy buffer is rewritten
 // only after the side stream's conv-wgrad of the following block has read it.
-extern "C" int m2t_backward(m2t_plan* p, const float* params, const float* x, float* grads, void* workspace,
-                            void* stream) {
-  if (!p || !params || !x || !grads || !workspace) return m2t_set_error(M2T_ERR_ARG, "m2t_backward: null argument");
-  if (!p->have_acts || !p->have_seed)
-    return m2t_set_error(M2T_ERR_STATE, "m2t_backward: needs m2t_forward and a seed (m2t_l1_loss / m2t_set_output_grad)");
+//
+// need_stage (m2t_backward_ex): n_blocks + 2 flags, head / body.b / tail, or NULL = every stage.  A clear flag drops that stage's
+// parameter-gradient launches (the same ones debug_skip_side drops); the data-gradient chain runs down to the lowest stage needed,
+// or to the input when gx != NULL.  Only the all-stages pass uses (and publishes) the plan's reduction table and its bucket events
+// as it goes; any other pass reduces once at its end through its mask's own table and then records every bucket event.
+static int backward_impl(m2t_plan* p, const float* params, const float* x, float* grads, float* gx_out,
+                         const unsigned char* need_stage, void* workspace, void* stream) {
+  const int nst = p->nb + 2;
+  std::vector<unsigned char> need(nst, 1);
+  if (need_stage)
+    for (int i = 0; i < nst; ++i) need[i] = need_stage[i] ? 1 : 0;
+  bool full = true, any = false, body_any = false;
+  for (int i = 0; i < nst; ++i) { full = full && need[i]; any = any || need[i]; }
+  for (int b = 0; b < p->nb; ++b) body_any = body_any || need[1 + b];
+  const bool need_head = need[0] != 0, need_tail = need[nst - 1] != 0;
+  // the data-gradient chain below the tail: needed by the head, a body stage or the input gradient
+  const bool chain_body = gx_out || need_head || body_any;
+  int lowest = p->nb;                        // lowest body block the chain reaches
+  if (gx_out || need_head) lowest = 0;
+  else for (int b = p->nb - 1; b >= 0; --b) if (need[1 + b]) lowest = b;
   g_m2t_f32_fast = p->use_fp32_fast;
   struct F32FastGuard { ~F32FastGuard() { g_m2t_f32_fast = 1; } } f32_fast_guard;
   hipStream_t st = (hipStream_t)stream;
   if (p->ensure_side(st) != 0) return m2t_set_error(M2T_ERR_STATE, "m2t_backward: cannot create the side stream / events");
-  hipStream_t sd = p->use_side ? p->side : st;
+  hipStream_t sd = (p->use_side && any) ? p->side : st;      // no parameter gradient at all: no side-stream work
   size_t evi = 0;
   auto next_event = [&]() -> hipEvent_t { return p->events[(evi++) % p->events.size()]; };
   // option "fork_on_kernel": arm_fork() in front of the launch the fork follows; the event then rides on that dispatch as its stop
@@ -806,7 +826,7 @@ extern "C" int m2t_backward(m2t_plan* p, const float* params, const float* x, fl
   };
   size_t bucket_i = 0;
   auto mark_bucket_on = [&](hipStream_t rs) {   // the gradient range of bucket_i is final on stream rs from here on
-    if (bucket_i < p->bucket_events.size() && p->red_uploaded) (void)hipEventRecord(p->bucket_events[bucket_i], rs);
+    if (full && bucket_i < p->bucket_events.size() && p->red_uploaded) (void)hipEventRecord(p->bucket_events[bucket_i], rs);
     ++bucket_i;
   };
   auto mark_bucket = [&]() { mark_bucket_on(sd); };
@@ -814,7 +834,7 @@ extern "C" int m2t_backward(m2t_plan* p, const float* params, const float* x, fl
   auto flush = [&]() -> int {        // one launch reduces everything deferred since the last flush
     if (overflow) return m2t_set_error(M2T_ERR_STATE, "m2t_backward: slab arena too small");
     if (descs.size() > 512) return m2t_set_error(M2T_ERR_STATE, "m2t_backward: too many deferred reductions");
-    if (!p->red_uploaded) return 0;  // first call: table not on the device yet, reduced at the end
+    if (!full || !p->red_uploaded) return 0;  // first call (or a partial pass): table not on the device yet, reduced at the end
     const int cnt = (int)(descs.size() - flushed);
     int rc = launch_multi_reduce(arena, grads, descs_dev + flushed, cnt, flush_stream);
     flushed = descs.size();
@@ -829,7 +849,8 @@ extern "C" int m2t_backward(m2t_plan* p, const float* params, const float* x, fl
   const void* last_act = (s == 4) ? WSP("t2act") : WSP("t1act");
   const void* last_der = (s == 4) ? WSP("t2der") : WSP("t1der");
   void* g_last = (s == 4) ? WSP("g_t2pre") : WSP("g_t1pre");
-  const bool skip = p->debug_skip_side;
+  const bool skip = p->debug_skip_side || !need_tail;         // (the tail's parameter-gradient work)
+  const bool skip_head = p->debug_skip_side || !need_head;
   hipStream_t tws = sd;      // tail weight gradients: side stream (same-box A/B: +0.5 % over the main stream)
   const bool fused_tail = p->use_fused_tail_bwd && s == 4 && dt != M2T_F32;
   const bool stream_x23 = p->stream_tail_x23();
@@ -843,7 +864,7 @@ extern "C" int m2t_backward(m2t_plan* p, const float* params, const float* x, fl
                        p->B, p->Hsp, p->Wsp, p->Hs, p->Ws, p->l1_R, p->l1_sc, p->l1_sc, st));
   fork();
   hipEvent_t im2col_done = nullptr;           // head_cols is produced on the side stream; the head weight gradient may run on the main one
-  if (!skip) { CK(launch_head_im2col(dt, x, WSP("head_cols"), B, p->H0, p->W0, H, W, sd)); im2col_done = side_marker(); }
+  if (!skip_head) { CK(launch_head_im2col(dt, x, WSP("head_cols"), B, p->H0, p->W0, H, W, sd)); im2col_done = side_marker(); }
   if (stream_x23) {
     // x2 / x3: the whole tail backward in one row-streaming launch (k_tail_bwd_stream.hip): g(body output) straight into gT
     const int N0 = 64 * r0 * r0;
@@ -854,9 +875,11 @@ extern "C" int m2t_backward(m2t_plan* p, const float* params, const float* x, fl
     { M2TProfScope ps(M2T_PROF_FINAL_DGRAD, st);
       CK(launch_tail_bwd_stream(gpre, params + p->poff.at(wl), WSP("X" + std::to_string(p->nb)), nullptr, packed_ptr(p, workspace, "t0T"),
                                 params + p->poff.at("tail.0.bias"), WSP("gT"), swf, sw0, sb0, &ns, B, H, W, r0, 1, st)); }
+    if (!skip) {
     defer(swf, p->poff.at(wl), ns, 32 * 64, 3, 0, 0, 0);
     defer(sw0, p->poff.at("tail.0.weight"), ns, (long long)N0 * 64, 2, 64, r0 * r0, 64);
     defer(sb0, p->poff.at("tail.0.bias"), ns, N0, 2, 64, r0 * r0, 1);
+    }
   } else if (fused_tail) {
     // one pass over the high-resolution tensors (k_tail_bwd.hip): tail conv dgrad + wgrad, GELU', tail.3 dgrad + wgrad
     const bool sbwd = p->use_stream_tail_bwd && p->use_fused_tail_fwd;      // (the streaming form always recomputes)
@@ -875,9 +898,11 @@ extern "C" int m2t_backward(m2t_plan* p, const float* params, const float* x, fl
                                sb3, &ns, B, p->Hsp, p->Wsp, st, l1_in_tail ? (const float*)WSP("srpre") : nullptr, p->l1_hr,
                                (float*)WSP("loss_part"), p->Hs, p->Ws, p->l1_R, p->l1_sc, p->use_tail_bwd32 ? 32 : 16)); }
     if (l1_in_tail) CK(launch_loss_finish((const float*)WSP("loss_part"), ns, p->l1_sc, p->l1_loss_out, st));
+    if (!skip) {
     defer(swf, p->poff.at(wl), ns, 32 * 64, 3, 0, 0, 0);
     defer(sw3, p->poff.at("tail.3.weight"), ns, 256 * 64, 2, 64, 4, 64);
     defer(sb3, p->poff.at("tail.3.bias"), ns, 256, 2, 64, 4, 1);
+    }
   } else {
   if (!skip) {
     ARENA(slabs, (size_t)1024 * 32 * 64);
@@ -922,7 +947,7 @@ extern "C" int m2t_backward(m2t_plan* p, const float* params, const float* x, fl
     m2t_gemm_args ga{};
     ga.A = WSP("g_t1pre"); ga.W = packed_ptr(p, workspace, "t0T"); ga.Y = WSP("gT"); ga.ldy = M2T_LD_P64;
     ga.M = BP; ga.N = 64; ga.K = N0; ga.H = H; ga.Wd = W; ga.r = r0; ga.C = 64;
-    { M2TProfScope ps(M2T_PROF_TAIL_GEMM, st); CK(launch_gemm_nt(dt, M2T_A_UNSHUF, M2T_E_PLAIN, ga, st)); }
+    if (chain_body) { M2TProfScope ps(M2T_PROF_TAIL_GEMM, st); CK(launch_gemm_nt(dt, M2T_A_UNSHUF, M2T_E_PLAIN, ga, st)); }
   }
   if (fused_tail || stream_x23) fork();     // the reduction (side stream) follows the main-stream producer
   CK(flush());
@@ -951,9 +976,10 @@ extern "C" int m2t_backward(m2t_plan* p, const float* params, const float* x, fl
   // buffers, so the lag is harmless.
   const bool gated = p->gate_branch >= 0 && sd != st;
   const int gate = p->gate_branch;          // branch index after whose attention launch the block's side work is released
-  for (int b = p->nb - 1; b >= 0; --b) {
+  for (int b = p->nb - 1; b >= lowest; --b) {
     const std::string k = "b" + std::to_string(b) + ".";
     const std::string pre = "body." + std::to_string(b) + ".";
+    const bool skip = p->debug_skip_side || !need[1 + b];     // (this block's parameter-gradient work)
     void* X = WSP("X" + std::to_string(b));
     float* mean = (float*)WSP(k + "mean");
     float* rstd = (float*)WSP(k + "rstd");
@@ -1124,14 +1150,16 @@ extern "C" int m2t_backward(m2t_plan* p, const float* params, const float* x, fl
                                        //  last data-gradient kernel is short -- the main stream idles until it is done)
   }
   // head: g(res) = g(X0) from the chain + g(Y) from `res + x`: added inside block 0's InstanceNorm backward (it wrote gxc)
-  if (p->nb == 0) CK(launch_add(dt, gy, WSP("gT"), WSP("gxc"), BP * 64, st));
+  if (p->nb == 0 && chain_body) CK(launch_add(dt, gy, WSP("gT"), WSP("gxc"), BP * 64, st));
+  // the input gradient: the head conv's adjoint over gxc = g(res), which nothing writes after this point
+  if (gx_out) CK(launch_head_conv_dgrad(dt, WSP("gxc"), params + p->poff.at("head.weight"), gx_out, B, p->H0, p->W0, H, W, st));
   // The end of the step is a serial chain: head weight gradient -> its reduction -> (the caller's) Adam.  In steady state it runs on the
   // MAIN stream behind the last data-gradient kernel: handing it to the side stream and back cost two cross-stream waits and a
   // queue position behind the last block pair's reduction (96 us between the last backward kernel and Adam, measured).
-  const bool tail_on_main = p->red_uploaded && sd != st;
+  const bool tail_on_main = full && p->red_uploaded && sd != st;
   hipStream_t hs = tail_on_main ? st : sd;
   if (!tail_on_main) fork();
-  if (!skip) {
+  if (!skip_head) {
     // head conv: im2col'd input (made at the start of this backward, off the critical path) x output gradient
     const int nsl = wgrad_slab_count(BP, 64, 32);
     ARENA(slabs, (size_t)nsl * 64 * 32);
@@ -1143,6 +1171,36 @@ extern "C" int m2t_backward(m2t_plan* p, const float* params, const float* x, fl
     CK(launch_wgrad_tn(dt, wa, &ns, hs));
     defer(slabs, p->poff.at("head.weight"), ns, 64 * 32, 5, 32, 27, 0);
     defer(colp, p->poff.at("head.bias"), ns, 64, 0, 0, 0, 0);
+  }
+  if (!full) {
+    // a partial pass: everything deferred is reduced here, through this mask's own table (uploaded once per mask and plan option set,
+    // never the plan's published table, which stays the all-stages one); then every bucket event is recorded, so that
+    // m2t_stream_wait_bucket after such a pass waits for the whole pass
+    if (overflow) return m2t_set_error(M2T_ERR_STATE, "m2t_backward_ex: slab arena too small");
+    if (descs.size() > 512) return m2t_set_error(M2T_ERR_STATE, "m2t_backward_ex: too many deferred reductions");
+    if (!descs.empty()) {
+      m2t_plan::MaskTable& mt = p->mask_tables[need];
+      if (!mt.uploaded) {
+        if (cap_status != hipStreamCaptureStatusNone)
+          return m2t_set_error(M2T_ERR_STATE, "m2t_backward_ex: the first pass of a stage mask cannot be captured (it uploads the mask's table)");
+        if (!mt.dev) {
+          hipError_t e = hipMalloc(&mt.dev, 512 * sizeof(m2t_red_desc));
+          if (e != hipSuccess) { mt.dev = nullptr; return m2t_set_hip_error(e, __FILE__, __LINE__); }
+        }
+        mt.descs = descs;
+        hipError_t e = hipMemcpyAsync(mt.dev, mt.descs.data(), descs.size() * sizeof(m2t_red_desc), hipMemcpyHostToDevice, sd);
+        if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
+        mt.uploaded = true;
+      } else if (mt.descs.size() != descs.size()) {
+        return m2t_set_error(M2T_ERR_STATE, "m2t_backward_ex: reduction table changed between steps");
+      }
+      CK(launch_multi_reduce(arena, grads, (const m2t_red_desc*)mt.dev, (int)descs.size(), sd));
+    }
+    for (auto e : p->bucket_events) (void)hipEventRecord(e, sd);
+    main_wait(side_marker());
+    p->have_seed = false;
+    p->l1_deferred = false;
+    return 0;
   }
   const bool first_backward = !p->red_uploaded;
   if (!p->red_uploaded) {
@@ -1175,6 +1233,27 @@ extern "C" int m2t_backward(m2t_plan* p, const float* params, const float* x, fl
   return 0;
 }
 
+extern "C" int m2t_backward(m2t_plan* p, const float* params, const float* x, float* grads, void* workspace,
+                            void* stream) {
+  if (!p || !params || !x || !grads || !workspace) return m2t_set_error(M2T_ERR_ARG, "m2t_backward: null argument");
+  if (!p->have_acts || !p->have_seed)
+    return m2t_set_error(M2T_ERR_STATE, "m2t_backward: needs m2t_forward and a seed (m2t_l1_loss / m2t_set_output_grad)");
+  return backward_impl(p, params, x, grads, nullptr, nullptr, workspace, stream);
+}
+
+extern "C" int m2t_backward_ex(m2t_plan* p, const float* params, const float* x, float* grads, float* gx,
+                               const unsigned char* need_stage, void* workspace, void* stream) {
+  if (!p || !params || !workspace) return m2t_set_error(M2T_ERR_ARG, "m2t_backward_ex: null argument");
+  bool any = false;
+  for (int i = 0; i < p->nb + 2; ++i) any = any || !need_stage || need_stage[i];
+  if (!any && !gx) return m2t_set_error(M2T_ERR_ARG, "m2t_backward_ex: nothing requested (no stage flag set and gx == NULL)");
+  if (any && !grads) return m2t_set_error(M2T_ERR_ARG, "m2t_backward_ex: a stage flag is set but grads is NULL");
+  if ((!need_stage || need_stage[0]) && !x) return m2t_set_error(M2T_ERR_ARG, "m2t_backward_ex: the head's gradient needs x");
+  if (!p->have_acts || !p->have_seed)
+    return m2t_set_error(M2T_ERR_STATE, "m2t_backward_ex: needs m2t_forward and a seed (m2t_l1_loss / m2t_set_output_grad)");
+  return backward_impl(p, params, x, grads, gx, need_stage, workspace, stream);
+}
+
 extern "C" int m2t_stream_wait_bucket(m2t_plan* p, int bucket, void* stream) {
   if (!p || bucket < 0 || (size_t)bucket >= p->buckets.size()) return m2t_set_error(M2T_ERR_ARG, "m2t_stream_wait_bucket: bad bucket");
   if (p->bucket_events.size() != p->buckets.size()) return m2t_set_error(M2T_ERR_STATE, "m2t_stream_wait_bucket: call m2t_backward first");
@@ -1186,6 +1265,7 @@ extern "C" int m2t_stream_wait_bucket(m2t_plan* p, int bucket, void* stream) {
 extern "C" int m2t_set_option(m2t_plan* p, const char* key, long long value) {
   if (!p || !key) return m2t_set_error(M2T_ERR_ARG, "m2t_set_option: null");
   p->red_uploaded = false;     // the deferred-reduction table depends on the schedule: rebuild it on the next backward
+  for (auto& kv : p->mask_tables) kv.second.uploaded = false;
   const std::string k(key);
   if (k == "side_stream") { p->use_side = (value != 0); return 0; }
   if (k == "fork_on_kernel") { p->fork_on_kernel = value != 0; return 0; }

@@ -143,6 +143,8 @@ int wgrad_slab_count(long long M, int N, int K);   // upper bound of the slabs l
 int launch_head_conv_fwd(int dt, const float* x, const float* w, const float* b, void* out, int B, int H0, int W0,
                          int H, int W, hipStream_t st);
 int launch_head_im2col(int dt, const float* x, void* cols, int B, int H0, int W0, int H, int W, hipStream_t st);   // cols [B*H*W][32] (T)
+// d x of the head conv (through both reflect pads): g P64 (T) [4][B*H*W][16] -> gx fp32 NCHW [B][3][H0][W0]; deterministic gather
+int launch_head_conv_dgrad(int dt, const void* g, const float* w, float* gx, int B, int H0, int W0, int H, int W, hipStream_t st);
 // 64->64 3x3, zero padding.  wp: packed [9][64 out][64 in] (T). y = conv(x) + bias + res1 + res2 (each optional)
 int launch_conv3x3_c64(int dt, const void* x, const void* wp, const float* bias, const void* res1, const void* res2,
                        void* y, int B, int H, int W, hipStream_t st,
