@@ -58,7 +58,10 @@ long long m2t_plan_query(const m2t_plan* p, const char* key);
  * every pair is A/B-tested in tests/test_gpu_model.py.  Defaults in brackets; m2t_plan_query("opt:<key>") reads the value in
  * force (gate_branch / wgrad_big_tiles are reported + 1000).  Variants that were measured and lost live under scratch/ with
  * their numbers in profiles/README.md, not behind options.
- *   "side_stream"       [1] parameter-gradient kernels of m2t_backward on a plan-owned second stream
+ *   "side_stream"       [1] parameter-gradient kernels of m2t_backward on a plan-owned second stream; 0 enqueues the same kernels with
+ *                           the same arguments in the same order on the caller's stream, so both settings give BIT-IDENTICAL losses,
+ *                           gradients and input gradients at every step (no kernel of the step uses atomics): enforced by
+ *                           tests/test_gpu_schedule.py, where any difference is a missing stream dependency
  *   "gate_branch"       [-1] -1: a branch's side work is released right behind its attention launch; 0..3: a block's side work waits for the
  *                           attention launch of that branch (2 = behind the two LDS-filling C = 256 launches; the default of rounds 1-2,
  *                           when the main chain still waited for the side stream once per branch)
@@ -129,7 +132,14 @@ int m2t_set_option(m2t_plan* p, const char* key, long long value);
  * is final, so an all-reduce of that range can run under the rest of the backward pass.  After an m2t_backward_ex pass with
  * some stage flag clear, every bucket event marks the end of that whole pass. */
 int m2t_stream_wait_bucket(m2t_plan* p, int bucket, void* stream);
-/* one-time initialisation of the workspace (uploads the weight-packing table). */
+/* Initialisation of the workspace (uploads the weight-packing tables, clears the zero page); synchronises `stream`.
+ * Four workspace regions PERSIST across steps and must not be overwritten by the caller: "zero_page" (zeros), "pack_descs" and
+ * "pack_blocks" (the weight-packing tables), all three written here, and "red_descs" (the table of the deferred gradient
+ * reductions), written by the first all-stages m2t_backward after this call.  Every other region is scratch WITHIN one step: each
+ * m2t_forward / m2t_backward writes whatever it reads before it reads it, so the contents left by an earlier step (or by the
+ * allocator) never reach a result -- tests/test_gpu_schedule.py fills them with NaN between steps.
+ * Calling this again on a live plan is legal (with the same or another buffer, once the plan's earlier work on `stream` is
+ * enqueued): it returns the plan to "no activations, no seed", and the next all-stages backward publishes "red_descs" again. */
 int m2t_plan_init_workspace(m2t_plan* p, void* workspace, void* stream);
 
 /* ---- model ----------------------------------------------------------------------------- */

@@ -512,6 +512,10 @@ extern "C" int m2t_plan_init_workspace(m2t_plan* p, void* workspace, void* strea
   e = hipStreamSynchronize((hipStream_t)stream);   // the host table may be freed/moved afterwards
   if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
   p->have_acts = p->have_seed = false;
+  p->l1_deferred = false;
+  // red_descs lives in the workspace: a workspace that was just (re)initialised -- possibly another buffer, possibly overwritten --
+  // does not hold the published table, so the next all-stages backward publishes it again (the first_backward schedule)
+  p->red_uploaded = false;
   return 0;
 }
 

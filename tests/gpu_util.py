@@ -57,6 +57,86 @@ BR_C = (16, 64, 256, 256)
 BR_L = (0, 1, 2, 2)
 
 
+# ------------------------------------------------------------------ schedule / stale-read gates (tests/test_gpu_schedule.py)
+def set_options(model, x, **opts):
+    """m2t_set_option on the plan of x's shape (created if need be); returns the plan."""
+    from m2trans_amd import _lib
+    plan = model._plan_for(x)
+    for k, v in opts.items():
+        _lib.check(_lib.load().m2t_set_option(plan.handle, k.encode(), int(v)), "m2t_set_option " + k)
+    return plan
+
+
+def differing_tensors(model, a: torch.Tensor, b: torch.Tensor):
+    """Names of the parameter tensors in whose range two flat buffers (gradients, parameters, Adam moments) differ."""
+    return [n for n, (o, k) in model.param_offsets().items() if not torch.equal(a[o:o + k], b[o:o + k])]
+
+
+def assert_flat_equal(model, a: torch.Tensor, b: torch.Tensor, what: str):
+    """torch.equal on two flat buffers; the failure names the differing parameter tensors (they place a missing stream edge:
+    a stage's weight gradients are produced by that stage's side-stream launches)."""
+    if not torch.equal(a, b):
+        bad = differing_tensors(model, a, b)
+        raise AssertionError(f"{what}: differ in {bad[:8]} ({len(bad)} of {len(model.param_offsets())} tensors)")
+
+
+# workspace regions that carry indices or descriptors, or that must hold zeros: never poisoned by name.  pack_descs, pack_blocks and
+# zero_page are (re)written by m2t_plan_init_workspace, red_descs by the first backward pass after it (include/m2t.h)
+WS_PERSISTENT = ("zero_page", "pack_descs", "pack_blocks", "red_descs")
+
+
+def ws_float_regions(plan):
+    """[(name, byte offset, bytes)] of every floating-point region of the plan's workspace, by the names m2t_plan_create registers.
+    Fails if these regions and WS_PERSISTENT together do not tile workspace_bytes exactly (up to the 256-byte alignment of each
+    region): a region added to the library later cannot silently escape the poison of the history-independence tests."""
+    nb, s = plan.n_blocks, plan.scale
+    from m2trans_amd import _lib
+    T, F = (4 if plan.dtype == _lib.F32 else 2), 4      # element size of a region: the plan's compute type, or always fp32
+    names = [("packed", T)] + [(f"X{b}", T) for b in range(nb + 1)]
+    for b in range(nb):
+        names += [(f"b{b}.mean", F), (f"b{b}.rstd", F), (f"b{b}.xc", T)]
+        for i in range(1, 5):
+            names += [(f"b{b}.d{i}", T), (f"b{b}.qkv{i}", T)]
+    names += [("xin", T), ("a", T), ("norm_part", F), ("norm_s", F), ("vring", T), ("norm_part0", F), ("t1act", T), ("t1der", T)]
+    if s == 4:
+        names += [("t2act", T), ("t2der", T)]
+    names += [("srpre", F), ("loss_part", F), ("gpre", F)]
+    if s == 4:
+        names += [("g_t2pre", T)]
+    names += [("g_t1pre", T)] + [(n, T) for n in ("gT", "gA", "gB", "gxc", "gn", "ga", "gd", "gd2", "gdwin2", "gdwin", "head_cols")]
+    for i in range(4):
+        for sfx in ("", "b"):
+            names += [(f"gqkv{i}{sfx}", T), (f"win{i}{sfx}", T), (f"relw{i}{sfx}", F)]
+    names += [("rel_part", F), ("arena", F), ("col_part", F)]
+    regions = [(n, plan.query("ws:" + n), plan.query("wsn:" + n) * e) for n, e in names]
+    every = regions + [(n, plan.query("ws:" + n), plan.query("wsn:" + n)) for n in WS_PERSISTENT]      # (byte-sized regions)
+    end = 0
+    for n, off, nbytes in sorted(every, key=lambda r: (r[1], r[2])):
+        if off != (end + 255) // 256 * 256:
+            raise AssertionError(f"workspace region list out of date: {n} starts at byte {off}, the listed regions before it end at {end}")
+        end = off + nbytes
+    total = plan.query("workspace_bytes")
+    if (end + 255) // 256 * 256 != total:
+        raise AssertionError(f"workspace region list out of date: the listed regions end at byte {end} of {total}")
+    return regions
+
+
+def poison_float_regions(plan):
+    """0xFF (NaN as bf16 and as fp32) into every floating-point workspace region, by name."""
+    for _, off, nbytes in ws_float_regions(plan):
+        plan.workspace[off:off + nbytes].fill_(0xFF)
+
+
+def poison_whole_workspace(plan):
+    """0xFF into the WHOLE workspace, then m2t_plan_init_workspace again: legal on a live plan, which is then back to
+    'no activations, no seed, reduction table not published' (include/m2t.h)."""
+    from m2trans_amd import _lib
+    ws_float_regions(plan)                      # (the inventory check: no unknown index-carrying region is about to be poisoned)
+    plan.workspace.fill_(0xFF)
+    _lib.check(_lib.load().m2t_plan_init_workspace(plan.handle, _lib.ptr(plan.workspace), _lib.stream_ptr()),
+               "m2t_plan_init_workspace")
+
+
 def hip_forward_trace(plan, scale, n_blocks, B, H, W):
     """Every stored activation of the last m2t_forward, read back from the workspace as float32 NCHW on the CPU, under the
     names the oracle's ``force`` / ``cap`` dicts use (H, W = padded LR size)."""
