@@ -189,6 +189,13 @@ int m2t_backward_ex(m2t_plan* p, const float* params, const float* x, float* gra
  * buffers; step = 1-based count; grad_scale multiplies g first (1/world_size after a SUM all-reduce). */
 int m2t_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n,
                   float lr, float beta1, float beta2, float eps, int step, float grad_scale, void* stream);
+/* Gradient accumulation over micro-batches (torch's AccumulateGrad under loss.backward() called several times before
+ * optimizer.step(), train.py:209-210): acc[i] = acc[i] + g[i] for i in [0, n) -- ONE IEEE fp32 addition per element, no
+ * scaling, no other arithmetic, so the result is the same bits as torch's acc += g.  acc and g: device pointers, 4-byte
+ * aligned, not overlapping (any n >= 0; 16-byte loads and stores when both are misaligned to 16 bytes by the same amount, a
+ * scalar loop otherwise).  loss_acc / loss_part: both NULL, or device float[1] each: loss_acc[0] = loss_acc[0] + loss_part[0]
+ * in the same launch.  M2T_ERR_ARG: null acc / g with n > 0, n < 0, exactly one of the two loss pointers set. */
+int m2t_grad_accumulate(float* acc, const float* g, long long n, float* loss_acc, const float* loss_part, void* stream);
 
 /* ---- measurement: per-kernel-category timing with HIP events recorded on the launch stream.
  * category ids are listed in m2trans_amd/profile.py; mask bit i enables category i; 0 = off. */

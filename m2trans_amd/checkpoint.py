@@ -32,7 +32,13 @@ def _param_index(model) -> Dict[str, int]:
 def export_checkpoint(model, train_step=None, epoch: int = 1, stat_dict: Optional[dict] = None,
                       lr0: float = 1e-4, eta_min: float = 1e-6, t_max: float = 200.0) -> dict:
     """The dict train.py:341-349 saves at the end of (1-based) epoch `epoch`."""
-    sd = {"module." + k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+    if train_step is not None and getattr(train_step, "micro_count", 0) != 0:
+        # TrainStep(accum_steps=k): the moments are one optimizer step behind gradients that are half summed and that no
+        # checkpoint format carries
+        from ._lib import M2TError
+        raise M2TError(f"export_checkpoint in the middle of an accumulation cycle ({train_step.micro_count} of "
+                       f"{getattr(train_step, 'accum_steps', '?')} micro-batches since the last optimizer step)")
+    sd ={"module." + k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
     out = {"epoch": int(epoch), "model_state_dict": sd}
     if train_step is not None:
         params = [p for _, p in model.named_parameters()]                 # ALL parameters, like train.py:81

@@ -1232,6 +1232,50 @@ int launch_adam(float* p, const float* g, float* m, float* v, long long n, float
 }
 
 // =======================================================================================
+// gradient accumulation over micro-batches   (torch's AccumulateGrad under loss.backward() called
+// several times before optimizer.step(), train.py:209-210)
+//   acc[i] = acc[i] + g[i]: ONE fp32 addition per element, the bits of torch's acc += g; the loss slot likewise.
+// vec: acc + head and g + head are both 16-byte aligned -> 16-byte loads / stores for the body, block 0 takes the
+// (at most 3 + 3) head and tail elements; pointers misaligned by DIFFERENT amounts take the scalar loop.
+// =======================================================================================
+__global__ void __launch_bounds__(256) grad_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, long long n,
+                                                              int head, int vec, float* loss_acc, const float* loss_part) {
+  const long long tid = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  if (vec) {
+    const long long n4 = (n - head) / 4;
+    f32x4* a4 = reinterpret_cast<f32x4*>(acc + head);
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(g + head);
+    for (long long t = tid; t < n4; t += stride) {
+      f32x4 aa = a4[t];
+      const f32x4 gg = g4[t];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) aa[i] = aa[i] + gg[i];
+      a4[t] = aa;
+    }
+    if (blockIdx.x == 0) {
+      if ((int)threadIdx.x < head) acc[threadIdx.x] = acc[threadIdx.x] + g[threadIdx.x];
+      const long long t0 = head + n4 * 4;          // tail: n - t0 in 0..3
+      if ((long long)threadIdx.x < n - t0) acc[t0 + threadIdx.x] = acc[t0 + threadIdx.x] + g[t0 + threadIdx.x];
+    }
+  } else {
+    for (long long i = tid; i < n; i += stride) acc[i] = acc[i] + g[i];
+  }
+  if (loss_acc && tid == 0) loss_acc[0] = loss_acc[0] + loss_part[0];
+}
+int launch_grad_accumulate(float* acc, const float* g, long long n, float* loss_acc, const float* loss_part, hipStream_t st) {
+  if (n == 0 && !loss_acc) return 0;
+  // elements up to acc's next 16-byte boundary (pointers are 4-byte aligned), never more than n
+  int head = (int)(((16 - ((uintptr_t)acc & 15)) & 15) / 4);
+  if (head > n) head = (int)n;
+  const int vec = (((uintptr_t)(acc + head) | (uintptr_t)(g + head)) & 15) == 0;
+  hipLaunchKernelGGL(grad_accumulate_kernel, dim3(grid_for(vec ? n / 4 + 1 : n)), dim3(256), 0, st, acc, g, n, head, vec,
+                     loss_acc, loss_part);
+  M2T_LAUNCH_CHECK();
+  return 0;
+}
+
+// =======================================================================================
 // weight packer: ONE launch converts every fp32 master tensor into the element type and
 // layouts the kernels want, driven by a descriptor table built at plan creation.
 // =======================================================================================

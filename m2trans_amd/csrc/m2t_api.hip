@@ -1307,6 +1307,12 @@ extern "C" int m2t_adam_step(float* params, const float* grads, float* exp_avg, 
   return launch_adam(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, grad_scale, (hipStream_t)stream);
 }
 
+extern "C" int m2t_grad_accumulate(float* acc, const float* g, long long n, float* loss_acc, const float* loss_part, void* stream) {
+  if (n < 0 || (n > 0 && (!acc || !g)) || ((loss_acc == nullptr) != (loss_part == nullptr)))
+    return m2t_set_error(M2T_ERR_ARG, "m2t_grad_accumulate: bad argument");
+  return launch_grad_accumulate(acc, g, n, loss_acc, loss_part, (hipStream_t)stream);
+}
+
 // ---- stand-alone operators ---------------------------------------------------------------
 extern "C" int m2t_dwt(int dtype, int levels, const void* src, void* dst, int B, int H, int W, int C, void* stream) {
   return launch_dwt(dtype, levels, src, C, 0, dst, C << (2 * levels), 0, B, H, W, C, false, (hipStream_t)stream);

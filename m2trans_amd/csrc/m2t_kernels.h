@@ -94,6 +94,8 @@ int launch_clamp_l1(const float* pre, const float* hr, float* sr, float* gpre, f
 int launch_loss_finish(const float* part, int n, float loss_scale, float* loss, hipStream_t st);
 int launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps,
                 int step, float gscale, hipStream_t st);
+// acc[0 .. n) += g (one fp32 addition per element); loss_acc[0] += loss_part[0] when both are given (same launch)
+int launch_grad_accumulate(float* acc, const float* g, long long n, float* loss_acc, const float* loss_part, hipStream_t st);
 // blocks: device table int2[nblocks] = (descriptor index, chunk of M2T_PACK_CHUNK output elements)
 int launch_pack(int dt, const float* master, void* packed, const m2t_pack_desc* descs, const void* blocks, int nblocks, hipStream_t st);
 int launch_layout(int dt, const float* nchw, void* nhwc, float* nchw_out, int B, int C, int HW, int inverse, hipStream_t st);

@@ -44,9 +44,11 @@ def shard_size(global_batch: int, world: int) -> int:
     return global_batch // world
 
 
-def global_divisor(local_hr_numel: int, world: int) -> float:
-    """Denominator of the L1 mean over the GLOBAL batch, given this rank's (equal) shard."""
-    return float(local_hr_numel) * world
+def global_divisor(local_hr_numel: int, world: int, accum_steps: int = 1) -> float:
+    """Denominator of the L1 mean over the GLOBAL batch, given this rank's (equal) shard -- with gradient accumulation
+    (TrainStep(accum_steps=k)) one of the k equal micro-batches of that shard: the mean runs over every sample of every
+    micro-batch of every rank, and a micro-batch is a rank that runs later on the same device."""
+    return float(local_hr_numel) * world * accum_steps
 
 
 class GradBucket:

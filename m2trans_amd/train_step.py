@@ -15,6 +15,10 @@ train.py:212-214, are left to the caller's logging cadence).
 Data parallelism (replaces nn.DataParallel, train.py:73): one process per GPU, persistent
 replicas, equal shards of the global batch; each rank divides its L1 sum by the GLOBAL element
 count, so SUM-all-reduced gradients equal the full-batch gradient.
+
+Gradient accumulation (``accum_steps=k``; replaces torch's AccumulateGrad under several ``loss.backward()`` calls before one
+``optimizer.step()``): a micro-batch is a rank that runs later on the same device -- the same global divisor, the sum taken by
+one streaming HIP pass per micro-batch (m2t_grad_accumulate), one exchange and one Adam pass per k micro-batches.
 """
 from __future__ import annotations
 
@@ -52,8 +56,15 @@ class TrainStep:
     def __init__(self, model: M2Trans, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  lambda_l1: float = 1.0, process_group=None, world_size: Optional[int] = None,
                  grad_bucket_dtype: torch.dtype = torch.float32, semantic_loss=None, lambda_clip: float = 0.0,
-                 overlap_comm: bool = True, force_comm_path: bool = False, overlap_semantic: bool = True):
+                 overlap_comm: bool = True, force_comm_path: bool = False, overlap_semantic: bool = True,
+                 accum_steps: int = 1):
         self.model = model
+        # gradient accumulation: one optimizer step consumes accum_steps equal micro-batches (forward_backward calls); the
+        # gradients and the loss of calls 2..k of a cycle are added to the first call's by m2t_grad_accumulate
+        if int(accum_steps) != accum_steps or int(accum_steps) < 1:
+            raise _lib.M2TError(f"accum_steps must be an integer >= 1, got {accum_steps!r}")
+        self.accum_steps = int(accum_steps)
+        self.micro_count = 0                    # forward_backward calls since the last optimizer step (stays 0 with accum_steps = 1)
         # the SemanticLoss forward needs only sr (final after m2t_forward): it runs on its own stream under the backward pass
         self.overlap_semantic = bool(overlap_semantic)
         self.sem_stream = None
@@ -81,6 +92,9 @@ class TrainStep:
         self.exp_avg_sq = torch.zeros_like(flat)
         self.l1_loss = torch.zeros(1, dtype=torch.float32, device=flat.device)
         self.loss = self.l1_loss
+        # where micro-batches 2..k of a cycle put their gradients and their L1 loss (nothing is allocated for accum_steps = 1)
+        self.micro_grads = torch.empty_like(self.grads) if self.accum_steps > 1 else None
+        self.micro_loss = torch.zeros(1, dtype=torch.float32, device=flat.device) if self.accum_steps > 1 else None
         # force_comm_path: build the exchange machinery even for one rank (tests exercise the stream / event logic)
         self.bucket = GradBucket(self.grads, process_group, grad_bucket_dtype, force=force_comm_path,
                                  expect_world=self.world_size) if (self.world_size > 1 or force_comm_path) else None
@@ -99,7 +113,13 @@ class TrainStep:
     # -- pieces (also used by tests) -------------------------------------------------------
     def forward_backward(self, lr_img: torch.Tensor, hr_img: torch.Tensor, captions=None) -> torch.Tensor:
         """forward + L1 (+ the constant SemanticLoss term) + backward into model.flat_grads; returns the
-        device loss tensor (this rank's share of the global mean)."""
+        device loss tensor (this rank's share of the global mean).  With accum_steps = k > 1 this is ONE micro-batch: the first
+        call of a cycle fills model.flat_grads and the loss, calls 2..k add to them (in call order, fp32), and a call beyond the
+        k-th before optimizer_step() raises."""
+        first = self.micro_count == 0
+        if self.accum_steps > 1 and self.micro_count >= self.accum_steps:
+            raise _lib.M2TError(f"forward_backward: {self.micro_count} micro-batches since the last optimizer step, accum_steps is "
+                                f"{self.accum_steps}: call all_reduce_grads() / optimizer_step() first")
         m = self.model
         lib = _lib.load()
         plan = m._plan_for(lr_img)
@@ -108,10 +128,13 @@ class TrainStep:
         B = lr_img.shape[0]
         if tuple(hr_img.shape) != (B, 3, lr_img.shape[2] * m.scale, lr_img.shape[3] * m.scale):
             raise _lib.M2TError("hr shape must be [B,3,H*scale,W*scale]")
-        divisor = global_divisor(hr_img.numel(), self.world_size)      # global mean (equal shards)
+        divisor = global_divisor(hr_img.numel(), self.world_size, self.accum_steps)      # global mean (equal shards, equal micro-batches)
         use_clip = self.semantic_loss is not None and self.lambda_clip > 0 and captions is not None
+        # (micro-batches 2..k of a cycle: a second gradient buffer and a second loss slot, added to the first ones below)
+        grads = self.grads if first else self.micro_grads
+        l1_loss = self.l1_loss if first else self.micro_loss
         if use_clip and getattr(self.semantic_loss, "differentiable", False):
-            return self._forward_backward_semantic_grad(m, lib, plan, lr_img, hr_img, captions, divisor)
+            return self._forward_backward_semantic_grad(m, lib, plan, lr_img, hr_img, captions, divisor, grads, l1_loss)
         sr = torch.empty_like(hr_img) if use_clip else None
         plan.gen += 1
         plan.trained = True              # (the plan LRU of the model keeps training plans while forward-only ones remain)
@@ -124,10 +147,11 @@ class TrainStep:
             # (deferred: the loss and the backward seed are produced inside m2t_backward, which follows at once -- on the bf16 x4
             #  path by the fused tail backward itself; hr_img stays alive until then)
             _lib.check(lib.m2t_l1_loss_deferred(plan.handle, _lib.ptr(hr_img), self.lambda_l1, divisor, float(m.rgb_range),
-                                                _lib.ptr(self.l1_loss), ws, st), "m2t_l1_loss_deferred")
+                                                _lib.ptr(l1_loss), ws, st), "m2t_l1_loss_deferred")
             fwd_done = torch.cuda.current_stream(lr_img.device).record_event() if (use_clip and self.overlap_semantic) else None
-            _lib.check(lib.m2t_backward(plan.handle, _lib.ptr(m.flat_params), _lib.ptr(lr_img), _lib.ptr(self.grads),
+            _lib.check(lib.m2t_backward(plan.handle, _lib.ptr(m.flat_params), _lib.ptr(lr_img), _lib.ptr(grads),
                                         ws, st), "m2t_backward")
+            self._accumulate_micro(lib, first, st)
         if use_clip:
             # clip_loss += loss_clip(sr[i], hr[i], caption_i) * lambda_clip  (train.py:203-205); no gradient
             if self.overlap_semantic:
@@ -139,16 +163,33 @@ class TrainStep:
                     self.sem_stream = _shared_stream(lr_img.device, "semantic")
                 self.sem_stream.wait_event(fwd_done)
                 with torch.cuda.stream(self.sem_stream):
-                    self.clip_loss = self.semantic_loss.batch(sr, hr_img, captions) * self.lambda_clip
+                    self._add_clip(self.semantic_loss.batch(sr, hr_img, captions) * self.lambda_clip, first)
                 main.wait_stream(self.sem_stream)
             else:
-                self.clip_loss = self.semantic_loss.batch(sr, hr_img, captions) * self.lambda_clip
+                self._add_clip(self.semantic_loss.batch(sr, hr_img, captions) * self.lambda_clip, first)
             self.loss = self.l1_loss + self.clip_loss
         else:
             self.loss = self.l1_loss
         return self.loss
 
-    def _forward_backward_semantic_grad(self, m, lib, plan, lr_img, hr_img, captions, divisor):
+    def _accumulate_micro(self, lib, first: bool, st):
+        """Close one micro-batch: count it and, from the second one of a cycle on, grads += micro_grads, l1_loss += micro_loss."""
+        if self.accum_steps == 1:
+            return
+        self.micro_count += 1
+        if first:
+            return
+        # no event needed: m2t_backward ends with its side stream joined into the caller's stream (every gradient and the deferred
+        # loss are complete in the order of that stream), and the next micro-batch's side-stream launches are forked from this
+        # stream behind this kernel -- the ordering Adam and the next step's backward rely on today
+        _lib.check(lib.m2t_grad_accumulate(_lib.ptr(self.grads), _lib.ptr(self.micro_grads), self.grads.numel(),
+                                           _lib.ptr(self.l1_loss), _lib.ptr(self.micro_loss), st), "m2t_grad_accumulate")
+
+    def _add_clip(self, clip: torch.Tensor, first: bool):
+        """The SemanticLoss term of one micro-batch (a per-sample SUM: no divisor) into the cycle's clip_loss."""
+        self.clip_loss = clip if first else self.clip_loss + clip
+
+    def _forward_backward_semantic_grad(self, m, lib, plan, lr_img, hr_img, captions, divisor, grads, l1_loss):
         """The route of a differentiable SemanticLoss: forward -> semantic encode (the SR crops stash what the encoder's backward
         needs, the HR crops do not) -> its vector-Jacobian product -> m2t_l1_loss (a MATERIALISED seed: the fused-L1 seed of the
         default route, m2t_l1_loss_deferred, does not apply here) -> m2t_add_output_grad(lambda_clip) -> m2t_backward.  HIP kernels
@@ -166,16 +207,18 @@ class TrainStep:
                                        float(m.rgb_range), 1, ws, st), "m2t_forward")
             tot, g, origins = sl._value_and_grad(sr, hr_img, captions)
             _lib.check(lib.m2t_l1_loss(plan.handle, _lib.ptr(hr_img), self.lambda_l1, divisor, float(m.rgb_range),
-                                       _lib.ptr(self.l1_loss), ws, st), "m2t_l1_loss")
+                                       _lib.ptr(l1_loss), ws, st), "m2t_l1_loss")
             g = g.contiguous()
             arr = None
             if origins is not None:
                 arr = (C.c_int * (2 * len(origins)))(*[int(v) for o in origins for v in o])
             _lib.check(lib.m2t_add_output_grad(plan.handle, _lib.ptr(g), g.shape[2], g.shape[3], arr, self.lambda_clip,
                                                float(m.rgb_range), ws, st), "m2t_add_output_grad")
-            _lib.check(lib.m2t_backward(plan.handle, _lib.ptr(m.flat_params), _lib.ptr(lr_img), _lib.ptr(self.grads),
+            _lib.check(lib.m2t_backward(plan.handle, _lib.ptr(m.flat_params), _lib.ptr(lr_img), _lib.ptr(grads),
                                         ws, st), "m2t_backward")
-        self.clip_loss = tot * self.lambda_clip
+            first = grads is self.grads
+            self._accumulate_micro(lib, first, st)
+        self._add_clip(tot * self.lambda_clip, first)
         self.loss = self.l1_loss + self.clip_loss
         return self.loss
 
@@ -183,7 +226,9 @@ class TrainStep:
         """SUM the gradients over the ranks.  Overlapped mode: m2t_backward (already enqueued) completes the flat
         buffer in contiguous buckets (tail, block pairs from last to first, head); each bucket's all-reduce is
         enqueued on the communication stream behind that bucket's event, so it runs under the remaining backward
-        kernels; the compute stream then waits for the communication stream (before Adam)."""
+        kernels; the compute stream then waits for the communication stream (before Adam).  With accum_steps = k > 1 the
+        exchange runs once per optimizer step, on the accumulated buffer, behind the last accumulate."""
+        self._check_cycle_complete("all_reduce_grads")
         if self.bucket is None:
             return
         ev0 = None
@@ -210,13 +255,26 @@ class TrainStep:
         cut = max(0, len(buckets) - 3)
         groups = [(cut, buckets[cut][0], buckets[0][1]), (len(buckets) - 1, 0, buckets[cut][0])] if cut > 0 else \
                  [(len(buckets) - 1, 0, buckets[0][1])]
+        if self.accum_steps > 1:
+            # the bucket events of the last micro-batch's backward describe the micro buffer, not the sum: the same two ranges,
+            # behind the last m2t_grad_accumulate
+            self.comm_stream.wait_stream(main)
         with torch.cuda.device(self.grads.device), torch.cuda.stream(self.comm_stream):
             for last, lo, hi in groups:
-                _lib.check(lib.m2t_stream_wait_bucket(plan.handle, last, self.comm_stream.cuda_stream), "m2t_stream_wait_bucket")
+                if self.accum_steps == 1:
+                    _lib.check(lib.m2t_stream_wait_bucket(plan.handle, last, self.comm_stream.cuda_stream), "m2t_stream_wait_bucket")
                 self.bucket.all_reduce_range(lo, hi)
         main.wait_stream(self.comm_stream)
 
+    def _check_cycle_complete(self, what: str):
+        """accum_steps = k > 1: a partial sum scaled by the full divisor would train silently on a wrong gradient."""
+        if self.accum_steps > 1 and self.micro_count != self.accum_steps:
+            raise _lib.M2TError(f"{what}: {self.micro_count} of {self.accum_steps} micro-batches since the last optimizer step "
+                                "(accum_steps): the gradient buffer does not hold the whole cycle")
+
     def optimizer_step(self):
+        self._check_cycle_complete("optimizer_step")
+        self.micro_count = 0                    # closes the cycle; step_count counts optimizer steps, never micro-batches
         self.step_count += 1
         lib = _lib.load()
         with torch.cuda.device(self.grads.device):
@@ -227,7 +285,31 @@ class TrainStep:
 
     # -- the step ----------------------------------------------------------------------------
     def step(self, lr_img: torch.Tensor, hr_img: torch.Tensor, captions=None) -> torch.Tensor:
+        """One optimizer step on one batch.  With accum_steps = k > 1 the batch holds k * b samples and is cut, in sample
+        order, into k micro-batches of b (views of the batch), each run through the plan of the micro-batch shape."""
+        if self.accum_steps > 1:
+            return self._step_accumulated(lr_img, hr_img, captions)
         loss = self.forward_backward(lr_img, hr_img, captions)
+        self.all_reduce_grads()
+        self.optimizer_step()
+        return loss
+
+    def _step_accumulated(self, lr_img, hr_img, captions):
+        k, B = self.accum_steps, int(lr_img.shape[0])
+        if B == 0 or B % k:
+            raise _lib.M2TError(f"step: a batch of {B} samples cannot be cut into accum_steps = {k} equal micro-batches")
+        if int(hr_img.shape[0]) != B:
+            raise _lib.M2TError(f"step: {B} LR samples but {int(hr_img.shape[0])} HR samples")
+        if self.micro_count != 0:
+            raise _lib.M2TError(f"step: {self.micro_count} of {k} micro-batches of a cycle are already in the gradient buffer")
+        if captions is not None:
+            captions = list(captions)
+            if len(captions) != B:
+                raise _lib.M2TError(f"step: {B} samples but {len(captions)} captions")
+        b = B // k
+        for i in range(k):
+            loss = self.forward_backward(lr_img[i * b:(i + 1) * b], hr_img[i * b:(i + 1) * b],
+                                         captions[i * b:(i + 1) * b] if captions is not None else None)
         self.all_reduce_grads()
         self.optimizer_step()
         return loss
