@@ -196,6 +196,37 @@ int m2t_adam_step(float* params, const float* grads, float* exp_avg, float* exp_
  * scalar loop otherwise).  loss_acc / loss_part: both NULL, or device float[1] each: loss_acc[0] = loss_acc[0] + loss_part[0]
  * in the same launch.  M2T_ERR_ARG: null acc / g with n > 0, n < 0, exactly one of the two loss pointers set. */
 int m2t_grad_accumulate(float* acc, const float* g, long long n, float* loss_acc, const float* loss_part, void* stream);
+/* The global gradient norm of the flat buffer and the decisions that hang on it (train.py:81,210 is the optimizer this feeds;
+ * restates total = torch.nn.utils.clip_grad_norm_(params, max_norm), the torch.isfinite(total) test of a skipping loop, and
+ * Adam's bias_correction1/2 for the step it will really take).  Two launches, no atomics: a fixed grid of fp64 partial sums of
+ * (grad_scale * g)^2 into `workspace` (m2t_grad_norm_workspace_bytes() bytes, device, 8-byte aligned), then one workgroup that
+ * adds them in index order and writes `record`: 8 doubles on the device, which the caller ZEROES once and then leaves alone --
+ *   [0] norm = sqrt(sum)                      [1] finite = isfinite(norm)
+ *   [2] clip_coef = min(1, max_norm / (float(norm) + 1e-6)) in fp32 as torch does; 1 when max_norm <= 0
+ *   [3] applied = 0 when skip_nonfinite and the norm is not finite, else 1
+ *   [4] skipped: running count of calls with applied == 0
+ *   [5] 1 - beta1^t   [6] sqrt(1 - beta2^t)   [7] t = step - skipped: the bias correction of the EFFECTIVE step number
+ * The summation tree depends on n (and the 16-byte phase of grads) alone: the same bits on every run and every device.
+ * grads: device, 4-byte aligned, read only (any n >= 0).  The library allocates nothing and synchronises nothing.
+ * M2T_ERR_ARG (decided on the host): n < 0, null grads with n > 0, null record or workspace, step < 1, NaN max_norm. */
+int m2t_grad_norm(const float* grads, long long n, float grad_scale, float max_norm, int skip_nonfinite, int step,
+                  float beta1, float beta2, double* record, void* workspace, void* stream);
+long long m2t_grad_norm_workspace_bytes(void);
+/* torch.optim.Adam(lr, betas, eps, weight_decay, decoupled_weight_decay).step() (train.py:81,210; the reference passes
+ * weight_decay there) behind torch.nn.utils.clip_grad_norm_, with ema.mul_(d).add_(p, alpha=1 - d) in the same pass.  Arguments
+ * up to grad_scale as m2t_adam_step.  Per element, fp32, in this order:
+ *   g' = g * grad_scale * clip_coef;  coupled (decoupled == 0, weight_decay > 0): g' = g' + weight_decay * p;
+ *   decoupled (AdamW): p = p * float32(1 - lr * weight_decay);  m, v, p as m2t_adam_step with g';
+ *   ema != NULL: ema = ema_decay * ema + (1 - ema_decay) * p_new.
+ * record: NULL, or the record m2t_grad_norm wrote on the same stream: clip_coef and the bias correction are read from it, and
+ * with applied == 0 NOTHING is written (params, moments and ema keep every bit).  NULL: no clip, no skip, bias correction
+ * from `step` on the host -- weight decay or EMA alone pay for no norm pass.  grads is never written: after the step it
+ * still holds the raw gradient and the record holds the coefficient.  Buffers: device, 16-byte aligned.
+ * M2T_ERR_ARG (decided on the host): n < 0, a null params / grads / moment buffer with n > 0, step < 1, weight_decay < 0,
+ * ema_decay outside [0, 1). */
+int m2t_adam_step_ex(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, float lr,
+                     float beta1, float beta2, float eps, int step, float grad_scale, float* ema, float weight_decay,
+                     int decoupled, float ema_decay, const double* record, void* stream);
 
 /* ---- measurement: per-kernel-category timing with HIP events recorded on the launch stream.
  * category ids are listed in m2trans_amd/profile.py; mask bit i enables category i; 0 = off. */

@@ -34,7 +34,10 @@ SIGNATURES = {
     "m2t_backward_ex": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_ubyte), _vp, _vp]),
     "m2t_adam_step": (_i, [_vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _i, _f, _vp]),
     "m2t_grad_accumulate": (_i, [_vp, _vp, _ll, _vp, _vp, _vp]),
-    "m2t_profile_enable": (_i, [C.c_ulonglong]),
+    "m2t_grad_norm": (_i, [_vp, _ll, _f, _f, _i, _i, _f, _f, _vp, _vp, _vp]),
+    "m2t_grad_norm_workspace_bytes": (_ll, []),
+    "m2t_adam_step_ex": (_i, [_vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _i, _f, _vp, _f, _i, _f, _vp, _vp]),
+    "m2t_profile_enable":(_i, [C.c_ulonglong]),
     "m2t_profile_read": (_i, [_i, C.POINTER(_d), C.POINTER(_ll)]),
     "m2t_profile_sample_every": (_i, [_i]),
     "m2t_swin_create": (_i, [C.POINTER(_vp), _i, _i]),

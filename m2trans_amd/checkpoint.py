@@ -16,6 +16,12 @@ fused step driver's flat moment buffers.  Pinned: the reference's model, optimis
 epochs and saved as train.py:341-349 does give the committed manifest ``tests/golden/checkpoint_manifest.json``
 (written by the pinning script of the test infrastructure); ``tests/test_host_cpu.py`` requires ``export_checkpoint``
 to match it key for key.
+
+With TrainStep's optimizer options on (max_grad_norm, weight_decay, ema_decay, skip_nonfinite) the dict additionally carries:
+the decay in torch's own ``param_groups`` (``weight_decay``, ``decoupled_weight_decay``), the APPLIED step number in every
+``step`` (optimizer steps that skip_nonfinite left out never happened), ``ema_state_dict`` (``module.``-prefixed, loadable
+strictly) and ``m2t_optim`` = {max_grad_norm, ema_decay, skip_nonfinite, skipped_steps}.  With every option off it is the dict
+above, key for key.
 """
 from __future__ import annotations
 
@@ -27,6 +33,47 @@ import torch
 
 def _param_index(model) -> Dict[str, int]:
     return {n: i for i, (n, _) in enumerate(model.named_parameters())}
+
+
+def ema_state_dict(model, ema_params) -> dict:
+    """The flat EMA buffer under the model's own state_dict names, as copies; the frozen MeanShift entries (and anything else
+    outside the flat buffer) are the model's, so ``model.load_state_dict(..., strict=True)`` accepts it."""
+    sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    for n, (o, k, shp) in zip(model._names, model._slots):
+        sd[n] = ema_params[o:o + k].view(shp).detach().clone()
+    return sd
+
+
+def _optim_options(train_step) -> dict:
+    """TrainStep's optimizer options, read with their "off" defaults (an object without them exports as before)."""
+    return {"max_grad_norm": getattr(train_step, "max_grad_norm", None),
+            "weight_decay": float(getattr(train_step, "weight_decay", 0.0)),
+            "decoupled_weight_decay": bool(getattr(train_step, "decoupled_weight_decay", False)),
+            "ema_decay": getattr(train_step, "ema_decay", None),
+            "skip_nonfinite": bool(getattr(train_step, "skip_nonfinite", False))}
+
+
+def _skipped(train_step) -> int:
+    s = getattr(train_step, "skipped_steps", None)
+    return 0 if s is None else int(float(s))
+
+
+def _reset_optim_state(train_step, model, ema_sd=None):
+    """After a load: the skipped count restarts at 0 (step_count is the applied count from here on) and the EMA weights come
+    from the file, or -- when it has none -- from the weights just loaded."""
+    rec = getattr(train_step, "optim_record", None)
+    if rec is not None:
+        rec.zero_()
+    ema = getattr(train_step, "ema_params", None)
+    if ema is None:
+        return
+    with torch.no_grad():
+        if ema_sd is None:
+            ema.copy_(model.flat_params.detach().to(ema))
+            return
+        for n, (o, k, shp) in zip(model._names, model._slots):
+            v = ema_sd["module." + n] if ("module." + n) in ema_sd else ema_sd[n]
+            ema[o:o + k].copy_(v.reshape(-1).to(ema))
 
 
 def export_checkpoint(model, train_step=None, epoch: int = 1, stat_dict: Optional[dict] = None,
@@ -42,7 +89,17 @@ def export_checkpoint(model, train_step=None, epoch: int = 1, stat_dict: Optiona
     out = {"epoch": int(epoch), "model_state_dict": sd}
     if train_step is not None:
         params = [p for _, p in model.named_parameters()]                 # ALL parameters, like train.py:81
-        opt = torch.optim.Adam(params, lr=lr0, weight_decay=0)
+        oo = _optim_options(train_step)
+        options_on = (oo["max_grad_norm"] is not None or oo["weight_decay"] != 0.0 or oo["ema_decay"] is not None
+                      or oo["skip_nonfinite"])
+        if oo["weight_decay"] != 0.0:
+            # torch's own param_groups carry the decay (decoupled_weight_decay is Adam's AdamW switch)
+            opt = torch.optim.Adam(params, lr=lr0, weight_decay=oo["weight_decay"],
+                                   decoupled_weight_decay=oo["decoupled_weight_decay"])
+        else:
+            opt = torch.optim.Adam(params, lr=lr0, weight_decay=0)
+        skipped = _skipped(train_step)
+        applied = int(train_step.step_count) - skipped                    # Adam's step number: skipped steps never happened
         sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, float(t_max), eta_min=eta_min)
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")                               # "scheduler.step() before optimizer.step()"
@@ -51,16 +108,21 @@ def export_checkpoint(model, train_step=None, epoch: int = 1, stat_dict: Optiona
         # the learning rate the step driver really used (equals the schedule's when the caller follows cosine_lr)
         opt.param_groups[0]["lr"] = float(train_step.lr)
         sched._last_lr = [float(train_step.lr)]
-        if train_step.step_count > 0:
+        if applied > 0:
             idx = _param_index(model)
             for n, (o, k, shp) in zip(model._names, model._slots):
                 p = params[idx[n]]
-                opt.state[p] = {"step": torch.tensor(float(train_step.step_count)),
+                opt.state[p] = {"step": torch.tensor(float(applied)),
                                 "exp_avg": train_step.exp_avg[o:o + k].view(shp).detach().cpu().clone(),
                                 "exp_avg_sq": train_step.exp_avg_sq[o:o + k].view(shp).detach().cpu().clone()}
         out["optimizer_state_dict"] = opt.state_dict()
         out["scheduler_state_dict"] = sched.state_dict()
     out["stat_dict"] = stat_dict or {}
+    if train_step is not None and options_on:
+        if getattr(train_step, "ema_params", None) is not None:
+            out["ema_state_dict"] = {"module." + k: v.cpu() for k, v in ema_state_dict(model, train_step.ema_params).items()}
+        out["m2t_optim"] = {"max_grad_norm": oo["max_grad_norm"], "ema_decay": oo["ema_decay"],
+                            "skip_nonfinite": oo["skip_nonfinite"], "skipped_steps": skipped}
     return out
 
 
@@ -82,6 +144,7 @@ def import_checkpoint(ckpt: dict, model, train_step=None) -> int:
         train_step.exp_avg_sq.zero_()
         train_step.step_count = 0
         train_step.scheduler_last_epoch = 0
+        _reset_optim_state(train_step, model, ckpt.get("ema_state_dict"))
         return 1
     if sch is None:
         # Adam state without the schedule it belongs to: the reference's --resume (train.py:97-103) always loads both, and
@@ -109,5 +172,21 @@ def import_checkpoint(ckpt: dict, model, train_step=None) -> int:
     pg = opt.get("param_groups")
     if pg:
         train_step.set_lr(pg[0]["lr"])
+    mo = ckpt.get("m2t_optim")
+    wd = float(pg[0].get("weight_decay", 0.0) or 0.0) if pg else 0.0
+    if mo is not None or wd != 0.0:
+        # the options the run was saved with (a file without them leaves the TrainStep's own untouched)
+        mo = mo or {}
+        new = {"max_grad_norm": mo.get("max_grad_norm", getattr(train_step, "max_grad_norm", None)), "weight_decay": wd,
+               "decoupled_weight_decay": bool(pg[0].get("decoupled_weight_decay", False)) if pg else False,
+               "ema_decay": mo.get("ema_decay", getattr(train_step, "ema_decay", None)),
+               "skip_nonfinite": bool(mo.get("skip_nonfinite", getattr(train_step, "skip_nonfinite", False)))}
+        if new != _optim_options(train_step):
+            if hasattr(train_step, "_init_optim_options"):       # TrainStep: (re)allocates the record and the EMA buffer it needs
+                train_step._init_optim_options(track_grad_norm=getattr(train_step, "track_grad_norm", False), **new)
+            else:
+                for k, v in new.items():
+                    setattr(train_step, k, v)
+    _reset_optim_state(train_step, model, ckpt.get("ema_state_dict"))
     train_step.scheduler_last_epoch = int(sch.get("last_epoch", 0))
     return int(ckpt.get("epoch", 0)) + 1

@@ -1313,6 +1313,27 @@ extern "C" int m2t_grad_accumulate(float* acc, const float* g, long long n, floa
   return launch_grad_accumulate(acc, g, n, loss_acc, loss_part, (hipStream_t)stream);
 }
 
+extern "C" long long m2t_grad_norm_workspace_bytes(void) { return (long long)M2T_GNORM_BLOCKS * (long long)sizeof(double); }
+
+extern "C" int m2t_grad_norm(const float* grads, long long n, float grad_scale, float max_norm, int skip_nonfinite, int step,
+                             float beta1, float beta2, double* record, void* workspace, void* stream) {
+  if (n < 0 || (n > 0 && !grads) || !record || !workspace || step < 1 || max_norm != max_norm)
+    return m2t_set_error(M2T_ERR_ARG, "m2t_grad_norm: bad argument");
+  return launch_grad_norm(grads, n, grad_scale, max_norm, skip_nonfinite != 0, step, beta1, beta2, record, (double*)workspace,
+                          (hipStream_t)stream);
+}
+
+extern "C" int m2t_adam_step_ex(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, float lr,
+                                float beta1, float beta2, float eps, int step, float grad_scale, float* ema, float weight_decay,
+                                int decoupled, float ema_decay, const double* record, void* stream) {
+  if (n < 0 || (n > 0 && (!params || !grads || !exp_avg || !exp_avg_sq)) || step < 1 || !(weight_decay >= 0.f) ||
+      !(ema_decay >= 0.f && ema_decay < 1.f))
+    return m2t_set_error(M2T_ERR_ARG, "m2t_adam_step_ex: bad argument");
+  if (n == 0) return 0;
+  return launch_adam_ex(params, grads, exp_avg, exp_avg_sq, ema, n, lr, beta1, beta2, eps, step, grad_scale, weight_decay,
+                        decoupled != 0, ema_decay, record, (hipStream_t)stream);
+}
+
 // ---- stand-alone operators ---------------------------------------------------------------
 extern "C" int m2t_dwt(int dtype, int levels, const void* src, void* dst, int B, int H, int W, int C, void* stream) {
   return launch_dwt(dtype, levels, src, C, 0, dst, C << (2 * levels), 0, B, H, W, C, false, (hipStream_t)stream);

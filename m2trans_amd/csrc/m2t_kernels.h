@@ -96,6 +96,15 @@ int launch_adam(float* p, const float* g, float* m, float* v, long long n, float
                 int step, float gscale, hipStream_t st);
 // acc[0 .. n) += g (one fp32 addition per element); loss_acc[0] += loss_part[0] when both are given (same launch)
 int launch_grad_accumulate(float* acc, const float* g, long long n, float* loss_acc, const float* loss_part, hipStream_t st);
+// ---- k_optim.hip: gradient norm -> optimizer record; Adam with clip / weight decay / EMA / skip in one pass
+#define M2T_GNORM_BLOCKS 256          // workgroups (= fp64 partials) of the norm's first stage: a constant, so the tree depends on n alone
+#define M2T_GNORM_THREADS 1024       // threads per workgroup of that stage (a constant for the same reason)
+#define M2T_OPTIM_RECORD_DOUBLES 8    // norm, finite, clip_coef, applied, skipped, bc1, sqrt(bc2), effective step
+int launch_grad_norm(const float* g, long long n, float gscale, float max_norm, int skip_nonfinite, int step, float b1, float b2,
+                     double* rec, double* part, hipStream_t st);
+// ema / rec may be nullptr (no EMA; no clip, no skip, host bias correction from `step`)
+int launch_adam_ex(float* p, const float* g, float* m, float* v, float* ema, long long n, float lr, float b1, float b2, float eps,
+                   int step, float gscale, float wd, int decoupled, float ema_d, const double* rec, hipStream_t st);
 // blocks: device table int2[nblocks] = (descriptor index, chunk of M2T_PACK_CHUNK output elements)
 int launch_pack(int dt, const float* master, void* packed, const m2t_pack_desc* descs, const void* blocks, int nblocks, hipStream_t st);
 int launch_layout(int dt, const float* nchw, void* nhwc, float* nchw_out, int B, int C, int HW, int inverse, hipStream_t st);

@@ -19,6 +19,11 @@ count, so SUM-all-reduced gradients equal the full-batch gradient (SURVEY sectio
 Gradient accumulation (``accum_steps=k``; replaces torch's AccumulateGrad under several ``loss.backward()`` calls before one
 ``optimizer.step()``): a micro-batch is a rank that runs later on the same device -- the same global divisor, the sum taken by
 one streaming HIP pass per micro-batch (m2t_grad_accumulate), one exchange and one Adam pass per k micro-batches.
+
+Optimizer options (all off by default; replace ``clip_grad_norm_``, Adam's ``weight_decay`` / ``decoupled_weight_decay`` -- the
+knob train.py:81 passes -- and a hand-kept EMA copy): the global norm of the accumulated, all-reduced gradient goes into a
+device-resident record (m2t_grad_norm: two launches, fp64, no atomics), and ONE pass (m2t_adam_step_ex) clips, decays, steps
+and updates the EMA weights -- or, with ``skip_nonfinite`` and a non-finite norm, touches nothing.  No host synchronisation.
 """
 from __future__ import annotations
 
@@ -57,7 +62,9 @@ class TrainStep:
                  lambda_l1: float = 1.0, process_group=None, world_size: Optional[int] = None,
                  grad_bucket_dtype: torch.dtype = torch.float32, semantic_loss=None, lambda_clip: float = 0.0,
                  overlap_comm: bool = True, force_comm_path: bool = False, overlap_semantic: bool = True,
-                 accum_steps: int = 1):
+                 accum_steps: int = 1, max_grad_norm: Optional[float] = None, weight_decay: float = 0.0,
+                 decoupled_weight_decay: bool = False, ema_decay: Optional[float] = None, skip_nonfinite: bool = False,
+                 track_grad_norm: bool = False):
         self.model = model
         # gradient accumulation: one optimizer step consumes accum_steps equal micro-batches (forward_backward calls); the
         # gradients and the loss of calls 2..k of a cycle are added to the first call's by m2t_grad_accumulate
@@ -106,6 +113,63 @@ class TrainStep:
         # timing events per step (exposed_comm_events: [(before, after)]) -- what the exchange costs the step after the overlap
         self.measure_exposed_comm = False
         self.exposed_comm_events = []
+        self._init_optim_options(max_grad_norm, weight_decay, decoupled_weight_decay, ema_decay, skip_nonfinite, track_grad_norm)
+
+    def _init_optim_options(self, max_grad_norm, weight_decay, decoupled_weight_decay, ema_decay, skip_nonfinite, track_grad_norm):
+        """Gradient-norm clipping, weight decay, EMA weights and the non-finite skip (m2t_grad_norm + m2t_adam_step_ex).  With
+        every option off nothing is allocated and optimizer_step() stays the single m2t_adam_step call."""
+        if max_grad_norm is not None and not (float(max_grad_norm) > 0.0 and math.isfinite(float(max_grad_norm))):
+            raise _lib.M2TError(f"max_grad_norm must be None or a finite number > 0, got {max_grad_norm!r}")
+        if not (float(weight_decay) >= 0.0 and math.isfinite(float(weight_decay))):
+            raise _lib.M2TError(f"weight_decay must be a finite number >= 0, got {weight_decay!r}")
+        if ema_decay is not None and not (0.0 <= float(ema_decay) < 1.0):
+            raise _lib.M2TError(f"ema_decay must be None or in [0, 1), got {ema_decay!r}")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.weight_decay = float(weight_decay)
+        self.decoupled_weight_decay = bool(decoupled_weight_decay)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.track_grad_norm = bool(track_grad_norm)
+        flat = self.model.flat_params
+        # the optimizer record (include/m2t.h, m2t_grad_norm): 8 doubles on the device, written by the norm's second stage
+        self._use_norm = self.max_grad_norm is not None or self.skip_nonfinite or self.track_grad_norm
+        self.optim_record = self._norm_ws = None
+        self.grad_norm = self.clip_coef = self.skipped_steps = None
+        if self._use_norm:
+            self.optim_record = torch.zeros(8, dtype=torch.float64, device=flat.device)
+            self._norm_ws = torch.empty(int(_lib.load().m2t_grad_norm_workspace_bytes()) // 8, dtype=torch.float64, device=flat.device)
+            # views of the record: reading one is the caller's synchronisation, at the caller's cadence
+            self.grad_norm, self.clip_coef, self.skipped_steps = self.optim_record[0], self.optim_record[2], self.optim_record[4]
+        self.ema_params = flat.detach().clone() if self.ema_decay is not None else None
+        self._optim_ex = self._use_norm or self.weight_decay != 0.0 or self.ema_params is not None
+
+    def applied_step_count(self) -> int:
+        """step_count minus the optimizer steps skip_nonfinite left out (Adam's effective step number).  Synchronises."""
+        return self.step_count - (int(self.skipped_steps.item()) if self.skipped_steps is not None else 0)
+
+    def _need_ema(self, what: str):
+        if self.ema_params is None:
+            raise _lib.M2TError(f"{what}: this TrainStep keeps no EMA weights (ema_decay=None)")
+
+    def ema_state_dict(self) -> dict:
+        """The EMA weights under the model's own state_dict names (the frozen MeanShift entries are the model's), as copies:
+        ``model.load_state_dict(ts.ema_state_dict(), strict=True)`` works."""
+        self._need_ema("ema_state_dict")
+        from .checkpoint import ema_state_dict
+        return ema_state_dict(self.model, self.ema_params)
+
+    def swap_ema(self):
+        """Exchange the contents of model.flat_params and ema_params in place (a validation sweep between epochs runs the model on
+        the EMA weights, a second call puts every bit back).  Plain torch copies: this is off the timed path."""
+        self._need_ema("swap_ema")
+        if self.micro_count != 0:
+            raise _lib.M2TError(f"swap_ema in the middle of an accumulation cycle ({self.micro_count} of {self.accum_steps} "
+                                "micro-batches since the last optimizer step)")
+        flat = self.model.flat_params
+        with torch.no_grad():
+            tmp = flat.detach().clone()
+            flat.copy_(self.ema_params)
+            self.ema_params.copy_(tmp)
 
     def set_lr(self, lr: float):
         self.lr = float(lr)
@@ -278,10 +342,28 @@ class TrainStep:
         self.step_count += 1
         lib = _lib.load()
         with torch.cuda.device(self.grads.device):
+            if self._optim_ex:
+                self._optimizer_step_ex(lib, _lib.stream_ptr())
+                return
             _lib.check(lib.m2t_adam_step(_lib.ptr(self.model.flat_params), _lib.ptr(self.grads), _lib.ptr(self.exp_avg),
                                          _lib.ptr(self.exp_avg_sq), self.grads.numel(), self.lr, self.betas[0],
                                          self.betas[1], self.eps, self.step_count, 1.0, _lib.stream_ptr()),
                        "m2t_adam_step")
+
+    def _optimizer_step_ex(self, lib, st):
+        """The step with options: the norm of the accumulated, all-reduced gradient (this runs behind the last accumulate and
+        behind the wait for the communication stream, so every rank computes the same number and takes the same skip decision
+        without a collective) into the record, then ONE pass that clips, decays, steps and updates the EMA -- or does nothing."""
+        n = self.grads.numel()
+        if self._use_norm:
+            _lib.check(lib.m2t_grad_norm(_lib.ptr(self.grads), n, 1.0, self.max_grad_norm or 0.0, int(self.skip_nonfinite),
+                                         self.step_count, self.betas[0], self.betas[1], _lib.ptr(self.optim_record),
+                                         _lib.ptr(self._norm_ws), st), "m2t_grad_norm")
+        _lib.check(lib.m2t_adam_step_ex(_lib.ptr(self.model.flat_params), _lib.ptr(self.grads), _lib.ptr(self.exp_avg),
+                                        _lib.ptr(self.exp_avg_sq), n, self.lr, self.betas[0], self.betas[1], self.eps,
+                                        self.step_count, 1.0, _lib.ptr(self.ema_params), self.weight_decay,
+                                        int(self.decoupled_weight_decay), self.ema_decay or 0.0, _lib.ptr(self.optim_record), st),
+                   "m2t_adam_step_ex")
 
     # -- the step ----------------------------------------------------------------------------
     def step(self, lr_img: torch.Tensor, hr_img: torch.Tensor, captions=None) -> torch.Tensor:
