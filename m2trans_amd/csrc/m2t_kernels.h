@@ -53,6 +53,7 @@ bool m2t_prof_take(hipEvent_t* a, hipEvent_t* b);
 // an armed fork event (m2t_backward, option "fork_on_kernel") rides on the dispatch as its stop event instead of being recorded by
 // a marker packet behind it; nullptr when none is armed or a timing pair already took the dispatch
 hipEvent_t m2t_fork_take();
+extern thread_local hipEvent_t g_m2t_fork_armed;      // (m2t_prof.hip; set and cleared by m2t_backward only)
 #define M2T_LAUNCH_TIMED(kernel, grid, block, sh, st, ...)                                                       \
   do {                                                                                                           \
     hipEvent_t ea__, eb__;                                                                                       \

@@ -3,31 +3,19 @@
 // forward only by default (the reference runs it under torch.no_grad()); the opt-in data gradient
 // (m2t_swin_encode_grad / m2t_swin_backward) has its kernels in k_swin_bwd.hip.  Host code; forward
 // kernels in k_swin.hip and k_gemm.hip.
-#include <map>
-#include <string>
-#include <vector>
 #include "m2t_kernels.h"
+#include "m2t_layout.h"
 #include <cstring>
 #include "../../include/m2t.h"
 
 namespace {
 const int DEPTHS[4] = {2, 2, 6, 2};
 const int HEADS[4] = {3, 6, 12, 24};
-struct Ws { size_t off, n; };
 }
 
 struct m2t_swin {
   int max_images, dt;
-  size_t esz;
-  std::vector<std::string> pnames;
-  std::map<std::string, long long> poff, pnum;
-  long long nparams = 0;
-  std::map<std::string, long long> pk;     // packed (T) offsets in elements
-  long long npacked = 0;
-  std::map<std::string, long long> fb;     // fp32 side buffers (fused qkv biases) offsets in floats
-  long long nfb = 0;
-  std::map<std::string, Ws> ws;
-  size_t ws_bytes = 0;
+  m2t_layout lay;
   const float* weights = nullptr;          // caller's flat fp32 weights (device), set by load_weights
   // crop tables travel through a small ring of PINNED host slots, so the upload is a true asynchronous copy and the call returns
   // without waiting for the stream (round 3: the hipStreamSynchronize that protected a pageable temporary made every
@@ -39,87 +27,74 @@ struct m2t_swin {
   int pin_next = 0;
   // opt-in data gradient (m2t_swin_encode_grad / m2t_swin_backward): the grad workspace's layout for grad_n crops, the
   // workspace whose transposed weights are current, and the crop count of the last stash
-  std::map<std::string, Ws> gws;
-  size_t gws_bytes = 0;
+  m2t_region gws;
   int gws_n = -1;
   const void* gws_packed = nullptr;
   int grad_n = 0;
   const void* grad_ws = nullptr;
-  void add_gws(const std::string& n, size_t elems, size_t es) {
-    gws_bytes = (gws_bytes + 255) & ~(size_t)255;
-    gws[n] = Ws{gws_bytes, elems};
-    gws_bytes += elems * es;
-  }
   bool fused_mlp = true;                   // bf16, stages 1 / 2: LayerNorm + fc1 + GELU + fc2 + residual in one kernel (k_swin.hip)
-  void add_param(const std::string& n, long long c) { pnames.push_back(n); poff[n] = nparams; pnum[n] = c; nparams += c; }
-  void add_pack(const std::string& n, long long c) { npacked = (npacked + 7) & ~7LL; pk[n] = npacked; npacked += c; }
-  void add_ws(const std::string& n, size_t elems, size_t es) {
-    ws_bytes = (ws_bytes + 255) & ~(size_t)255;
-    ws[n] = Ws{ws_bytes, elems};
-    ws_bytes += elems * es;
-  }
 };
 
 extern "C" int m2t_swin_create(m2t_swin** out, int max_images, int dtype) {
   if (!out || max_images < 1 || (dtype != M2T_F32 && dtype != M2T_BF16)) return m2t_set_error(M2T_ERR_ARG, "m2t_swin_create: bad argument");
   m2t_swin* p = new m2t_swin();
-  p->max_images = max_images; p->dt = dtype; p->esz = (dtype == M2T_F32) ? 4 : 2;
+  p->max_images = max_images; p->dt = dtype; p->lay.esz = (dtype == M2T_F32) ? 4 : 2;
   // parameter inventory: HF swin-tiny checkpoint names (transformers 4.24), + the MedCLIP projection
-  p->add_param("embeddings.patch_embeddings.projection.weight", 96 * 48);
-  p->add_param("embeddings.patch_embeddings.projection.bias", 96);
-  p->add_param("embeddings.norm.weight", 96);
-  p->add_param("embeddings.norm.bias", 96);
-  p->add_pack("pe", 96 * 48);
+  p->lay.add_param("embeddings.patch_embeddings.projection.weight", 96 * 48);
+  p->lay.add_param("embeddings.patch_embeddings.projection.bias", 96);
+  p->lay.add_param("embeddings.norm.weight", 96);
+  p->lay.add_param("embeddings.norm.bias", 96);
+  p->lay.add_pack("pe", 96 * 48);
   for (int s = 0; s < 4; ++s) {
     const long long C = 96LL << s;
     for (int j = 0; j < DEPTHS[s]; ++j) {
       const std::string b = "encoder.layers." + std::to_string(s) + ".blocks." + std::to_string(j) + ".";
-      p->add_param(b + "layernorm_before.weight", C);
-      p->add_param(b + "layernorm_before.bias", C);
+      p->lay.add_param(b + "layernorm_before.weight", C);
+      p->lay.add_param(b + "layernorm_before.bias", C);
       for (const char* nm : {"query", "key", "value"}) {
-        p->add_param(b + "attention.self." + nm + ".weight", C * C);
-        p->add_param(b + "attention.self." + nm + ".bias", C);
+        p->lay.add_param(b + "attention.self." + nm + ".weight", C * C);
+        p->lay.add_param(b + "attention.self." + nm + ".bias", C);
       }
-      p->add_param(b + "attention.self.relative_position_bias_table", 169LL * HEADS[s]);
-      p->add_param(b + "attention.output.dense.weight", C * C);
-      p->add_param(b + "attention.output.dense.bias", C);
-      p->add_param(b + "layernorm_after.weight", C);
-      p->add_param(b + "layernorm_after.bias", C);
-      p->add_param(b + "intermediate.dense.weight", 4 * C * C);
-      p->add_param(b + "intermediate.dense.bias", 4 * C);
-      p->add_param(b + "output.dense.weight", 4 * C * C);
-      p->add_param(b + "output.dense.bias", C);
-      p->add_pack(b + "qkv", 3 * C * C);
-      p->add_pack(b + "o", C * C);
-      p->add_pack(b + "fc1", 4 * C * C);
-      p->add_pack(b + "fc2", 4 * C * C);
-      if (s < 2) { p->add_pack(b + "fc1F", 4 * C * C); p->add_pack(b + "fc2F", 4 * C * C); }   // MFMA fragment order: fused MLP of stages 1 / 2
-      p->fb[b + "qkv_bias"] = p->nfb; p->nfb += 3 * C;
+      p->lay.add_param(b + "attention.self.relative_position_bias_table", 169LL * HEADS[s]);
+      p->lay.add_param(b + "attention.output.dense.weight", C * C);
+      p->lay.add_param(b + "attention.output.dense.bias", C);
+      p->lay.add_param(b + "layernorm_after.weight", C);
+      p->lay.add_param(b + "layernorm_after.bias", C);
+      p->lay.add_param(b + "intermediate.dense.weight", 4 * C * C);
+      p->lay.add_param(b + "intermediate.dense.bias", 4 * C);
+      p->lay.add_param(b + "output.dense.weight", 4 * C * C);
+      p->lay.add_param(b + "output.dense.bias", C);
+      p->lay.add_pack(b + "qkv", 3 * C * C);
+      p->lay.add_pack(b + "o", C * C);
+      p->lay.add_pack(b + "fc1", 4 * C * C);
+      p->lay.add_pack(b + "fc2", 4 * C * C);
+      if (s < 2) { p->lay.add_pack(b + "fc1F", 4 * C * C); p->lay.add_pack(b + "fc2F", 4 * C * C); }   // MFMA fragment order: fused MLP of stages 1 / 2
+      p->lay.add_fb(b + "qkv_bias", 3 * C);
     }
     if (s < 3) {
       const std::string d = "encoder.layers." + std::to_string(s) + ".downsample.";
-      p->add_param(d + "norm.weight", 4 * C);
-      p->add_param(d + "norm.bias", 4 * C);
-      p->add_param(d + "reduction.weight", 8 * C * C);
-      p->add_pack(d + "red", 8 * C * C);
+      p->lay.add_param(d + "norm.weight", 4 * C);
+      p->lay.add_param(d + "norm.bias", 4 * C);
+      p->lay.add_param(d + "reduction.weight", 8 * C * C);
+      p->lay.add_pack(d + "red", 8 * C * C);
     }
   }
-  p->add_param("layernorm.weight", 768);
-  p->add_param("layernorm.bias", 768);
-  p->add_param("projection_head.weight", 512 * 768);
-  const size_t n = (size_t)max_images, es = p->esz;
+  p->lay.add_param("layernorm.weight", 768);
+  p->lay.add_param("layernorm.bias", 768);
+  p->lay.add_param("projection_head.weight", 512 * 768);
+  const size_t n = (size_t)max_images, es = p->lay.esz;
   const size_t tok = n * 3136 * 96;             // elements of the widest token tensor at every stage
-  p->add_ws("packed", (size_t)p->npacked, es);
-  p->add_ws("fbias", (size_t)p->nfb, 4);
-  p->add_ws("crops", n * 3, 4);
-  p->add_ws("A0", n * 3136 * 48, es);
-  p->add_ws("X", tok, es);
-  p->add_ws("Hn", tok, es);
-  p->add_ws("QKV", tok * 3, es);
-  p->add_ws("AO", tok, es);
-  p->add_ws("MH", tok * 4, es);
-  p->add_ws("emb", n * 512, 4);
-  p->ws_bytes = (p->ws_bytes + 255) & ~(size_t)255;
+  p->lay.ws.add("packed", (size_t)p->lay.npacked, es);
+  p->lay.ws.add("fbias", (size_t)p->lay.nfb, 4);
+  p->lay.ws.add("crops", n * 3, 4);
+  p->lay.ws.add("A0", n * 3136 * 48, es);
+  p->lay.ws.add("X", tok, es);
+  p->lay.ws.add("Hn", tok, es);
+  p->lay.ws.add("QKV", tok * 3, es);
+  p->lay.ws.add("AO", tok, es);
+  p->lay.ws.add("MH", tok * 4, es);
+  p->lay.ws.add("emb", n * 512, 4);
+  p->lay.ws.seal();
   *out = p;
   return 0;
 }
@@ -134,26 +109,12 @@ extern "C" void m2t_swin_destroy(m2t_swin* p) {
 extern "C" long long m2t_swin_query(const m2t_swin* p, const char* key) {
   if (!p || !key) return -1;
   const std::string k(key);
-  if (k == "workspace_bytes") return (long long)p->ws_bytes;
-  if (k == "num_params") return p->nparams;
-  if (k == "num_param_tensors") return (long long)p->pnames.size();
   if (k == "max_images") return p->max_images;
-  if (k.rfind("param:", 0) == 0) { auto it = p->poff.find(k.substr(6)); return it == p->poff.end() ? -1 : it->second; }
-  if (k.rfind("numel:", 0) == 0) { auto it = p->pnum.find(k.substr(6)); return it == p->pnum.end() ? -1 : it->second; }
-  if (k.rfind("name:", 0) == 0) return -1;
-  if (k.rfind("ws:", 0) == 0) { auto it = p->ws.find(k.substr(3)); return it == p->ws.end() ? -1 : (long long)it->second.off; }
-  return -1;
+  return p->lay.query(k, m2t_layout::Q_WS);
 }
 // i-th parameter name in flat order (so the Python side never duplicates the inventory)
 extern "C" const char* m2t_swin_param_name(const m2t_swin* p, int i) {
-  if (!p || i < 0 || i >= (int)p->pnames.size()) return nullptr;
-  return p->pnames[i].c_str();
-}
-
-#define SWP(name) ((char*)workspace + p->ws.at(name).off)
-#define CKS(call) do { int rc__ = (call); if (rc__) return rc__; } while (0)
-static inline char* spk(const m2t_swin* p, void* workspace, const std::string& k) {
-  return (char*)workspace + p->ws.at("packed").off + p->pk.at(k) * p->esz;
+  return p ? p->lay.param_name(i) : nullptr;
 }
 
 // one-time: convert the frozen fp32 weights to the element type / fused layouts the kernels read
@@ -163,31 +124,31 @@ extern "C" int m2t_swin_load_weights(m2t_swin* p, const float* weights, void* wo
   const int dt = p->dt;
   p->weights = weights;
   p->gws_packed = nullptr;                 // the transposed weights of a grad workspace are re-derived on its next use
-  float* fbias = (float*)SWP("fbias");
-  CKS(launch_convert(dt, weights + p->poff.at("embeddings.patch_embeddings.projection.weight"), spk(p, workspace, "pe"), 96 * 48, st));
+  float* fbias = (float*)WSP("fbias");
+  CK(launch_convert(dt, weights + p->lay.poff.at("embeddings.patch_embeddings.projection.weight"), p->lay.packed_ptr(workspace, "pe"), 96 * 48, st));
   for (int s = 0; s < 4; ++s) {
     const long long C = 96LL << s;
     for (int j = 0; j < DEPTHS[s]; ++j) {
       const std::string b = "encoder.layers." + std::to_string(s) + ".blocks." + std::to_string(j) + ".";
       int part = 0;
       for (const char* nm : {"query", "key", "value"}) {
-        CKS(launch_convert(dt, weights + p->poff.at(b + "attention.self." + nm + ".weight"),
-                           spk(p, workspace, b + "qkv") + (size_t)part * C * C * p->esz, C * C, st));
-        CKS(launch_convert(M2T_F32, weights + p->poff.at(b + "attention.self." + nm + ".bias"),
-                           fbias + p->fb.at(b + "qkv_bias") + part * C, C, st));
+        CK(launch_convert(dt, weights + p->lay.poff.at(b + "attention.self." + nm + ".weight"),
+                           p->lay.packed_ptr(workspace, b + "qkv") + (size_t)part * C * C * p->lay.esz, C * C, st));
+        CK(launch_convert(M2T_F32, weights + p->lay.poff.at(b + "attention.self." + nm + ".bias"),
+                           fbias + p->lay.fb.at(b + "qkv_bias") + part * C, C, st));
         ++part;
       }
-      CKS(launch_convert(dt, weights + p->poff.at(b + "attention.output.dense.weight"), spk(p, workspace, b + "o"), C * C, st));
-      CKS(launch_convert(dt, weights + p->poff.at(b + "intermediate.dense.weight"), spk(p, workspace, b + "fc1"), 4 * C * C, st));
-      CKS(launch_convert(dt, weights + p->poff.at(b + "output.dense.weight"), spk(p, workspace, b + "fc2"), 4 * C * C, st));
+      CK(launch_convert(dt, weights + p->lay.poff.at(b + "attention.output.dense.weight"), p->lay.packed_ptr(workspace, b + "o"), C * C, st));
+      CK(launch_convert(dt, weights + p->lay.poff.at(b + "intermediate.dense.weight"), p->lay.packed_ptr(workspace, b + "fc1"), 4 * C * C, st));
+      CK(launch_convert(dt, weights + p->lay.poff.at(b + "output.dense.weight"), p->lay.packed_ptr(workspace, b + "fc2"), 4 * C * C, st));
       if (s < 2) {
-        CKS(launch_frag16_pack(dt, weights + p->poff.at(b + "intermediate.dense.weight"), spk(p, workspace, b + "fc1F"), (int)(4 * C), (int)C, st));
-        CKS(launch_frag16_pack(dt, weights + p->poff.at(b + "output.dense.weight"), spk(p, workspace, b + "fc2F"), (int)C, (int)(4 * C), st));
+        CK(launch_frag16_pack(dt, weights + p->lay.poff.at(b + "intermediate.dense.weight"), p->lay.packed_ptr(workspace, b + "fc1F"), (int)(4 * C), (int)C, st));
+        CK(launch_frag16_pack(dt, weights + p->lay.poff.at(b + "output.dense.weight"), p->lay.packed_ptr(workspace, b + "fc2F"), (int)C, (int)(4 * C), st));
       }
     }
     if (s < 3) {
       const std::string d = "encoder.layers." + std::to_string(s) + ".downsample.";
-      CKS(launch_convert(dt, weights + p->poff.at(d + "reduction.weight"), spk(p, workspace, d + "red"), 8 * C * C, st));
+      CK(launch_convert(dt, weights + p->lay.poff.at(d + "reduction.weight"), p->lay.packed_ptr(workspace, d + "red"), 8 * C * C, st));
     }
   }
   return 0;
@@ -225,49 +186,48 @@ extern "C" int m2t_swin_encode_pair(m2t_swin* p, const float* src, int n_a, cons
 static void grad_layout(m2t_swin* p, int ng) {
   if (p->gws_n == ng) return;
   p->gws.clear();
-  p->gws_bytes = 0;
-  const size_t es = p->esz, g = (size_t)ng, tok = g * 3136 * 96;
+  const size_t es = p->lay.esz, g = (size_t)ng, tok = g * 3136 * 96;
   for (int s = 0; s < 4; ++s) {
     const size_t C = 96u << s;
     for (int j = 0; j < DEPTHS[s]; ++j) {
       const std::string b = "encoder.layers." + std::to_string(s) + ".blocks." + std::to_string(j) + ".";
-      p->add_gws(b + "qkvT", 3 * C * C, es);
-      p->add_gws(b + "oT", C * C, es);
-      p->add_gws(b + "fc1T", 4 * C * C, es);
-      p->add_gws(b + "fc2T", 4 * C * C, es);
+      p->gws.add(b + "qkvT", 3 * C * C, es);
+      p->gws.add(b + "oT", C * C, es);
+      p->gws.add(b + "fc1T", 4 * C * C, es);
+      p->gws.add(b + "fc2T", 4 * C * C, es);
     }
-    if (s < 3) p->add_gws("encoder.layers." + std::to_string(s) + ".downsample.redT", 8 * C * C, es);
+    if (s < 3) p->gws.add("encoder.layers." + std::to_string(s) + ".downsample.redT", 8 * C * C, es);
   }
-  p->add_gws("gR", tok, 4);            // residual-stream gradient (fp32 in both modes)
-  p->add_gws("gF", tok, 4);            // fp32 LayerNorm-gradient scratch (merge, embedding)
-  p->add_gws("gT", tok, es);           // storage-type copy of gR: the operand of the next data-gradient GEMM
-  p->add_gws("gC", tok, es);
-  p->add_gws("gQ", tok * 3, es);
-  p->add_gws("gA", tok * 4, es);
-  p->add_gws("e0", tok, es);
+  p->gws.add("gR", tok, 4);            // residual-stream gradient (fp32 in both modes)
+  p->gws.add("gF", tok, 4);            // fp32 LayerNorm-gradient scratch (merge, embedding)
+  p->gws.add("gT", tok, es);           // storage-type copy of gR: the operand of the next data-gradient GEMM
+  p->gws.add("gC", tok, es);
+  p->gws.add("gQ", tok * 3, es);
+  p->gws.add("gA", tok * 4, es);
+  p->gws.add("e0", tok, es);
   for (int s = 0; s < 4; ++s) {
     const size_t tc = tok >> s;        // tokens x channels of stage s
     for (int j = 0; j < DEPTHS[s]; ++j) {
       const std::string b = "s" + std::to_string(s) + "b" + std::to_string(j) + ".";
-      p->add_gws(b + "xin", tc, es);
-      p->add_gws(b + "xmid", tc, es);
-      p->add_gws(b + "qkv", 3 * tc, es);
-      p->add_gws(b + "gder", 4 * tc, es);
+      p->gws.add(b + "xin", tc, es);
+      p->gws.add(b + "xmid", tc, es);
+      p->gws.add(b + "qkv", 3 * tc, es);
+      p->gws.add(b + "gder", 4 * tc, es);
     }
-    if (s < 3) p->add_gws("m" + std::to_string(s), tc, es);
+    if (s < 3) p->gws.add("m" + std::to_string(s), tc, es);
   }
-  p->add_gws("xf", g * 49 * 768, es);
-  p->add_gws("hnf", g * 49 * 768, es);
-  p->add_gws("MD", (size_t)p->max_images * 3136 * 96 * 4, es);   // gelu'(fc1) of every crop of the call (stash keeps the first n_grad)
-  p->gws_bytes = (p->gws_bytes + 255) & ~(size_t)255;
+  p->gws.add("xf", g * 49 * 768, es);
+  p->gws.add("hnf", g * 49 * 768, es);
+  p->gws.add("MD", (size_t)p->max_images * 3136 * 96 * 4, es);   // gelu'(fc1) of every crop of the call (stash keeps the first n_grad)
+  p->gws.seal();
   p->gws_n = ng;
 }
-#define GWP(name) ((char*)grad_ws + p->gws.at(name).off)
+#define GWP(name) (p->gws.ptr(grad_ws, name))
 
 extern "C" long long m2t_swin_grad_workspace_bytes(m2t_swin* p, int n_grad) {
   if (!p || n_grad < 1 || n_grad > p->max_images) return m2t_set_error(M2T_ERR_ARG, "m2t_swin_grad_workspace_bytes: n_grad out of range");
   grad_layout(p, n_grad);
-  return (long long)p->gws_bytes;
+  return (long long)p->gws.bytes;
 }
 
 static int pack_grad_weights(m2t_swin* p, void* grad_ws, hipStream_t st) {
@@ -279,14 +239,14 @@ static int pack_grad_weights(m2t_swin* p, void* grad_ws, hipStream_t st) {
       const std::string b = "encoder.layers." + std::to_string(s) + ".blocks." + std::to_string(j) + ".";
       int part = 0;
       for (const char* nm : {"query", "key", "value"})
-        CKS(launch_transpose_convert(dt, wt + p->poff.at(b + "attention.self." + nm + ".weight"), GWP(b + "qkvT"), C, C, 3 * C, C * part++, st));
-      CKS(launch_transpose_convert(dt, wt + p->poff.at(b + "attention.output.dense.weight"), GWP(b + "oT"), C, C, C, 0, st));
-      CKS(launch_transpose_convert(dt, wt + p->poff.at(b + "intermediate.dense.weight"), GWP(b + "fc1T"), 4 * C, C, 4 * C, 0, st));
-      CKS(launch_transpose_convert(dt, wt + p->poff.at(b + "output.dense.weight"), GWP(b + "fc2T"), C, 4 * C, C, 0, st));
+        CK(launch_transpose_convert(dt, wt + p->lay.poff.at(b + "attention.self." + nm + ".weight"), GWP(b + "qkvT"), C, C, 3 * C, C * part++, st));
+      CK(launch_transpose_convert(dt, wt + p->lay.poff.at(b + "attention.output.dense.weight"), GWP(b + "oT"), C, C, C, 0, st));
+      CK(launch_transpose_convert(dt, wt + p->lay.poff.at(b + "intermediate.dense.weight"), GWP(b + "fc1T"), 4 * C, C, 4 * C, 0, st));
+      CK(launch_transpose_convert(dt, wt + p->lay.poff.at(b + "output.dense.weight"), GWP(b + "fc2T"), C, 4 * C, C, 0, st));
     }
     if (s < 3) {
       const std::string d = "encoder.layers." + std::to_string(s) + ".downsample.";
-      CKS(launch_transpose_convert(dt, wt + p->poff.at(d + "reduction.weight"), GWP(d + "redT"), 2 * C, 4 * C, 2 * C, 0, st));
+      CK(launch_transpose_convert(dt, wt + p->lay.poff.at(d + "reduction.weight"), GWP(d + "redT"), 2 * C, 4 * C, 2 * C, 0, st));
     }
   }
   p->gws_packed = grad_ws;
@@ -315,14 +275,14 @@ static int encode_impl(m2t_swin* p, const float* src, int n_a, const float* src_
   const bool G = grad_ws != nullptr;
   if (G) {
     grad_layout(p, n_grad);
-    if (p->gws_packed != grad_ws) CKS(pack_grad_weights(p, grad_ws, st));
+    if (p->gws_packed != grad_ws) CK(pack_grad_weights(p, grad_ws, st));
     p->grad_n = 0;                     // until the stash below is complete
     p->grad_ws = grad_ws;
   }
   // grad mode: the first n_grad crops' copy of a token tensor (contiguous rows at the front of the batch) into the stash
   auto stash = [&](const void* from, const std::string& to, size_t elems_per_crop) -> int {
     if (!G) return 0;
-    const hipError_t e2 = hipMemcpyAsync(GWP(to), from, elems_per_crop * n_grad * p->esz, hipMemcpyDeviceToDevice, st);
+    const hipError_t e2 = hipMemcpyAsync(GWP(to), from, elems_per_crop * n_grad * p->lay.esz, hipMemcpyDeviceToDevice, st);
     return e2 == hipSuccess ? 0 : m2t_set_hip_error(e2, __FILE__, __LINE__);
   };
   const int dt = p->dt;
@@ -344,19 +304,19 @@ static int encode_impl(m2t_swin* p, const float* src, int n_a, const float* src_
   }
   int* stage = p->pinned + (size_t)slot * 3 * p->max_images;
   memcpy(stage, crops_host, sizeof(int) * 3 * n);      // crops_host may be a temporary of the caller
-  e = hipMemcpyAsync(SWP("crops"), stage, sizeof(int) * 3 * n, hipMemcpyHostToDevice, st);
+  e = hipMemcpyAsync(WSP("crops"), stage, sizeof(int) * 3 * n, hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
   e = hipEventRecord(p->pin_ev[slot], st);
   if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
   p->pin_used[slot] = true;
-  void *X = SWP("X"), *Hn = SWP("Hn"), *QKV = SWP("QKV"), *AO = SWP("AO"), *MH = SWP("MH");
-  const float* fbias = (const float*)SWP("fbias");
-  CKS(launch_swin_patchify(dt, src, src_b, n_a, Hs, Ws, (const int*)SWP("crops"), n, SWP("A0"), st));
+  void *X = WSP("X"), *Hn = WSP("Hn"), *QKV = WSP("QKV"), *AO = WSP("AO"), *MH = WSP("MH");
+  const float* fbias = (const float*)WSP("fbias");
+  CK(launch_swin_patchify(dt, src, src_b, n_a, Hs, Ws, (const int*)WSP("crops"), n, WSP("A0"), st));
   long long M = (long long)n * 3136;
-  CKS(swin_gemm(dt, M2T_E_BIAS, SWP("A0"), 48, spk(p, workspace, "pe"), X, 96, M,
-                wt + p->poff.at("embeddings.patch_embeddings.projection.bias"), nullptr, st));
-  CKS(stash(X, "e0", 3136 * 96));
-  CKS(launch_layernorm(dt, X, wt + p->poff.at("embeddings.norm.weight"), wt + p->poff.at("embeddings.norm.bias"), X, M, 96, st));
+  CK(swin_gemm(dt, M2T_E_BIAS, WSP("A0"), 48, p->lay.packed_ptr(workspace, "pe"), X, 96, M,
+                wt + p->lay.poff.at("embeddings.patch_embeddings.projection.bias"), nullptr, st));
+  CK(stash(X, "e0", 3136 * 96));
+  CK(launch_layernorm(dt, X, wt + p->lay.poff.at("embeddings.norm.weight"), wt + p->lay.poff.at("embeddings.norm.bias"), X, M, 96, st));
   int H = 56;
   for (int s = 0; s < 4; ++s) {
     const int C = 96 << s;
@@ -365,50 +325,50 @@ static int encode_impl(m2t_swin* p, const float* src, int n_a, const float* src_
       const int shift = (j % 2 == 0 || H <= 7) ? 0 : 3;
       const std::string sb = "s" + std::to_string(s) + "b" + std::to_string(j) + ".";
       const size_t tc = (size_t)(H * H) * C;
-      CKS(stash(X, sb + "xin", tc));
-      CKS(launch_layernorm(dt, X, wt + p->poff.at(b + "layernorm_before.weight"), wt + p->poff.at(b + "layernorm_before.bias"), Hn, M, C, st));
-      CKS(swin_gemm(dt, M2T_E_BIAS, Hn, C, spk(p, workspace, b + "qkv"), QKV, 3 * C, M, fbias + p->fb.at(b + "qkv_bias"), nullptr, st));
-      CKS(stash(QKV, sb + "qkv", 3 * tc));
-      CKS(launch_swin_attn(dt, QKV, wt + p->poff.at(b + "attention.self.relative_position_bias_table"), AO, n, H, H, C, HEADS[s], shift, st));
-      CKS(swin_gemm(dt, M2T_E_BIAS_RESID, AO, C, spk(p, workspace, b + "o"), X, C, M, wt + p->poff.at(b + "attention.output.dense.bias"), X, st));
-      CKS(stash(X, sb + "xmid", tc));
+      CK(stash(X, sb + "xin", tc));
+      CK(launch_layernorm(dt, X, wt + p->lay.poff.at(b + "layernorm_before.weight"), wt + p->lay.poff.at(b + "layernorm_before.bias"), Hn, M, C, st));
+      CK(swin_gemm(dt, M2T_E_BIAS, Hn, C, p->lay.packed_ptr(workspace, b + "qkv"), QKV, 3 * C, M, fbias + p->lay.fb.at(b + "qkv_bias"), nullptr, st));
+      CK(stash(QKV, sb + "qkv", 3 * tc));
+      CK(launch_swin_attn(dt, QKV, wt + p->lay.poff.at(b + "attention.self.relative_position_bias_table"), AO, n, H, H, C, HEADS[s], shift, st));
+      CK(swin_gemm(dt, M2T_E_BIAS_RESID, AO, C, p->lay.packed_ptr(workspace, b + "o"), X, C, M, wt + p->lay.poff.at(b + "attention.output.dense.bias"), X, st));
+      CK(stash(X, sb + "xmid", tc));
       if (G) {
         // fc1 + bias + GELU storing gelu'(t) beside gelu(t) (the bias / GELU / derivative epilogue of gemm_nt with a trivial
         // 1 x 1 shuffle; fp32: the same accumulation and the same erf GELU as M2T_E_BIAS_GELU, so emb is bit-identical)
-        CKS(launch_layernorm(dt, X, wt + p->poff.at(b + "layernorm_after.weight"), wt + p->poff.at(b + "layernorm_after.bias"), Hn, M, C, st));
+        CK(launch_layernorm(dt, X, wt + p->lay.poff.at(b + "layernorm_after.weight"), wt + p->lay.poff.at(b + "layernorm_after.bias"), Hn, M, C, st));
         m2t_gemm_args ga{};
-        ga.A = Hn; ga.lda = C; ga.W = spk(p, workspace, b + "fc1"); ga.Y = MH; ga.ldy = 4 * C; ga.Y2 = GWP("MD");
-        ga.bias = wt + p->poff.at(b + "intermediate.dense.bias"); ga.M = M; ga.N = 4 * C; ga.K = C;
+        ga.A = Hn; ga.lda = C; ga.W = p->lay.packed_ptr(workspace, b + "fc1"); ga.Y = MH; ga.ldy = 4 * C; ga.Y2 = GWP("MD");
+        ga.bias = wt + p->lay.poff.at(b + "intermediate.dense.bias"); ga.M = M; ga.N = 4 * C; ga.K = C;
         ga.H = 1; ga.Wd = 1; ga.r = 1; ga.C = 4 * C;
-        CKS(launch_gemm_nt(dt, M2T_A_PLAIN, M2T_E_BIAS_SHUF, ga, st));
-        CKS(stash(GWP("MD"), sb + "gder", 4 * tc));
-        CKS(swin_gemm(dt, M2T_E_BIAS_RESID, MH, 4 * C, spk(p, workspace, b + "fc2"), X, C, M, wt + p->poff.at(b + "output.dense.bias"), X, st));
+        CK(launch_gemm_nt(dt, M2T_A_PLAIN, M2T_E_BIAS_SHUF, ga, st));
+        CK(stash(GWP("MD"), sb + "gder", 4 * tc));
+        CK(swin_gemm(dt, M2T_E_BIAS_RESID, MH, 4 * C, p->lay.packed_ptr(workspace, b + "fc2"), X, C, M, wt + p->lay.poff.at(b + "output.dense.bias"), X, st));
         continue;
       }
       if (dt != M2T_F32 && s < 2 && p->fused_mlp) {
         // LayerNorm + fc1 + GELU + fc2 + residual in one kernel: the 4C-wide hidden tensor stays in LDS
-        CKS(launch_swin_mlp_fused(X, wt + p->poff.at(b + "layernorm_after.weight"), wt + p->poff.at(b + "layernorm_after.bias"),
-                                  spk(p, workspace, b + "fc1F"), wt + p->poff.at(b + "intermediate.dense.bias"), spk(p, workspace, b + "fc2F"),
-                                  wt + p->poff.at(b + "output.dense.bias"), M, C, st));
+        CK(launch_swin_mlp_fused(X, wt + p->lay.poff.at(b + "layernorm_after.weight"), wt + p->lay.poff.at(b + "layernorm_after.bias"),
+                                  p->lay.packed_ptr(workspace, b + "fc1F"), wt + p->lay.poff.at(b + "intermediate.dense.bias"), p->lay.packed_ptr(workspace, b + "fc2F"),
+                                  wt + p->lay.poff.at(b + "output.dense.bias"), M, C, st));
         continue;
       }
-      CKS(launch_layernorm(dt, X, wt + p->poff.at(b + "layernorm_after.weight"), wt + p->poff.at(b + "layernorm_after.bias"), Hn, M, C, st));
-      CKS(swin_gemm(dt, M2T_E_BIAS_GELU, Hn, C, spk(p, workspace, b + "fc1"), MH, 4 * C, M, wt + p->poff.at(b + "intermediate.dense.bias"), nullptr, st));
-      CKS(swin_gemm(dt, M2T_E_BIAS_RESID, MH, 4 * C, spk(p, workspace, b + "fc2"), X, C, M, wt + p->poff.at(b + "output.dense.bias"), X, st));
+      CK(launch_layernorm(dt, X, wt + p->lay.poff.at(b + "layernorm_after.weight"), wt + p->lay.poff.at(b + "layernorm_after.bias"), Hn, M, C, st));
+      CK(swin_gemm(dt, M2T_E_BIAS_GELU, Hn, C, p->lay.packed_ptr(workspace, b + "fc1"), MH, 4 * C, M, wt + p->lay.poff.at(b + "intermediate.dense.bias"), nullptr, st));
+      CK(swin_gemm(dt, M2T_E_BIAS_RESID, MH, 4 * C, p->lay.packed_ptr(workspace, b + "fc2"), X, C, M, wt + p->lay.poff.at(b + "output.dense.bias"), X, st));
     }
     if (s < 3) {
       const std::string d = "encoder.layers." + std::to_string(s) + ".downsample.";
-      CKS(launch_swin_merge_gather(dt, X, Hn, n, H, H, C, st));
-      CKS(stash(Hn, "m" + std::to_string(s), (size_t)(H * H) * C));
+      CK(launch_swin_merge_gather(dt, X, Hn, n, H, H, C, st));
+      CK(stash(Hn, "m" + std::to_string(s), (size_t)(H * H) * C));
       M /= 4; H /= 2;
-      CKS(launch_layernorm(dt, Hn, wt + p->poff.at(d + "norm.weight"), wt + p->poff.at(d + "norm.bias"), Hn, M, 4 * C, st));
-      CKS(swin_gemm(dt, M2T_E_PLAIN, Hn, 4 * C, spk(p, workspace, d + "red"), X, 2 * C, M, nullptr, nullptr, st));
+      CK(launch_layernorm(dt, Hn, wt + p->lay.poff.at(d + "norm.weight"), wt + p->lay.poff.at(d + "norm.bias"), Hn, M, 4 * C, st));
+      CK(swin_gemm(dt, M2T_E_PLAIN, Hn, 4 * C, p->lay.packed_ptr(workspace, d + "red"), X, 2 * C, M, nullptr, nullptr, st));
     }
   }
-  CKS(stash(X, "xf", 49 * 768));
-  CKS(launch_layernorm(dt, X, wt + p->poff.at("layernorm.weight"), wt + p->poff.at("layernorm.bias"), Hn, M, 768, st));
-  CKS(stash(Hn, "hnf", 49 * 768));
-  CKS(launch_swin_head(dt, Hn, wt + p->poff.at("projection_head.weight"), emb, n, st));
+  CK(stash(X, "xf", 49 * 768));
+  CK(launch_layernorm(dt, X, wt + p->lay.poff.at("layernorm.weight"), wt + p->lay.poff.at("layernorm.bias"), Hn, M, 768, st));
+  CK(stash(Hn, "hnf", 49 * 768));
+  CK(launch_swin_head(dt, Hn, wt + p->lay.poff.at("projection_head.weight"), emb, n, st));
   if (G) p->grad_n = n_grad;
   return 0;
 }
@@ -434,8 +394,8 @@ extern "C" int m2t_swin_backward(m2t_swin* p, const float* g_emb, int n_grad, fl
   float *gR = (float*)GWP("gR"), *gF = (float*)GWP("gF");
   void *gT = GWP("gT"), *gC = GWP("gC"), *gQ = GWP("gQ"), *gA = GWP("gA");
   const int ng = n_grad;
-  CKS(launch_swin_head_bwd(dt, GWP("hnf"), wt + p->poff.at("projection_head.weight"), g_emb, gC, ng, st));
-  CKS(launch_layernorm_bwd(dt, GWP("xf"), gC, wt + p->poff.at("layernorm.weight"), nullptr, gR, gT, (long long)ng * 49, 768, st));
+  CK(launch_swin_head_bwd(dt, GWP("hnf"), wt + p->lay.poff.at("projection_head.weight"), g_emb, gC, ng, st));
+  CK(launch_layernorm_bwd(dt, GWP("xf"), gC, wt + p->lay.poff.at("layernorm.weight"), nullptr, gR, gT, (long long)ng * 49, 768, st));
   for (int s = 3; s >= 0; --s) {
     const int H = 56 >> s, C = 96 << s;
     const long long M = (long long)ng * H * H;
@@ -444,28 +404,28 @@ extern "C" int m2t_swin_backward(m2t_swin* p, const float* g_emb, int n_grad, fl
       const std::string sb = "s" + std::to_string(s) + "b" + std::to_string(j) + ".";
       const int shift = (j % 2 == 0 || H <= 7) ? 0 : 3;
       // MLP: d(fc1 out) = (g W2) o gelu'(t); d(LN2 out) = that W1; + LayerNorm backward into the residual stream
-      CKS(swin_gemm_g(dt, M2T_E_GELU_GRAD, gT, C, GWP(b + "fc2T"), gA, 4 * C, M, GWP(sb + "gder"), st));
-      CKS(swin_gemm_g(dt, M2T_E_PLAIN, gA, 4 * C, GWP(b + "fc1T"), gC, C, M, nullptr, st));
-      CKS(launch_layernorm_bwd(dt, GWP(sb + "xmid"), gC, wt + p->poff.at(b + "layernorm_after.weight"), gR, gR, gT, M, C, st));
+      CK(swin_gemm_g(dt, M2T_E_GELU_GRAD, gT, C, GWP(b + "fc2T"), gA, 4 * C, M, GWP(sb + "gder"), st));
+      CK(swin_gemm_g(dt, M2T_E_PLAIN, gA, 4 * C, GWP(b + "fc1T"), gC, C, M, nullptr, st));
+      CK(launch_layernorm_bwd(dt, GWP(sb + "xmid"), gC, wt + p->lay.poff.at(b + "layernorm_after.weight"), gR, gR, gT, M, C, st));
       // attention: o_proj^T, window attention, qkv^T, LayerNorm backward into the residual stream
-      CKS(swin_gemm_g(dt, M2T_E_PLAIN, gT, C, GWP(b + "oT"), gC, C, M, nullptr, st));
-      CKS(launch_swin_attn_bwd(dt, GWP(sb + "qkv"), wt + p->poff.at(b + "attention.self.relative_position_bias_table"), gC, gQ, ng, H, H, C,
+      CK(swin_gemm_g(dt, M2T_E_PLAIN, gT, C, GWP(b + "oT"), gC, C, M, nullptr, st));
+      CK(launch_swin_attn_bwd(dt, GWP(sb + "qkv"), wt + p->lay.poff.at(b + "attention.self.relative_position_bias_table"), gC, gQ, ng, H, H, C,
                                HEADS[s], shift, st));
-      CKS(swin_gemm_g(dt, M2T_E_PLAIN, gQ, 3 * C, GWP(b + "qkvT"), gC, C, M, nullptr, st));
-      CKS(launch_layernorm_bwd(dt, GWP(sb + "xin"), gC, wt + p->poff.at(b + "layernorm_before.weight"), gR, gR, gT, M, C, st));
+      CK(swin_gemm_g(dt, M2T_E_PLAIN, gQ, 3 * C, GWP(b + "qkvT"), gC, C, M, nullptr, st));
+      CK(launch_layernorm_bwd(dt, GWP(sb + "xin"), gC, wt + p->lay.poff.at(b + "layernorm_before.weight"), gR, gR, gT, M, C, st));
     }
     if (s > 0) {
       // patch merging of stage s - 1 (C' = C / 2 channels at 2H x 2H): reduction^T, LayerNorm backward (4 C'), scatter
       const std::string d = "encoder.layers." + std::to_string(s - 1) + ".downsample.";
-      CKS(swin_gemm_g(dt, M2T_E_PLAIN, gT, C, GWP(d + "redT"), gC, 2 * C, M, nullptr, st));
-      CKS(launch_layernorm_bwd(dt, GWP("m" + std::to_string(s - 1)), gC, wt + p->poff.at(d + "norm.weight"), nullptr, gF, nullptr, M, 2 * C, st));
-      CKS(launch_swin_merge_scatter(dt, gF, gR, gT, ng, 2 * H, 2 * H, C / 2, st));
+      CK(swin_gemm_g(dt, M2T_E_PLAIN, gT, C, GWP(d + "redT"), gC, 2 * C, M, nullptr, st));
+      CK(launch_layernorm_bwd(dt, GWP("m" + std::to_string(s - 1)), gC, wt + p->lay.poff.at(d + "norm.weight"), nullptr, gF, nullptr, M, 2 * C, st));
+      CK(launch_swin_merge_scatter(dt, gF, gR, gT, ng, 2 * H, 2 * H, C / 2, st));
     }
   }
   // embedding LayerNorm (its incoming gradient is the fp32 residual stream) and the patch projection^T + patchify adjoint, fp32
-  CKS(launch_layernorm_bwd(dt, GWP("e0"), nullptr, wt + p->poff.at("embeddings.norm.weight"), nullptr, gF, nullptr, (long long)ng * 3136, 96, st,
+  CK(launch_layernorm_bwd(dt, GWP("e0"), nullptr, wt + p->lay.poff.at("embeddings.norm.weight"), nullptr, gF, nullptr, (long long)ng * 3136, 96, st,
                            1e-5f, gR));
-  CKS(launch_swin_embed_bwd(gF, wt + p->poff.at("embeddings.patch_embeddings.projection.weight"), g_crops, ng, st));
+  CK(launch_swin_embed_bwd(gF, wt + p->lay.poff.at("embeddings.patch_embeddings.projection.weight"), g_crops, ng, st));
   return 0;
 }
 

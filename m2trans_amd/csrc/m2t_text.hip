@@ -9,15 +9,12 @@
 // depends only on the caption's token COUNT -- m2trans_amd/losses.py caches one embedding per count.
 // Built from the library's GEMM (bias / bias + GELU / bias + residual epilogues) and LayerNorm launchers plus three
 // small kernels here (embedding + LayerNorm, masked multi-head attention for short sequences, pooling + projection).
-#include <map>
-#include <string>
-#include <vector>
 #include "m2t_kernels.h"
+#include "m2t_layout.h"
 #include "../../include/m2t.h"
 
 namespace {
 constexpr int TX_H = 768, TX_HEADS = 12, TX_DH = 64, TX_FF = 3072, TX_LAYERS = 12, TX_VOCAB = 28996, TX_POS = 512, TX_TYPES = 2;
-struct Ws { size_t off, n; };
 
 // embeddings(input_ids, position 0..len-1, token type 0) + LayerNorm(eps 1e-12): one wave per token row
 template <typename T>
@@ -123,73 +120,57 @@ __global__ void __launch_bounds__(512) text_head_kernel(const float* __restrict_
 
 struct m2t_text {
   int max_seqs, max_len, dt;
-  size_t esz;
-  std::vector<std::string> pnames;
-  std::map<std::string, long long> poff, pnum;
-  long long nparams = 0;
-  std::map<std::string, long long> pk;     // packed (T) weight offsets in elements
-  long long npacked = 0;
-  std::map<std::string, long long> fb;     // fused fp32 qkv biases
-  long long nfb = 0;
-  std::map<std::string, Ws> ws;
-  size_t ws_bytes = 0;
+  m2t_layout lay;
   const float* weights = nullptr;
-  void add_param(const std::string& n, long long c) { pnames.push_back(n); poff[n] = nparams; pnum[n] = c; nparams += c; }
-  void add_pack(const std::string& n, long long c) { npacked = (npacked + 7) & ~7LL; pk[n] = npacked; npacked += c; }
-  void add_ws(const std::string& n, size_t elems, size_t es) {
-    ws_bytes = (ws_bytes + 255) & ~(size_t)255;
-    ws[n] = Ws{ws_bytes, elems};
-    ws_bytes += elems * es;
-  }
 };
 
 extern "C" int m2t_text_create(m2t_text** out, int max_seqs, int max_len, int dtype) {
   if (!out || max_seqs < 1 || max_len < 1 || max_len > 128 || (dtype != M2T_F32 && dtype != M2T_BF16))
     return m2t_set_error(M2T_ERR_ARG, "m2t_text_create: bad argument (1 <= max_len <= 128)");
   m2t_text* p = new m2t_text();
-  p->max_seqs = max_seqs; p->max_len = max_len; p->dt = dtype; p->esz = (dtype == M2T_F32) ? 4 : 2;
+  p->max_seqs = max_seqs; p->max_len = max_len; p->dt = dtype; p->lay.esz = (dtype == M2T_F32) ? 4 : 2;
   // parameter inventory: HF BertModel checkpoint names (transformers 4.24; `pooler.*` is not used by encode_text and is
   // not part of the buffer) + the MedCLIP text projection
-  p->add_param("embeddings.word_embeddings.weight", (long long)TX_VOCAB * TX_H);
-  p->add_param("embeddings.position_embeddings.weight", (long long)TX_POS * TX_H);
-  p->add_param("embeddings.token_type_embeddings.weight", (long long)TX_TYPES * TX_H);
-  p->add_param("embeddings.LayerNorm.weight", TX_H);
-  p->add_param("embeddings.LayerNorm.bias", TX_H);
+  p->lay.add_param("embeddings.word_embeddings.weight", (long long)TX_VOCAB * TX_H);
+  p->lay.add_param("embeddings.position_embeddings.weight", (long long)TX_POS * TX_H);
+  p->lay.add_param("embeddings.token_type_embeddings.weight", (long long)TX_TYPES * TX_H);
+  p->lay.add_param("embeddings.LayerNorm.weight", TX_H);
+  p->lay.add_param("embeddings.LayerNorm.bias", TX_H);
   for (int l = 0; l < TX_LAYERS; ++l) {
     const std::string b = "encoder.layer." + std::to_string(l) + ".";
     for (const char* nm : {"query", "key", "value"}) {
-      p->add_param(b + "attention.self." + nm + ".weight", (long long)TX_H * TX_H);
-      p->add_param(b + "attention.self." + nm + ".bias", TX_H);
+      p->lay.add_param(b + "attention.self." + nm + ".weight", (long long)TX_H * TX_H);
+      p->lay.add_param(b + "attention.self." + nm + ".bias", TX_H);
     }
-    p->add_param(b + "attention.output.dense.weight", (long long)TX_H * TX_H);
-    p->add_param(b + "attention.output.dense.bias", TX_H);
-    p->add_param(b + "attention.output.LayerNorm.weight", TX_H);
-    p->add_param(b + "attention.output.LayerNorm.bias", TX_H);
-    p->add_param(b + "intermediate.dense.weight", (long long)TX_FF * TX_H);
-    p->add_param(b + "intermediate.dense.bias", TX_FF);
-    p->add_param(b + "output.dense.weight", (long long)TX_H * TX_FF);
-    p->add_param(b + "output.dense.bias", TX_H);
-    p->add_param(b + "output.LayerNorm.weight", TX_H);
-    p->add_param(b + "output.LayerNorm.bias", TX_H);
-    p->add_pack(b + "qkv", 3LL * TX_H * TX_H);
-    p->add_pack(b + "o", (long long)TX_H * TX_H);
-    p->add_pack(b + "fc1", (long long)TX_FF * TX_H);
-    p->add_pack(b + "fc2", (long long)TX_H * TX_FF);
-    p->fb[b + "qkv_bias"] = p->nfb; p->nfb += 3 * TX_H;
+    p->lay.add_param(b + "attention.output.dense.weight", (long long)TX_H * TX_H);
+    p->lay.add_param(b + "attention.output.dense.bias", TX_H);
+    p->lay.add_param(b + "attention.output.LayerNorm.weight", TX_H);
+    p->lay.add_param(b + "attention.output.LayerNorm.bias", TX_H);
+    p->lay.add_param(b + "intermediate.dense.weight", (long long)TX_FF * TX_H);
+    p->lay.add_param(b + "intermediate.dense.bias", TX_FF);
+    p->lay.add_param(b + "output.dense.weight", (long long)TX_H * TX_FF);
+    p->lay.add_param(b + "output.dense.bias", TX_H);
+    p->lay.add_param(b + "output.LayerNorm.weight", TX_H);
+    p->lay.add_param(b + "output.LayerNorm.bias", TX_H);
+    p->lay.add_pack(b + "qkv", 3LL * TX_H * TX_H);
+    p->lay.add_pack(b + "o", (long long)TX_H * TX_H);
+    p->lay.add_pack(b + "fc1", (long long)TX_FF * TX_H);
+    p->lay.add_pack(b + "fc2", (long long)TX_H * TX_FF);
+    p->lay.add_fb(b + "qkv_bias", 3 * TX_H);
   }
-  p->add_param("projection_head.weight", 512LL * TX_H);
-  const size_t rows = (size_t)max_seqs * max_len, es = p->esz;
-  p->add_ws("packed", (size_t)p->npacked, es);
-  p->add_ws("fbias", (size_t)p->nfb, 4);
-  p->add_ws("ids", rows, 4);
-  p->add_ws("mask", rows, 4);
-  p->add_ws("X", rows * TX_H, es);
-  p->add_ws("Y", rows * TX_H, es);
-  p->add_ws("QKV", rows * 3 * TX_H, es);
-  p->add_ws("AO", rows * TX_H, es);
-  p->add_ws("MH", rows * TX_FF, es);
-  p->add_ws("pooled", (size_t)max_seqs * TX_H, 4);
-  p->ws_bytes = (p->ws_bytes + 255) & ~(size_t)255;
+  p->lay.add_param("projection_head.weight", 512LL * TX_H);
+  const size_t rows = (size_t)max_seqs * max_len, es = p->lay.esz;
+  p->lay.ws.add("packed", (size_t)p->lay.npacked, es);
+  p->lay.ws.add("fbias", (size_t)p->lay.nfb, 4);
+  p->lay.ws.add("ids", rows, 4);
+  p->lay.ws.add("mask", rows, 4);
+  p->lay.ws.add("X", rows * TX_H, es);
+  p->lay.ws.add("Y", rows * TX_H, es);
+  p->lay.ws.add("QKV", rows * 3 * TX_H, es);
+  p->lay.ws.add("AO", rows * TX_H, es);
+  p->lay.ws.add("MH", rows * TX_FF, es);
+  p->lay.ws.add("pooled", (size_t)max_seqs * TX_H, 4);
+  p->lay.ws.seal();
   *out = p;
   return 0;
 }
@@ -197,24 +178,12 @@ extern "C" void m2t_text_destroy(m2t_text* p) { delete p; }
 extern "C" long long m2t_text_query(const m2t_text* p, const char* key) {
   if (!p || !key) return -1;
   const std::string k(key);
-  if (k == "workspace_bytes") return (long long)p->ws_bytes;
-  if (k == "num_params") return p->nparams;
-  if (k == "num_param_tensors") return (long long)p->pnames.size();
   if (k == "max_seqs") return p->max_seqs;
   if (k == "max_len") return p->max_len;
-  if (k.rfind("param:", 0) == 0) { auto it = p->poff.find(k.substr(6)); return it == p->poff.end() ? -1 : it->second; }
-  if (k.rfind("numel:", 0) == 0) { auto it = p->pnum.find(k.substr(6)); return it == p->pnum.end() ? -1 : it->second; }
-  return -1;
+  return p->lay.query(k, 0);      // (no ws: / wsn: / packed: keys on this handle)
 }
 extern "C" const char* m2t_text_param_name(const m2t_text* p, int i) {
-  if (!p || i < 0 || i >= (int)p->pnames.size()) return nullptr;
-  return p->pnames[i].c_str();
-}
-
-#define TXP(name) ((char*)workspace + p->ws.at(name).off)
-#define CKX(call) do { int rc__ = (call); if (rc__) return rc__; } while (0)
-static inline char* tpk(const m2t_text* p, void* workspace, const std::string& k) {
-  return (char*)workspace + p->ws.at("packed").off + p->pk.at(k) * p->esz;
+  return p ? p->lay.param_name(i) : nullptr;
 }
 
 // once per weight set: the frozen fp32 weights -> element type T, q | k | v fused into one [2304][768] matrix per layer
@@ -223,19 +192,19 @@ extern "C" int m2t_text_load_weights(m2t_text* p, const float* weights, void* wo
   hipStream_t st = (hipStream_t)stream;
   const int dt = p->dt;
   p->weights = weights;
-  float* fbias = (float*)TXP("fbias");
+  float* fbias = (float*)WSP("fbias");
   for (int l = 0; l < TX_LAYERS; ++l) {
     const std::string b = "encoder.layer." + std::to_string(l) + ".";
     int part = 0;
     for (const char* nm : {"query", "key", "value"}) {
-      CKX(launch_convert(dt, weights + p->poff.at(b + "attention.self." + nm + ".weight"),
-                         tpk(p, workspace, b + "qkv") + (size_t)part * TX_H * TX_H * p->esz, (long long)TX_H * TX_H, st));
-      CKX(launch_convert(M2T_F32, weights + p->poff.at(b + "attention.self." + nm + ".bias"), fbias + p->fb.at(b + "qkv_bias") + part * TX_H, TX_H, st));
+      CK(launch_convert(dt, weights + p->lay.poff.at(b + "attention.self." + nm + ".weight"),
+                         p->lay.packed_ptr(workspace, b + "qkv") + (size_t)part * TX_H * TX_H * p->lay.esz, (long long)TX_H * TX_H, st));
+      CK(launch_convert(M2T_F32, weights + p->lay.poff.at(b + "attention.self." + nm + ".bias"), fbias + p->lay.fb.at(b + "qkv_bias") + part * TX_H, TX_H, st));
       ++part;
     }
-    CKX(launch_convert(dt, weights + p->poff.at(b + "attention.output.dense.weight"), tpk(p, workspace, b + "o"), (long long)TX_H * TX_H, st));
-    CKX(launch_convert(dt, weights + p->poff.at(b + "intermediate.dense.weight"), tpk(p, workspace, b + "fc1"), (long long)TX_FF * TX_H, st));
-    CKX(launch_convert(dt, weights + p->poff.at(b + "output.dense.weight"), tpk(p, workspace, b + "fc2"), (long long)TX_H * TX_FF, st));
+    CK(launch_convert(dt, weights + p->lay.poff.at(b + "attention.output.dense.weight"), p->lay.packed_ptr(workspace, b + "o"), (long long)TX_H * TX_H, st));
+    CK(launch_convert(dt, weights + p->lay.poff.at(b + "intermediate.dense.weight"), p->lay.packed_ptr(workspace, b + "fc1"), (long long)TX_FF * TX_H, st));
+    CK(launch_convert(dt, weights + p->lay.poff.at(b + "output.dense.weight"), p->lay.packed_ptr(workspace, b + "fc2"), (long long)TX_H * TX_FF, st));
   }
   return 0;
 }
@@ -260,15 +229,15 @@ extern "C" int m2t_text_encode(m2t_text* p, const int* ids_host, const int* mask
   const int dt = p->dt;
   const float* wt = p->weights;
   const int rows = n * len;
-  hipError_t e = hipMemcpyAsync(TXP("ids"), ids_host, sizeof(int) * rows, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(TXP("mask"), mask_host, sizeof(int) * rows, hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(WSP("ids"), ids_host, sizeof(int) * rows, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(WSP("mask"), mask_host, sizeof(int) * rows, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);       // the host arrays may be temporaries
   if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
-  void *X = TXP("X"), *Y = TXP("Y"), *QKV = TXP("QKV"), *AO = TXP("AO"), *MH = TXP("MH");
-  float* pooled = (float*)TXP("pooled");
-  const float* fbias = (const float*)TXP("fbias");
-  const int* ids = (const int*)TXP("ids");
-  const int* mask = (const int*)TXP("mask");
+  void *X = WSP("X"), *Y = WSP("Y"), *QKV = WSP("QKV"), *AO = WSP("AO"), *MH = WSP("MH");
+  float* pooled = (float*)WSP("pooled");
+  const float* fbias = (const float*)WSP("fbias");
+  const int* ids = (const int*)WSP("ids");
+  const int* mask = (const int*)WSP("mask");
 #define TX_LAUNCH(kern, grid, block, ...)                                                                 \
   do {                                                                                                    \
     if (dt == M2T_F32) hipLaunchKernelGGL(kern<float>, grid, block, 0, st, __VA_ARGS__);                  \
@@ -276,26 +245,26 @@ extern "C" int m2t_text_encode(m2t_text* p, const int* ids_host, const int* mask
     M2T_LAUNCH_CHECK();                                                                                   \
   } while (0)
   if (dt == M2T_F32)
-    hipLaunchKernelGGL(text_embed_kernel<float>, dim3((rows + 3) / 4), dim3(256), 0, st, ids, wt + p->poff.at("embeddings.word_embeddings.weight"),
-                       wt + p->poff.at("embeddings.position_embeddings.weight"), wt + p->poff.at("embeddings.token_type_embeddings.weight"),
-                       wt + p->poff.at("embeddings.LayerNorm.weight"), wt + p->poff.at("embeddings.LayerNorm.bias"), (float*)X, rows, len);
+    hipLaunchKernelGGL(text_embed_kernel<float>, dim3((rows + 3) / 4), dim3(256), 0, st, ids, wt + p->lay.poff.at("embeddings.word_embeddings.weight"),
+                       wt + p->lay.poff.at("embeddings.position_embeddings.weight"), wt + p->lay.poff.at("embeddings.token_type_embeddings.weight"),
+                       wt + p->lay.poff.at("embeddings.LayerNorm.weight"), wt + p->lay.poff.at("embeddings.LayerNorm.bias"), (float*)X, rows, len);
   else
-    hipLaunchKernelGGL(text_embed_kernel<bf16_t>, dim3((rows + 3) / 4), dim3(256), 0, st, ids, wt + p->poff.at("embeddings.word_embeddings.weight"),
-                       wt + p->poff.at("embeddings.position_embeddings.weight"), wt + p->poff.at("embeddings.token_type_embeddings.weight"),
-                       wt + p->poff.at("embeddings.LayerNorm.weight"), wt + p->poff.at("embeddings.LayerNorm.bias"), (bf16_t*)X, rows, len);
+    hipLaunchKernelGGL(text_embed_kernel<bf16_t>, dim3((rows + 3) / 4), dim3(256), 0, st, ids, wt + p->lay.poff.at("embeddings.word_embeddings.weight"),
+                       wt + p->lay.poff.at("embeddings.position_embeddings.weight"), wt + p->lay.poff.at("embeddings.token_type_embeddings.weight"),
+                       wt + p->lay.poff.at("embeddings.LayerNorm.weight"), wt + p->lay.poff.at("embeddings.LayerNorm.bias"), (bf16_t*)X, rows, len);
   M2T_LAUNCH_CHECK();
   for (int l = 0; l < TX_LAYERS; ++l) {
     const std::string b = "encoder.layer." + std::to_string(l) + ".";
-    CKX(text_gemm(dt, M2T_E_BIAS, X, TX_H, tpk(p, workspace, b + "qkv"), QKV, 3 * TX_H, rows, fbias + p->fb.at(b + "qkv_bias"), nullptr, st));
+    CK(text_gemm(dt, M2T_E_BIAS, X, TX_H, p->lay.packed_ptr(workspace, b + "qkv"), QKV, 3 * TX_H, rows, fbias + p->lay.fb.at(b + "qkv_bias"), nullptr, st));
     if (dt == M2T_F32) hipLaunchKernelGGL(text_attn_kernel<float>, dim3(n * TX_HEADS), dim3(256), 0, st, (const float*)QKV, mask, (float*)AO, len);
     else hipLaunchKernelGGL(text_attn_kernel<bf16_t>, dim3(n * TX_HEADS), dim3(256), 0, st, (const bf16_t*)QKV, mask, (bf16_t*)AO, len);
     M2T_LAUNCH_CHECK();
     // BertSelfOutput: LayerNorm(dense(attention) + hidden); BertOutput: LayerNorm(dense(gelu(dense(h))) + h)
-    CKX(text_gemm(dt, M2T_E_BIAS_RESID, AO, TX_H, tpk(p, workspace, b + "o"), Y, TX_H, rows, wt + p->poff.at(b + "attention.output.dense.bias"), X, st));
-    CKX(launch_layernorm(dt, Y, wt + p->poff.at(b + "attention.output.LayerNorm.weight"), wt + p->poff.at(b + "attention.output.LayerNorm.bias"), X, rows, TX_H, st, 1e-12f));
-    CKX(text_gemm(dt, M2T_E_BIAS_GELU, X, TX_H, tpk(p, workspace, b + "fc1"), MH, TX_FF, rows, wt + p->poff.at(b + "intermediate.dense.bias"), nullptr, st));
-    CKX(text_gemm(dt, M2T_E_BIAS_RESID, MH, TX_FF, tpk(p, workspace, b + "fc2"), Y, TX_H, rows, wt + p->poff.at(b + "output.dense.bias"), X, st));
-    CKX(launch_layernorm(dt, Y, wt + p->poff.at(b + "output.LayerNorm.weight"), wt + p->poff.at(b + "output.LayerNorm.bias"), X, rows, TX_H, st, 1e-12f));
+    CK(text_gemm(dt, M2T_E_BIAS_RESID, AO, TX_H, p->lay.packed_ptr(workspace, b + "o"), Y, TX_H, rows, wt + p->lay.poff.at(b + "attention.output.dense.bias"), X, st));
+    CK(launch_layernorm(dt, Y, wt + p->lay.poff.at(b + "attention.output.LayerNorm.weight"), wt + p->lay.poff.at(b + "attention.output.LayerNorm.bias"), X, rows, TX_H, st, 1e-12f));
+    CK(text_gemm(dt, M2T_E_BIAS_GELU, X, TX_H, p->lay.packed_ptr(workspace, b + "fc1"), MH, TX_FF, rows, wt + p->lay.poff.at(b + "intermediate.dense.bias"), nullptr, st));
+    CK(text_gemm(dt, M2T_E_BIAS_RESID, MH, TX_FF, p->lay.packed_ptr(workspace, b + "fc2"), Y, TX_H, rows, wt + p->lay.poff.at(b + "output.dense.bias"), X, st));
+    CK(launch_layernorm(dt, Y, wt + p->lay.poff.at(b + "output.LayerNorm.weight"), wt + p->lay.poff.at(b + "output.LayerNorm.bias"), X, rows, TX_H, st, 1e-12f));
     // hidden_states[l + 1] = X: the package pools hidden states 1, 2 and -1
     if (l == 0 || l == 1 || l == TX_LAYERS - 1) {
       if (dt == M2T_F32) hipLaunchKernelGGL(text_pool_kernel<float>, dim3(n), dim3(256), 0, st, (const float*)X, pooled, len, l == 0 ? 0 : 1);
@@ -303,7 +272,7 @@ extern "C" int m2t_text_encode(m2t_text* p, const int* ids_host, const int* mask
       M2T_LAUNCH_CHECK();
     }
   }
-  hipLaunchKernelGGL(text_head_kernel, dim3(n), dim3(512), 0, st, pooled, wt + p->poff.at("projection_head.weight"), emb);
+  hipLaunchKernelGGL(text_head_kernel, dim3(n), dim3(512), 0, st, pooled, wt + p->lay.poff.at("projection_head.weight"), emb);
   M2T_LAUNCH_CHECK();
   return 0;
 }
