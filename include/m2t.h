@@ -160,12 +160,31 @@ int m2t_l1_loss(m2t_plan* p, const float* hr, float lambda_l1, double divisor, f
  * from m2t_l1_loss's by the order of an fp32 sum.  A later m2t_l1_loss / m2t_set_output_grad / m2t_forward cancels it. */
 int m2t_l1_loss_deferred(m2t_plan* p, const float* hr, float lambda_l1, double divisor, float rgb_range,
                          float* loss_out, void* workspace, void* stream);
+/* The pixel-loss family: weight * mean(rho(clamp(sr) - hr)) + the backward seed, for the criteria the reference offers next to L1
+ * (losses.py:225-230: l1 / sl1 = nn.SmoothL1Loss / l2 = nn.MSELoss; losses.py:287-297: L1_Charbonnier_loss, eps added under the
+ * root as in :295).  With d = clamp(sr) - hr, in fp32:
+ *   M2T_LOSS_L1           |d|                                               seed factor sign(d) (0 at d = 0)      param unused
+ *   M2T_LOSS_MSE          d^2                                               2 d                                   param unused
+ *   M2T_LOSS_CHARBONNIER  sqrt(d^2 + eps)                                   d / sqrt(d^2 + eps)                   param = eps  (1e-6 in the reference)
+ *   M2T_LOSS_SMOOTH_L1    |d| < beta ? d^2 / (2 beta) : |d| - beta / 2      |d| < beta ? d / beta : sign(d)       param = beta (1.0 in torch)
+ * seed = factor * (float)(weight / divisor) where 0 <= pre-clamp output <= rgb_range inside the image, 0 elsewhere.
+ * m2t_pixel_loss is m2t_l1_loss, m2t_pixel_loss_deferred is m2t_l1_loss_deferred with the kind chosen: the same state rules, the same
+ * launches, the same schedule ("fused_l1" takes EVERY kind inside the fused tail backward on the bf16 x4 path; on every other path
+ * m2t_backward runs m2t_pixel_loss's kernel first), and a later loss / m2t_set_output_grad / m2t_forward cancels a deferred request.
+ * kind = M2T_LOSS_L1 is m2t_l1_loss / m2t_l1_loss_deferred, bit for bit.  m2t_add_output_grad works on the seed of any kind.
+ * M2T_ERR_ARG: an unknown kind; eps / beta not finite or not > 0 (beta = 0 is the L1 loss: ask for M2T_LOSS_L1).
+ * M2T_ERR_STATE: no forward with saved activations. */
+enum m2t_pixel_loss_kind { M2T_LOSS_L1 = 0, M2T_LOSS_MSE = 1, M2T_LOSS_CHARBONNIER = 2, M2T_LOSS_SMOOTH_L1 = 3 };
+int m2t_pixel_loss(m2t_plan* p, int kind, float param, const float* hr, float weight, double divisor, float rgb_range,
+                   float* loss_out, void* workspace, void* stream);
+int m2t_pixel_loss_deferred(m2t_plan* p, int kind, float param, const float* hr, float weight, double divisor, float rgb_range,
+                            float* loss_out, void* workspace, void* stream);
 /* alternative seed: an arbitrary upstream gradient g_sr [B,3,H0*s,W0*s] (torch autograd). */
 int m2t_set_output_grad(m2t_plan* p, const float* g_sr, float rgb_range, void* workspace, void* stream);
-/* adds scale * g into the seed already materialised by m2t_l1_loss or m2t_set_output_grad (the opt-in differentiable
+/* adds scale * g into the seed already materialised by m2t_l1_loss / m2t_pixel_loss or m2t_set_output_grad (the opt-in differentiable
  * SemanticLoss): g [B,3,gh,gw] float32; sample b's block lands at crops_host int[B][2] = (row0, col0) of the SR image, or at
  * (0, 0) for every sample when crops_host is NULL; the same clamp mask and padded layout as m2t_set_output_grad.
- * M2T_ERR_STATE without a seed or after m2t_l1_loss_deferred (no materialised seed); M2T_ERR_ARG for a block outside the image. */
+ * M2T_ERR_STATE without a seed or after m2t_l1_loss_deferred / m2t_pixel_loss_deferred (no materialised seed); M2T_ERR_ARG for a block outside the image. */
 int m2t_add_output_grad(m2t_plan* p, const float* g, int gh, int gw, const int* crops_host, float scale, float rgb_range,
                         void* workspace, void* stream);
 /* loss.backward() (train.py:209) restricted to the model: fills grads (flat, same layout as

@@ -28,6 +28,8 @@ SIGNATURES = {
     "m2t_forward": (_i, [_vp, _vp, _vp, _vp, _f, _i, _vp, _vp]),
     "m2t_l1_loss": (_i, [_vp, _vp, _f, _d, _f, _vp, _vp, _vp]),
     "m2t_l1_loss_deferred": (_i, [_vp, _vp, _f, _d, _f, _vp, _vp, _vp]),
+    "m2t_pixel_loss": (_i, [_vp, _i, _f, _vp, _f, _d, _f, _vp, _vp, _vp]),
+    "m2t_pixel_loss_deferred": (_i, [_vp, _i, _f, _vp, _f, _d, _f, _vp, _vp, _vp]),
     "m2t_set_output_grad": (_i, [_vp, _vp, _f, _vp, _vp]),
     "m2t_add_output_grad": (_i, [_vp, _vp, _i, _i, C.POINTER(_i), _f, _f, _vp, _vp]),
     "m2t_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),

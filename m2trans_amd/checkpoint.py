@@ -22,6 +22,10 @@ the decay in torch's own ``param_groups`` (``weight_decay``, ``decoupled_weight_
 ``step`` (optimizer steps that skip_nonfinite left out never happened), ``ema_state_dict`` (``module.``-prefixed, loadable
 strictly) and ``m2t_optim`` = {max_grad_norm, ema_decay, skip_nonfinite, skipped_steps}.  With every option off it is the dict
 above, key for key.
+
+With a pixel loss other than L1 (TrainStep(pixel_loss=...)) the dict carries ``m2t_loss`` = {"pixel_loss": name, "param": eps /
+beta / None}; ``import_checkpoint`` sets the TrainStep's loss from it and leaves the loss alone when the file has no such entry.
+An L1 run writes no entry: its dict is the one above.
 """
 from __future__ import annotations
 
@@ -51,6 +55,15 @@ def _optim_options(train_step) -> dict:
             "decoupled_weight_decay": bool(getattr(train_step, "decoupled_weight_decay", False)),
             "ema_decay": getattr(train_step, "ema_decay", None),
             "skip_nonfinite": bool(getattr(train_step, "skip_nonfinite", False))}
+
+
+def _pixel_loss(train_step):
+    """The ``m2t_loss`` entry of a step object, or None for L1 (and for an object that knows no pixel losses)."""
+    from .train_step import resolve_pixel_loss
+    _, canon, value = resolve_pixel_loss(getattr(train_step, "pixel_loss", "l1"), getattr(train_step, "pixel_loss_param", None))
+    if canon == "l1":
+        return None
+    return {"pixel_loss": canon, "param": value}
 
 
 def _skipped(train_step) -> int:
@@ -123,6 +136,8 @@ def export_checkpoint(model, train_step=None, epoch: int = 1, stat_dict: Optiona
             out["ema_state_dict"] = {"module." + k: v.cpu() for k, v in ema_state_dict(model, train_step.ema_params).items()}
         out["m2t_optim"] = {"max_grad_norm": oo["max_grad_norm"], "ema_decay": oo["ema_decay"],
                             "skip_nonfinite": oo["skip_nonfinite"], "skipped_steps": skipped}
+    if train_step is not None and _pixel_loss(train_step) is not None:
+        out["m2t_loss"] = _pixel_loss(train_step)
     return out
 
 
@@ -135,6 +150,14 @@ def import_checkpoint(ckpt: dict, model, train_step=None) -> int:
     model.load_state_dict(ckpt["model_state_dict"], strict=True)
     if train_step is None:
         return int(ckpt.get("epoch", 0)) + 1
+    ml = ckpt.get("m2t_loss")
+    if ml is not None:
+        # the pixel loss the run was saved with (a file without the entry leaves the TrainStep's own untouched)
+        if hasattr(train_step, "set_pixel_loss"):
+            train_step.set_pixel_loss(ml["pixel_loss"], ml.get("param"))
+        else:
+            from .train_step import resolve_pixel_loss
+            _, train_step.pixel_loss, train_step.pixel_loss_param = resolve_pixel_loss(ml["pixel_loss"], ml.get("param"))
     opt = ckpt.get("optimizer_state_dict") or {}
     sch = ckpt.get("scheduler_state_dict")
     if not opt.get("state") and not opt.get("param_groups") and sch is None:

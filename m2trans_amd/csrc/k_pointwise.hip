@@ -1076,11 +1076,14 @@ int launch_multi_reduce(const float* arena, float* grads, const m2t_red_desc* de
 //   sr   [B][3][Hs][Ws] fp32  = clamp(pre, 0, R) cropped
 //   loss partial sums of |sr - hr|  -> part[blocks]  (sum finished by loss_finish)
 //   gpre [B][3][Hp][Wp] fp32  = scale * sign(sr - hr) * [0 <= pre <= R] inside the crop, 0 outside
+// KIND: the other pixel losses of the reference (losses.py:225-230 l2 / sl1, :287-297 Charbonnier) through the one per-pixel
+// function of m2t_pixel_loss.h, which the fused tail backward (k_tail_bwd.hip) calls too; KIND = l1 is the code above, bit for bit
 // =======================================================================================
+template <int KIND>
 __global__ void __launch_bounds__(256) clamp_l1_kernel(const float* __restrict__ pre, const float* __restrict__ hr,
                                                        float* __restrict__ sr, float* __restrict__ gpre,
                                                        float* __restrict__ part, int B, int Hp, int Wp, int Hs, int Ws,
-                                                       float R, float gscale) {
+                                                       float R, float gscale, float lparam, float lf0, float lf1) {
   const long long total = (long long)B * 3 * Hp * Wp;
   float acc = 0.f;
   for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < total;
@@ -1097,8 +1100,9 @@ __global__ void __launch_bounds__(256) clamp_l1_kernel(const float* __restrict__
       if (sr) sr[o] = c;
       if (hr) {
         const float d = c - hr[o];
-        acc += fabsf(d);
-        const float sg = (d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f);
+        float term;
+        const float sg = m2t_pixel_loss_eval(KIND, d, lparam, lf0, lf1, term);
+        acc += term;
         g = (v >= 0.f && v <= R) ? sg * gscale : 0.f;
       }
     }
@@ -1112,10 +1116,11 @@ __global__ void __launch_bounds__(256) clamp_l1_kernel(const float* __restrict__
 }
 // four consecutive x per thread (Wp, Ws multiples of 4): 16-byte accesses and one index decomposition per quad -- the
 // scalar kernel above is bound by memory instructions and 64-bit divisions (64 us for 150 MB)
+template <int KIND>
 __global__ void __launch_bounds__(256) clamp_l1_vec4_kernel(const float* __restrict__ pre, const float* __restrict__ hr,
                                                             float* __restrict__ sr, float* __restrict__ gpre,
                                                             float* __restrict__ part, int B, int Hp, int Wp, int Hs, int Ws,
-                                                            float R, float gscale) {
+                                                            float R, float gscale, float lparam, float lf0, float lf1) {
   const int wq = Wp >> 2;
   const long long total = (long long)B * 3 * Hp * wq;
   float acc = 0.f;
@@ -1137,8 +1142,9 @@ __global__ void __launch_bounds__(256) clamp_l1_vec4_kernel(const float* __restr
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const float d = c[i] - hv[i];
-          acc += fabsf(d);
-          const float sg = (d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f);
+          float term;
+          const float sg = m2t_pixel_loss_eval(KIND, d, lparam, lf0, lf1, term);
+          acc += term;
           g[i] = (v[i] >= 0.f && v[i] <= R) ? sg * gscale : 0.f;
         }
       }
@@ -1164,12 +1170,26 @@ __global__ void loss_finish_kernel(const float* __restrict__ part, int n, float 
   }
   if (threadIdx.x == 0) loss[0] = sh[0] * scale;
 }
+template <int KIND>
+static void clamp_l1_go(bool vec, int g, hipStream_t st, const float* pre, const float* hr, float* sr, float* gpre, float* part, int B, int Hp,
+                        int Wp, int Hs, int Ws, float R, float gscale, float lparam, float lf0, float lf1) {
+  if (vec) hipLaunchKernelGGL(clamp_l1_vec4_kernel<KIND>, dim3(g), dim3(256), 0, st, pre, hr, sr, gpre, part, B, Hp, Wp, Hs, Ws, R, gscale, lparam, lf0, lf1);
+  else hipLaunchKernelGGL(clamp_l1_kernel<KIND>, dim3(g), dim3(256), 0, st, pre, hr, sr, gpre, part, B, Hp, Wp, Hs, Ws, R, gscale, lparam, lf0, lf1);
+}
 int launch_clamp_l1(const float* pre, const float* hr, float* sr, float* gpre, float* part, float* loss, int B, int Hp,
-                    int Wp, int Hs, int Ws, float R, float loss_scale, float gscale, hipStream_t st) {
+                    int Wp, int Hs, int Ws, float R, float loss_scale, float gscale, hipStream_t st, int loss_kind, float lparam,
+                    float lf0, float lf1) {
   const bool vec = (Wp % 4 == 0) && (Ws % 4 == 0) && ((long long)B * 3 * Hp < (1LL << 31));
   const int g = std::min(M2T_LOSS_BLOCKS, grid_for((long long)B * 3 * Hp * Wp / (vec ? 4 : 1)));
-  if (vec) hipLaunchKernelGGL(clamp_l1_vec4_kernel, dim3(g), dim3(256), 0, st, pre, hr, sr, gpre, part, B, Hp, Wp, Hs, Ws, R, gscale);
-  else hipLaunchKernelGGL(clamp_l1_kernel, dim3(g), dim3(256), 0, st, pre, hr, sr, gpre, part, B, Hp, Wp, Hs, Ws, R, gscale);
+#define CL_GO(K_) clamp_l1_go<K_>(vec, g, st, pre, hr, sr, gpre, part, B, Hp, Wp, Hs, Ws, R, gscale, lparam, lf0, lf1)
+  switch (loss_kind) {
+    case M2T_PL_L1: CL_GO(M2T_PL_L1); break;
+    case M2T_PL_MSE: CL_GO(M2T_PL_MSE); break;
+    case M2T_PL_CHARBONNIER: CL_GO(M2T_PL_CHARBONNIER); break;
+    case M2T_PL_SMOOTH_L1: CL_GO(M2T_PL_SMOOTH_L1); break;
+    default: return m2t_set_error(-2, "clamp_l1: unknown pixel-loss kind");
+  }
+#undef CL_GO
   M2T_LAUNCH_CHECK();
   if (loss) {
     hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, st, part, g, loss_scale, loss);

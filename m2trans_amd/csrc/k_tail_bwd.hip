@@ -56,6 +56,8 @@ struct TailBwdArgs {
   float* loss_part;       // [nblk]
   int Hs, Ws;
   float R, gscale;
+  // the loss kind's parameters (m2t_pixel_loss.h; the kind itself is a template constant of the kernels): l1 reads none of them
+  float lparam, lf0, lf1;
 };
 
 __device__ __forceinline__ Frag8<bf16_t> tr_rows(const bf16_t* lo, const bf16_t* hi) {
@@ -75,9 +77,11 @@ __device__ __forceinline__ int hr_row(int m, int sub) { return (2 * (m >> 3) + (
 // the two erf-based functions 32 elements per thread.  Same operand fragments, k order, bias add and gelu_erf_both as
 // tail_expand_kernel (k_gemm.hip), so the recomputed values are the bits the forward would have stored.  gelu'(t2) is
 // written where g(t2) goes (the product is formed in place), so the LDS footprint does not grow.
-template <bool RC, bool L1 = false>
+// LK: the pixel-loss kind taken inside (M2TPixelLossKind), -1: none (g(sr) is read from gout)
+template <bool RC, int LK = -1>
 __global__ void __launch_bounds__(512) tail_bwd_fused_kernel(TailBwdArgs a) {
   using T = bf16_t;
+  constexpr bool L1 = LK >= 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float(*Gs)[TB_HP] = reinterpret_cast<float(*)[TB_HP]>(smem);                 // [3][324] g(sr) halo (0 outside the image)
   size_t off = sizeof(float) * 3 * TB_HP;
@@ -224,9 +228,10 @@ __global__ void __launch_bounds__(512) tail_bwd_fused_kernel(TailBwdArgs a) {
             const float v = rg[it];
             const float c = fminf(fmaxf(v, 0.f), a.R);
             const float d = c - rh[it];
-            const float sg = (d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f);
+            float term;
+            const float sg = m2t_pixel_loss_eval(LK, d, a.lparam, a.lf0, a.lf1, term);
             gv = (v >= 0.f && v <= a.R) ? sg * a.gscale : 0.f;
-            if (py >= 1 && py <= TB_T && px >= 1 && px <= TB_T) l1acc += fabsf(d);     // the tile's OWN pixels: each pixel of the image once
+            if (py >= 1 && py <= TB_T && px >= 1 && px <= TB_T) l1acc += term;         // the tile's OWN pixels: each pixel of the image once
           }
           Gs[i / TB_HP][p] = gv;
         } else {
@@ -564,9 +569,10 @@ __device__ __forceinline__ constexpr int acc32_row(int t) { return (t & 3) + 8 *
 #define T32_KO 0                                 // scratch/bench_tail_bwd16.hip: knock-out experiments (results WRONG): 1 D loads, 2 D stores,
 #endif                                           // 4 W loads, 8 GELU, 16 R stores, 32 Geff gather, 64 F loads
 
-template <bool L1>
+template <int LK>
 __global__ void __launch_bounds__(512) tail_bwd32_kernel(TailBwdArgs a) {
   using T = bf16_t;
+  constexpr bool L1 = LK >= 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float(*Gs2)[3][TB_HP] = reinterpret_cast<float(*)[3][TB_HP]>(smem);          // 2 x [3][324] g(sr) halo, raster (0 outside the image)
   size_t off = sizeof(float) * 2 * 3 * TB_HP;
@@ -714,9 +720,10 @@ __global__ void __launch_bounds__(512) tail_bwd32_kernel(TailBwdArgs a) {
                 const float v = rg[it];
                 const float c = fminf(fmaxf(v, 0.f), a.R);
                 const float d = c - rh[it];
-                const float sg = (d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f);
+                float term;
+                const float sg = m2t_pixel_loss_eval(LK, d, a.lparam, a.lf0, a.lf1, term);
                 gv = (v >= 0.f && v <= a.R) ? sg * a.gscale : 0.f;
-                if (py >= 1 && py <= TB_T && px >= 1 && px <= TB_T) l1acc += fabsf(d);     // the tile's OWN pixels: each pixel of the image once
+                if (py >= 1 && py <= TB_T && px >= 1 && px <= TB_T) l1acc += term;         // the tile's OWN pixels: each pixel of the image once
               }
               Gs[i / TB_HP][p] = gv;
             } else {
@@ -954,7 +961,7 @@ int tail_bwd_fused_blocks(int B, int H, int W) {
 int launch_tail_bwd_fused(const float* gout, const float* wf, const void* act, const void* der, const void* a1, const void* d1,
                           const void* w3t, const float* b3, void* gt1, float* slab_wf, float* slab_w3, float* slab_b3, int* nslab_out,
                           int B, int H, int W, hipStream_t st, const float* l1_pre, const float* l1_hr, float* l1_part, int Hs, int Ws,
-                          float R, float gscale, int variant) {
+                          float R, float gscale, int variant, int loss_kind, float lparam, float lf0, float lf1) {
   // act == nullptr: the forward did not store gelu(t2) / gelu'(t2); they are recomputed per tile from a1, w3t and b3
   // l1_pre != nullptr: the clamp + L1 seed is taken inside (gout unused); l1_part [tail_bwd_fused_blocks] receives the loss partials
   if (H % 32 || W % 32) return m2t_set_error(-2, "tail_bwd_fused: H, W must be multiples of 32");
@@ -963,8 +970,9 @@ int launch_tail_bwd_fused(const float* gout, const float* wf, const void* act, c
   const int nblk = tail_bwd_fused_blocks(B, H, W);
   const size_t sh = tail_bwd_smem();
   TailBwdArgs a{gout, wf, (const bf16_t*)act, (const bf16_t*)der, (const bf16_t*)a1, (const bf16_t*)d1, (const bf16_t*)w3t, b3,
-                (bf16_t*)gt1, slab_wf, slab_w3, slab_b3, B, H, W, l1_pre, l1_hr, l1_part, Hs, Ws, R, gscale};
+                (bf16_t*)gt1, slab_wf, slab_w3, slab_b3, B, H, W, l1_pre, l1_hr, l1_part, Hs, Ws, R, gscale, lparam, lf0, lf1};
   if (l1_pre && (!l1_hr || !l1_part || act != nullptr)) return m2t_set_error(-2, "tail_bwd_fused: the fused L1 seed needs hr, the partial buffer and the recomputing variant");
+  if (l1_pre && (loss_kind < 0 || loss_kind >= M2T_PL_KINDS)) return m2t_set_error(-2, "tail_bwd_fused: unknown pixel-loss kind");
 #define TB_GO(RC_, L1_)                                                                                                    \
   do {                                                                                                                      \
     if (int rc__ = m2t_ensure_dynamic_lds((const void*)tail_bwd_fused_kernel<RC_, L1_>, (int)sh)) return rc__;               \
@@ -977,10 +985,28 @@ int launch_tail_bwd_fused(const float* gout, const float* wf, const void* act, c
   } while (0)
   if (act == nullptr) {
     if (!b3) return m2t_set_error(-2, "tail_bwd_fused: the recomputing variant needs the tail.3 bias");
-    if (variant == 32) { if (l1_pre) TB_GO32(true); else TB_GO32(false); }
-    else if (l1_pre) TB_GO(true, true); else TB_GO(true, false);
+    // (the kind is a template constant: a uniform run-time switch would sit in the stage of kernels that are bound by VALU issue and
+    // hold 243 / 244 registers with the l1 seed alone)
+    const int lk = l1_pre ? loss_kind : -1;
+    if (variant == 32) {
+      switch (lk) {
+        case M2T_PL_L1: TB_GO32(M2T_PL_L1); break;
+        case M2T_PL_MSE: TB_GO32(M2T_PL_MSE); break;
+        case M2T_PL_CHARBONNIER: TB_GO32(M2T_PL_CHARBONNIER); break;
+        case M2T_PL_SMOOTH_L1: TB_GO32(M2T_PL_SMOOTH_L1); break;
+        default: TB_GO32(-1); break;
+      }
+    } else {
+      switch (lk) {
+        case M2T_PL_L1: TB_GO(true, M2T_PL_L1); break;
+        case M2T_PL_MSE: TB_GO(true, M2T_PL_MSE); break;
+        case M2T_PL_CHARBONNIER: TB_GO(true, M2T_PL_CHARBONNIER); break;
+        case M2T_PL_SMOOTH_L1: TB_GO(true, M2T_PL_SMOOTH_L1); break;
+        default: TB_GO(true, -1); break;
+      }
+    }
   } else {
-    TB_GO(false, false);
+    TB_GO(false, -1);
   }
 #undef TB_GO
 #undef TB_GO32

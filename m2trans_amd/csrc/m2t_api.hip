@@ -101,6 +101,7 @@ struct m2t_plan {
   // m2t_l1_loss_deferred: the loss and the seed are produced inside the next m2t_backward (round 5)
   bool l1_deferred = false;
   const float* l1_hr = nullptr; float* l1_loss_out = nullptr; float l1_sc = 0.f, l1_R = 0.f;
+  M2TPixelLoss l1_pl;                  // the deferred loss's kind and factors (m2t_pixel_loss_deferred; m2t_l1_loss_deferred: l1)
   // ---- raw option values (m2t_set_option; include/m2t.h documents each).  Only resolve_schedule combines them. ----
   int use_fp32_fast = 1;               // fp32: the v_mfma_f32_32x32x2_f32 GEMM / qkv weight-gradient kernels of round 5 (k_gemm.hip); 0 = the 16x16x4 kernels
   int use_fused_l1 = 1;                // bf16 x4: the clamp + L1 seed inside the fused tail backward when the loss was requested through m2t_l1_loss_deferred
@@ -595,31 +596,55 @@ extern "C" int m2t_forward(m2t_plan* p, const float* params, const float* x, flo
   return 0;
 }
 
-extern "C" int m2t_l1_loss(m2t_plan* p, const float* hr, float lambda_l1, double divisor, float rgb_range,
-                           float* loss_out, void* workspace, void* stream) {
-  if (!p || !hr || !workspace) return m2t_set_error(M2T_ERR_ARG, "m2t_l1_loss: null argument");
-  if (!p->have_acts) return m2t_set_error(M2T_ERR_STATE, "m2t_l1_loss: call m2t_forward first");
+// The pixel-loss family (m2t_pixel_loss.h: l1, mse, charbonnier, smooth_l1 -- reference losses.py:225-230, :287-297).  The kind only
+// selects the per-pixel function inside the kernel that takes the loss; state rules, launches and the schedule are those of the L1 loss.
+static int pixel_loss_request(const char* who, int kind, float param, float weight, double divisor, M2TPixelLoss* pl) {
+  if (!m2t_pixel_loss_make(kind, param, (float)((double)weight / divisor), pl)) {
+    char msg[200];
+    if (kind < 0 || kind >= M2T_PL_KINDS) snprintf(msg, sizeof msg, "%s: unknown pixel-loss kind %d (0 l1, 1 mse, 2 charbonnier, 3 smooth_l1)", who, kind);
+    else if (kind == M2T_PL_CHARBONNIER) snprintf(msg, sizeof msg, "%s: charbonnier needs a finite eps > 0, got %g", who, (double)param);
+    else snprintf(msg, sizeof msg, "%s: smooth_l1 needs a finite beta > 0, got %g (beta = 0 is the l1 loss: use kind l1)", who, (double)param);
+    return m2t_set_error(M2T_ERR_ARG, msg);
+  }
+  return 0;
+}
+
+extern "C" int m2t_pixel_loss(m2t_plan* p, int kind, float param, const float* hr, float weight, double divisor, float rgb_range,
+                              float* loss_out, void* workspace, void* stream) {
+  if (!p || !hr || !workspace) return m2t_set_error(M2T_ERR_ARG, "m2t_pixel_loss: null argument");
+  M2TPixelLoss pl;
+  CK(pixel_loss_request("m2t_pixel_loss", kind, param, weight, divisor, &pl));
+  if (!p->have_acts) return m2t_set_error(M2T_ERR_STATE, "m2t_pixel_loss: call m2t_forward first");
   char* const ws = (char*)workspace;
-  const float sc = (float)((double)lambda_l1 / divisor);
   CK(launch_clamp_l1((const float*)(ws + p->hd.srpre), hr, nullptr, (float*)(ws + p->hd.gpre), (float*)(ws + p->hd.loss_part), loss_out,
-                     p->B, p->Hsp, p->Wsp, p->Hs, p->Ws, rgb_range, sc, sc, (hipStream_t)stream));
+                     p->B, p->Hsp, p->Wsp, p->Hs, p->Ws, rgb_range, pl.loss_scale, pl.gscale, (hipStream_t)stream, pl.kind, pl.param, pl.f0, pl.f1));
   p->have_seed = true;
   p->l1_deferred = false;
   return 0;
 }
+extern "C" int m2t_l1_loss(m2t_plan* p, const float* hr, float lambda_l1, double divisor, float rgb_range,
+                           float* loss_out, void* workspace, void* stream) {
+  return m2t_pixel_loss(p, M2T_PL_L1, 0.f, hr, lambda_l1, divisor, rgb_range, loss_out, workspace, stream);
+}
 
-// The same loss and seed, produced INSIDE the next m2t_backward: on the bf16 x4 path the clamp + L1 seed are taken by the fused tail
+// The same loss and seed, produced INSIDE the next m2t_backward: on the bf16 x4 path the clamp + loss seed are taken by the fused tail
 // backward while it stages its g(sr) halo (the pre-clamp output is read there instead of a stored seed: one 150 MB pass and two
-// launches fewer per step); everywhere else m2t_backward simply runs m2t_l1_loss's kernel first.  hr must stay valid until then.
-extern "C" int m2t_l1_loss_deferred(m2t_plan* p, const float* hr, float lambda_l1, double divisor, float rgb_range,
-                                    float* loss_out, void* workspace, void* stream) {
+// launches fewer per step); everywhere else m2t_backward simply runs m2t_pixel_loss's kernel first.  hr must stay valid until then.
+extern "C" int m2t_pixel_loss_deferred(m2t_plan* p, int kind, float param, const float* hr, float weight, double divisor, float rgb_range,
+                                       float* loss_out, void* workspace, void* stream) {
   (void)stream;
-  if (!p || !hr || !workspace || !loss_out) return m2t_set_error(M2T_ERR_ARG, "m2t_l1_loss_deferred: null argument");
-  if (!p->have_acts) return m2t_set_error(M2T_ERR_STATE, "m2t_l1_loss_deferred: call m2t_forward first");
-  p->l1_hr = hr; p->l1_loss_out = loss_out; p->l1_sc = (float)((double)lambda_l1 / divisor); p->l1_R = rgb_range;
+  if (!p || !hr || !workspace || !loss_out) return m2t_set_error(M2T_ERR_ARG, "m2t_pixel_loss_deferred: null argument");
+  M2TPixelLoss pl;
+  CK(pixel_loss_request("m2t_pixel_loss_deferred", kind, param, weight, divisor, &pl));
+  if (!p->have_acts) return m2t_set_error(M2T_ERR_STATE, "m2t_pixel_loss_deferred: call m2t_forward first");
+  p->l1_hr = hr; p->l1_loss_out = loss_out; p->l1_sc = pl.loss_scale; p->l1_R = rgb_range; p->l1_pl = pl;
   p->l1_deferred = true;
   p->have_seed = true;
   return 0;
+}
+extern "C" int m2t_l1_loss_deferred(m2t_plan* p, const float* hr, float lambda_l1, double divisor, float rgb_range,
+                                    float* loss_out, void* workspace, void* stream) {
+  return m2t_pixel_loss_deferred(p, M2T_PL_L1, 0.f, hr, lambda_l1, divisor, rgb_range, loss_out, workspace, stream);
 }
 
 // upstream gradient -> gradient of the padded pre-clamp output (clamp mask, zero outside the crop)
@@ -659,7 +684,7 @@ extern "C" int m2t_add_output_grad(m2t_plan* p, const float* g, int gh, int gw, 
                                    void* workspace, void* stream) {
   if (!p || !g || !workspace || gh < 1 || gw < 1) return m2t_set_error(M2T_ERR_ARG, "m2t_add_output_grad: null / bad argument");
   if (!p->have_acts || !p->have_seed || p->l1_deferred)
-    return m2t_set_error(M2T_ERR_STATE, "m2t_add_output_grad: needs a materialised seed (m2t_l1_loss or m2t_set_output_grad)");
+    return m2t_set_error(M2T_ERR_STATE, "m2t_add_output_grad: needs a materialised seed (m2t_l1_loss / m2t_pixel_loss or m2t_set_output_grad)");
   for (int b = 0; b < p->B; ++b) {
     const int y0 = crops_host ? crops_host[2 * b] : 0, x0 = crops_host ? crops_host[2 * b + 1] : 0;
     if (y0 < 0 || x0 < 0 || y0 + gh > p->Hs || x0 + gw > p->Ws) return m2t_set_error(M2T_ERR_ARG, "m2t_add_output_grad: block outside the image");
@@ -809,7 +834,8 @@ static int backward_impl(m2t_plan* p, const float* params, const float* x, float
   const bool l1_in_tail = p->l1_deferred && sc.l1_in_tail;
   if (p->l1_deferred && !l1_in_tail)
     CK(launch_clamp_l1((const float*)(ws + hd.srpre), p->l1_hr, nullptr, (float*)(ws + hd.gpre), loss_part, p->l1_loss_out,
-                       p->B, p->Hsp, p->Wsp, p->Hs, p->Ws, p->l1_R, p->l1_sc, p->l1_sc, st));
+                       p->B, p->Hsp, p->Wsp, p->Hs, p->Ws, p->l1_R, p->l1_sc, p->l1_pl.gscale, st, p->l1_pl.kind, p->l1_pl.param, p->l1_pl.f0,
+                       p->l1_pl.f1));
   fork();
   hipEvent_t im2col_done = nullptr;           // head_cols is produced on the side stream; the head weight gradient may run on the main one
   if (!skip_head) { CK(launch_head_im2col(dt, x, ws + hd.head_cols, B, p->H0, p->W0, H, W, sd)); im2col_done = side_marker(); }
@@ -843,8 +869,8 @@ static int backward_impl(m2t_plan* p, const float* params, const float* x, float
       else
         CK(launch_tail_bwd_fused(gpre, wlast, stored ? ws + hd.t2act : nullptr, stored ? ws + hd.t2der : nullptr, ws + hd.t1act, ws + hd.t1der,
                                  pk(hd.t3T), params + hd.tail3_b, ws + hd.g_t1pre, swf, sw3, sb3, &ns, B, p->Hsp, p->Wsp, st,
-                                 l1_in_tail ? (const float*)(ws + hd.srpre) : nullptr, p->l1_hr, loss_part, p->Hs, p->Ws, p->l1_R, p->l1_sc,
-                                 sc.tail_bwd == TAIL_BWD_RC32 ? 32 : 16)); }
+                                 l1_in_tail ? (const float*)(ws + hd.srpre) : nullptr, p->l1_hr, loss_part, p->Hs, p->Ws, p->l1_R,
+                                 p->l1_pl.gscale, sc.tail_bwd == TAIL_BWD_RC32 ? 32 : 16, p->l1_pl.kind, p->l1_pl.param, p->l1_pl.f0, p->l1_pl.f1)); }
     if (l1_in_tail) CK(launch_loss_finish(loss_part, ns, p->l1_sc, p->l1_loss_out, st));
     if (!skip) {
       defer(swf, hd.wlast, ns, 32 * 64, 3, 0, 0, 0);

@@ -2,6 +2,7 @@
 #pragma once
 #include <algorithm>
 #include "m2t_common.h"
+#include "m2t_pixel_loss.h"
 #include <hip/hip_ext.h>
 
 #define M2T_NORM_SPLIT 32     // pixel splits per image in the InstanceNorm reductions
@@ -89,8 +90,10 @@ int launch_colsum(int dt, const void* a, int lda, long long M, int N, float* par
                   int accumulate, hipStream_t st, int unshuf = 0, int gH = 0, int gW = 0, int gr = 1, int gC = 64,
                   int* nblk_out = nullptr);   // nblk_out != null: write the partials only and report their count
 int launch_multi_reduce(const float* arena, float* grads, const m2t_red_desc* descs, int ndesc, hipStream_t st);
+// loss_kind (M2TPixelLossKind) and its factors lparam / lf0 / lf1: m2t_pixel_loss.h (gscale carries mse's 2); the default is the L1 loss
 int launch_clamp_l1(const float* pre, const float* hr, float* sr, float* gpre, float* part, float* loss, int B, int Hp,
-                    int Wp, int Hs, int Ws, float R, float loss_scale, float gscale, hipStream_t st);
+                    int Wp, int Hs, int Ws, float R, float loss_scale, float gscale, hipStream_t st, int loss_kind = M2T_PL_L1,
+                    float lparam = 0.f, float lf0 = 0.f, float lf1 = 0.f);
 // loss = loss_scale * sum(part[0 .. n)) in a fixed order (n <= M2T_LOSS_BLOCKS)
 int launch_loss_finish(const float* part, int n, float loss_scale, float* loss, hipStream_t st);
 int launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps,
@@ -211,11 +214,13 @@ int tail_bwd_fused_blocks(int B, int H, int W);
 // act == der == nullptr: gelu(t2) / gelu'(t2) are recomputed per tile from a1, w3t and the tail.3 bias b3 (torch order)
 // l1_pre != nullptr (recomputing variant only): the clamp + L1 seed of launch_clamp_l1 is taken inside the kernel from the pre-clamp
 // output l1_pre [B][3][H][W] and the target l1_hr [B][3][Hs][Ws] (gout is then unused); l1_part [tail_bwd_fused_blocks] receives the
-// partial sums of |clamp(pre) - hr| for launch_loss_finish
+// partial sums of |clamp(pre) - hr| for launch_loss_finish.  loss_kind / lparam / lf0 / lf1 as launch_clamp_l1's: the same per-pixel function
+// (m2t_pixel_loss.h), so the seed taken inside and the stand-alone one cannot drift apart
 int launch_tail_bwd_fused(const float* gout, const float* wf, const void* act, const void* der, const void* a1, const void* d1,
                           const void* w3t, const float* b3, void* gt1, float* slab_wf, float* slab_w3, float* slab_b3,
                           int* nslab_out, int B, int H, int W, hipStream_t st, const float* l1_pre = nullptr, const float* l1_hr = nullptr,
-                          float* l1_part = nullptr, int Hs = 0, int Ws = 0, float R = 0.f, float gscale = 0.f, int variant = 32);
+                          float* l1_part = nullptr, int Hs = 0, int Ws = 0, float R = 0.f, float gscale = 0.f, int variant = 32,
+                          int loss_kind = M2T_PL_L1, float lparam = 0.f, float lf0 = 0.f, float lf1 = 0.f);
 // variant (recomputing form): 32 = the round-6 kernel on v_mfma_f32_32x32x16_bf16 (conflict-free LDS operand reads, g(t2) formed in
 // registers; results agree with the older kernel to fp32 summation order), 16 = the 16x16x32 kernel of rounds 2-5 (what the stored
 // form always runs)

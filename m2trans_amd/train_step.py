@@ -24,6 +24,11 @@ Optimizer options (all off by default; replace ``clip_grad_norm_``, Adam's ``wei
 knob train.py:81 passes -- and a hand-kept EMA copy): the global norm of the accumulated, all-reduced gradient goes into a
 device-resident record (m2t_grad_norm: two launches, fp64, no atomics), and ONE pass (m2t_adam_step_ex) clips, decays, steps
 and updates the EMA weights -- or, with ``skip_nonfinite`` and a non-finite norm, touches nothing.  No host synchronisation.
+
+Pixel losses (``pixel_loss=``; the criteria the reference offers next to L1, losses.py:225-230 l1 / sl1 / l2 and :287-297
+L1_Charbonnier_loss): the kind only selects the per-pixel function inside the kernel that takes the loss (m2t_pixel_loss /
+m2t_pixel_loss_deferred), so every kind runs the schedule of the L1 step -- the seed fused into the x4 tail backward, accumulation,
+the overlapped exchange and the optimizer options included.
 """
 from __future__ import annotations
 
@@ -42,6 +47,38 @@ def cosine_lr(epoch: int, lr0: float = 1e-4, eta_min: float = 1e-6, t_max: float
     """CosineAnnealingLR(optimizer, float(epochs), eta_min) evaluated at `epoch` scheduler steps
     (train.py:82,358; the scheduler is stepped once per epoch)."""
     return eta_min + 0.5 * (lr0 - eta_min) * (1.0 + math.cos(math.pi * epoch / t_max))
+
+
+# pixel_loss name -> (kind of include/m2t.h's m2t_pixel_loss_kind, canonical name, name of its parameter, default)
+PIXEL_LOSSES = {"l1": (0, "l1", None, None), "mse": (1, "mse", None, None), "l2": (1, "mse", None, None),
+                "charbonnier": (2, "charbonnier", "eps", 1e-6),                  # losses.py:295: sqrt(diff * diff + 1e-6)
+                "smooth_l1": (3, "smooth_l1", "beta", 1.0), "sl1": (3, "smooth_l1", "beta", 1.0)}      # nn.SmoothL1Loss's default
+
+
+def resolve_pixel_loss(name, param=None):
+    """(kind, canonical name, parameter) of TrainStep's ``pixel_loss`` / ``pixel_loss_param``; M2TError for an unknown name, a
+    parameter given to a kind that takes none, or an eps / beta that is not a finite number > 0.  The parameter of a kind that
+    takes none is None."""
+    key = name.lower() if isinstance(name, str) else name
+    if not isinstance(key, str) or key not in PIXEL_LOSSES:
+        raise _lib.M2TError(f"pixel_loss must be one of {sorted(PIXEL_LOSSES)}, got {name!r}")
+    kind, canon, pname, default = PIXEL_LOSSES[key]
+    if pname is None:
+        if param is not None:
+            raise _lib.M2TError(f"pixel_loss {canon!r} takes no parameter, got pixel_loss_param={param!r}")
+        return kind, canon, None
+    if param is None:
+        param = default
+    try:
+        value = float(param)
+    except (TypeError, ValueError):
+        raise _lib.M2TError(f"pixel_loss {canon!r}: {pname} must be a finite number > 0, got {param!r}") from None
+    # (the library takes the parameter as a float: what rounds to 0 or inf there is refused here, at construction)
+    as_f32 = C.c_float(value).value
+    if not (math.isfinite(as_f32) and as_f32 > 0.0):
+        hint = " (beta = 0 is the l1 loss: use pixel_loss='l1')" if canon == "smooth_l1" and value == 0.0 else ""
+        raise _lib.M2TError(f"pixel_loss {canon!r}: {pname} must be a finite number > 0, got {param!r}{hint}")
+    return kind, canon, value
 
 
 _STREAMS: dict = {}
@@ -64,8 +101,10 @@ class TrainStep:
                  overlap_comm: bool = True, force_comm_path: bool = False, overlap_semantic: bool = True,
                  accum_steps: int = 1, max_grad_norm: Optional[float] = None, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, ema_decay: Optional[float] = None, skip_nonfinite: bool = False,
-                 track_grad_norm: bool = False):
+                 track_grad_norm: bool = False, pixel_loss: str = "l1", pixel_loss_param: Optional[float] = None):
         self.model = model
+        # the pixel term: lambda_l1 (the reference's config key) stays its weight and l1_loss the tensor that holds it, whatever the kind
+        self.set_pixel_loss(pixel_loss, pixel_loss_param)
         # gradient accumulation: one optimizer step consumes accum_steps equal micro-batches (forward_backward calls); the
         # gradients and the loss of calls 2..k of a cycle are added to the first call's by m2t_grad_accumulate
         if int(accum_steps) != accum_steps or int(accum_steps) < 1:
@@ -143,6 +182,25 @@ class TrainStep:
         self.ema_params = flat.detach().clone() if self.ema_decay is not None else None
         self._optim_ex = self._use_norm or self.weight_decay != 0.0 or self.ema_params is not None
 
+    def set_pixel_loss(self, name, param=None):
+        """Choose the pixel loss: 'l1', 'mse' (alias 'l2'), 'charbonnier' (param = eps, default 1e-6), 'smooth_l1' (alias 'sl1';
+        param = beta, default 1.0).  Takes effect with the next forward_backward (checkpoint.import_checkpoint calls this)."""
+        if getattr(self, "micro_count", 0) != 0:
+            raise _lib.M2TError(f"set_pixel_loss in the middle of an accumulation cycle ({self.micro_count} of {self.accum_steps} "
+                                "micro-batches since the last optimizer step)")
+        self._pixel_kind, self.pixel_loss, self.pixel_loss_param = resolve_pixel_loss(name, param)
+
+    def _pixel_loss_call(self, lib, deferred: bool, plan, hr_img, divisor, l1_loss, ws, st):
+        """The loss + seed request of one (micro-)batch.  'l1' calls the entry points it always called."""
+        m = self.model
+        if self._pixel_kind == 0:
+            fn, what = (lib.m2t_l1_loss_deferred, "m2t_l1_loss_deferred") if deferred else (lib.m2t_l1_loss, "m2t_l1_loss")
+            _lib.check(fn(plan.handle, _lib.ptr(hr_img), self.lambda_l1, divisor, float(m.rgb_range), _lib.ptr(l1_loss), ws, st), what)
+            return
+        fn, what = (lib.m2t_pixel_loss_deferred, "m2t_pixel_loss_deferred") if deferred else (lib.m2t_pixel_loss, "m2t_pixel_loss")
+        _lib.check(fn(plan.handle, self._pixel_kind, self.pixel_loss_param or 0.0, _lib.ptr(hr_img), self.lambda_l1, divisor,
+                      float(m.rgb_range), _lib.ptr(l1_loss), ws, st), what)
+
     def applied_step_count(self) -> int:
         """step_count minus the optimizer steps skip_nonfinite left out (Adam's effective step number).  Synchronises."""
         return self.step_count - (int(self.skipped_steps.item()) if self.skipped_steps is not None else 0)
@@ -176,7 +234,7 @@ class TrainStep:
 
     # -- pieces (also used by tests) -------------------------------------------------------
     def forward_backward(self, lr_img: torch.Tensor, hr_img: torch.Tensor, captions=None) -> torch.Tensor:
-        """forward + L1 (+ the constant SemanticLoss term) + backward into model.flat_grads; returns the
+        """forward + the pixel loss (L1 by default) (+ the constant SemanticLoss term) + backward into model.flat_grads; returns the
         device loss tensor (this rank's share of the global mean).  With accum_steps = k > 1 this is ONE micro-batch: the first
         call of a cycle fills model.flat_grads and the loss, calls 2..k add to them (in call order, fp32), and a call beyond the
         k-th before optimizer_step() raises."""
@@ -210,8 +268,7 @@ class TrainStep:
                                        float(m.rgb_range), 1, ws, st), "m2t_forward")
             # (deferred: the loss and the backward seed are produced inside m2t_backward, which follows at once -- on the bf16 x4
             #  path by the fused tail backward itself; hr_img stays alive until then)
-            _lib.check(lib.m2t_l1_loss_deferred(plan.handle, _lib.ptr(hr_img), self.lambda_l1, divisor, float(m.rgb_range),
-                                                _lib.ptr(l1_loss), ws, st), "m2t_l1_loss_deferred")
+            self._pixel_loss_call(lib, True, plan, hr_img, divisor, l1_loss, ws, st)
             fwd_done = torch.cuda.current_stream(lr_img.device).record_event() if (use_clip and self.overlap_semantic) else None
             _lib.check(lib.m2t_backward(plan.handle, _lib.ptr(m.flat_params), _lib.ptr(lr_img), _lib.ptr(grads),
                                         ws, st), "m2t_backward")
@@ -270,8 +327,7 @@ class TrainStep:
             _lib.check(lib.m2t_forward(plan.handle, _lib.ptr(m.flat_params), _lib.ptr(lr_img), _lib.ptr(sr),
                                        float(m.rgb_range), 1, ws, st), "m2t_forward")
             tot, g, origins = sl._value_and_grad(sr, hr_img, captions)
-            _lib.check(lib.m2t_l1_loss(plan.handle, _lib.ptr(hr_img), self.lambda_l1, divisor, float(m.rgb_range),
-                                       _lib.ptr(l1_loss), ws, st), "m2t_l1_loss")
+            self._pixel_loss_call(lib, False, plan, hr_img, divisor, l1_loss, ws, st)
             g = g.contiguous()
             arr = None
             if origins is not None:
