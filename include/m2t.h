@@ -187,6 +187,37 @@ int m2t_set_output_grad(m2t_plan* p, const float* g_sr, float rgb_range, void* w
  * M2T_ERR_STATE without a seed or after m2t_l1_loss_deferred / m2t_pixel_loss_deferred (no materialised seed); M2T_ERR_ARG for a block outside the image. */
 int m2t_add_output_grad(m2t_plan* p, const float* g, int gh, int gw, const int* crops_host, float scale, float rgb_range,
                         void* workspace, void* stream);
+/* The structural term of the loss surface: weight * (1 - mean SSIM) with its gradient (the reference's losses.py:8 imports SSIMLoss /
+ * MultiScaleSSIMLoss from piq next to the pixel criteria; utils.py:232-234 scores every epoch by pytorch_msssim.ssim).  Per channel,
+ * the pytorch_msssim.ssim / piq.ssim(downsample=False) form: x = clamp(pre, 0, R) / R, y = hr / R (data_range 1), separable 11-tap
+ * Gaussian sigma 1.5 (the fp32 taps torch.exp / torch.sum give, as pytorch_msssim builds them, widened to fp64), VALID -> a (H-10) x (W-10) map per
+ * channel, K = (0.01, 0.03), no non-negativity clamp.  Moments, map and gradient coefficients are fp64; inputs are fp32; every
+ * gradient value is rounded to fp32 once and added in fp32.  Deterministic (no atomics; partial sums folded in a fixed order).
+ * piq.SSIMLoss's default downsample=True (an average pooling in front, by 2 at 512 x 512) is NOT applied.  MS-SSIM is not offered.
+ *
+ * m2t_ssim_loss_tensor (plan-free): x [B,C,H,W] float32 on the device with image stride x_image_stride, channel stride
+ * x_image_stride / C, row stride x_row_stride (elements); y contiguous [B,C,H,W].  With S the SSIM map of (x / data_range, y / data_range),
+ * x clamped to [0, data_range] first when clamp != 0:
+ *   loss_out[0] = (accumulate ? loss_out[0] : 0) + (float)(scale * sum_map (1 - S))        (pass scale = 1 / map entries for the mean)
+ *   gx_add[q]  += (float)(-scale * d sum(S) / dx[q])     x's strides; where clamp != 0 and x[q] is outside [0, data_range] (ends
+ *                 included in the pass band) the element is left alone; elements outside [H,W] are never touched; NULL = value only.
+ * scratch: m2t_ssim_loss_scratch_bytes(B, C, H, W) bytes on the device (0 when H < 11 or W < 11), no initialisation needed.
+ * M2T_ERR_ARG: a null x / y / loss_out / scratch, H or W < 11, data_range not a finite number > 0, B * C outside 1 .. 65535, strides
+ * that do not hold the image.
+ *
+ * m2t_ssim_loss: the same routine on the forward's pre-clamp output (rgb_range = R, the clamp on), adding into the seed that
+ * m2t_l1_loss / m2t_pixel_loss (weight 0 for SSIM alone) or m2t_set_output_grad materialised: seed += -(weight / divisor) / R *
+ * d sum(S) / dx through the clamp mask, exactly 0 in the reflect padding; loss_out as above with scale = weight / divisor.  divisor =
+ * the GLOBAL number of map entries, world * accum * B * 3 * (Hs-10) * (Ws-10), so that rank shards and micro-batches sum to
+ * weight * (1 - global mean SSIM) (the scheme of the pixel term).  scratch: m2t_ssim_loss_scratch_bytes(B, 3, Hs, Ws).
+ * State rules of m2t_add_output_grad: M2T_ERR_STATE without a forward with saved activations, without a seed, or after
+ * m2t_l1_loss_deferred / m2t_pixel_loss_deferred.  M2T_ERR_ARG: a null argument, an SR image below 11 x 11, a bad rgb_range / divisor. */
+size_t m2t_ssim_loss_scratch_bytes(int B, int C, int H, int W);
+int m2t_ssim_loss_tensor(const float* x, const float* y, int B, int C, int H, int W, long long x_image_stride, int x_row_stride,
+                         float data_range, int clamp, double scale, float* gx_add, float* loss_out, int accumulate, void* scratch,
+                         void* stream);
+int m2t_ssim_loss(m2t_plan* p, const float* hr, float weight, double divisor, float rgb_range, float* loss_out, int accumulate,
+                  void* scratch, void* workspace, void* stream);
 /* loss.backward() (train.py:209) restricted to the model: fills grads (flat, same layout as
  * params; every element is written). */
 int m2t_backward(m2t_plan* p, const float* params, const float* x, float* grads, void* workspace,

@@ -32,6 +32,9 @@ SIGNATURES = {
     "m2t_pixel_loss_deferred": (_i, [_vp, _i, _f, _vp, _f, _d, _f, _vp, _vp, _vp]),
     "m2t_set_output_grad": (_i, [_vp, _vp, _f, _vp, _vp]),
     "m2t_add_output_grad": (_i, [_vp, _vp, _i, _i, C.POINTER(_i), _f, _f, _vp, _vp]),
+    "m2t_ssim_loss_scratch_bytes": (C.c_size_t, [_i, _i, _i, _i]),
+    "m2t_ssim_loss_tensor": (_i, [_vp, _vp, _i, _i, _i, _i, _ll, _i, _f, _i, _d, _vp, _vp, _i, _vp, _vp]),
+    "m2t_ssim_loss": (_i, [_vp, _vp, _f, _d, _f, _vp, _i, _vp, _vp, _vp]),
     "m2t_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "m2t_backward_ex": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_ubyte), _vp, _vp]),
     "m2t_adam_step": (_i, [_vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _i, _f, _vp]),

@@ -25,7 +25,9 @@ above, key for key.
 
 With a pixel loss other than L1 (TrainStep(pixel_loss=...)) the dict carries ``m2t_loss`` = {"pixel_loss": name, "param": eps /
 beta / None}; ``import_checkpoint`` sets the TrainStep's loss from it and leaves the loss alone when the file has no such entry.
-An L1 run writes no entry: its dict is the one above.
+An L1 run writes no entry: its dict is the one above.  With TrainStep(lambda_ssim > 0) the entry also carries ``"lambda_ssim"``
+(and then exists for an L1 pixel term too); ``import_checkpoint`` calls ``set_lambda_ssim`` with it.  With lambda_ssim = 0 the
+key is absent and the dict is the one described above, byte for byte.
 """
 from __future__ import annotations
 
@@ -61,9 +63,13 @@ def _pixel_loss(train_step):
     """The ``m2t_loss`` entry of a step object, or None for L1 (and for an object that knows no pixel losses)."""
     from .train_step import resolve_pixel_loss
     _, canon, value = resolve_pixel_loss(getattr(train_step, "pixel_loss", "l1"), getattr(train_step, "pixel_loss_param", None))
-    if canon == "l1":
+    lam = float(getattr(train_step, "lambda_ssim", 0.0) or 0.0)
+    if canon == "l1" and lam == 0.0:
         return None
-    return {"pixel_loss": canon, "param": value}
+    out = {"pixel_loss": canon, "param": value}
+    if lam != 0.0:
+        out["lambda_ssim"] = lam
+    return out
 
 
 def _skipped(train_step) -> int:
@@ -158,6 +164,12 @@ def import_checkpoint(ckpt: dict, model, train_step=None) -> int:
         else:
             from .train_step import resolve_pixel_loss
             _, train_step.pixel_loss, train_step.pixel_loss_param = resolve_pixel_loss(ml["pixel_loss"], ml.get("param"))
+        if "lambda_ssim" in ml:
+            if hasattr(train_step, "set_lambda_ssim"):
+                train_step.set_lambda_ssim(ml["lambda_ssim"])
+            else:
+                from .train_step import resolve_lambda_ssim
+                train_step.lambda_ssim = resolve_lambda_ssim(ml["lambda_ssim"])
     opt = ckpt.get("optimizer_state_dict") or {}
     sch = ckpt.get("scheduler_state_dict")
     if not opt.get("state") and not opt.get("param_groups") and sch is None:

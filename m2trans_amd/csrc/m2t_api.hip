@@ -704,6 +704,23 @@ extern "C" int m2t_add_output_grad(m2t_plan* p, const float* g, int gh, int gw, 
   return 0;
 }
 
+// weight * (1 - mean SSIM) (k_ssim_loss.hip; losses.py:8, utils.py:232-234) on the forward's pre-clamp output, added into the
+// materialised seed: the routine of m2t_ssim_loss_tensor on ws:srpre (padded Hsp x Wsp, image in the top-left Hs x Ws) and ws:gpre.
+// State rules of m2t_add_output_grad.  Scratch is the caller's: no plan option, no workspace region.
+extern "C" int m2t_ssim_loss(m2t_plan* p, const float* hr, float weight, double divisor, float rgb_range, float* loss_out, int accumulate,
+                             void* scratch, void* workspace, void* stream) {
+  if (!p || !hr || !loss_out || !scratch || !workspace) return m2t_set_error(M2T_ERR_ARG, "m2t_ssim_loss: null argument");
+  if (!(rgb_range > 0.f) || !std::isfinite(rgb_range) || !(divisor > 0.0) || !std::isfinite(divisor) || !std::isfinite(weight))
+    return m2t_set_error(M2T_ERR_ARG, "m2t_ssim_loss: rgb_range and divisor must be finite numbers > 0, weight finite");
+  if (p->Hs < 11 || p->Ws < 11) return m2t_set_error(M2T_ERR_ARG, "m2t_ssim_loss: the SR image is smaller than the 11 x 11 window");
+  if (p->B * 3 > 65535) return m2t_set_error(M2T_ERR_ARG, "m2t_ssim_loss: batch too large (B * 3 <= 65535)");
+  if (!p->have_acts || !p->have_seed || p->l1_deferred)
+    return m2t_set_error(M2T_ERR_STATE, "m2t_ssim_loss: needs a materialised seed (m2t_l1_loss / m2t_pixel_loss or m2t_set_output_grad)");
+  char* const ws = (char*)workspace;
+  return launch_ssim_loss((const float*)(ws + p->hd.srpre), hr, p->B, 3, p->Hs, p->Ws, 3LL * p->Hsp * p->Wsp, p->Wsp, rgb_range, 1,
+                          (double)weight / divisor, (float*)(ws + p->hd.gpre), loss_out, accumulate ? 1 : 0, scratch, (hipStream_t)stream);
+}
+
 // Two-stream backward.  The data-gradient chain (what the next kernel needs) runs on the
 // caller's stream; everything that only produces PARAMETER gradients (weight/bias gradients,
 // slab reductions, rel-pos reductions) runs on the plan's side stream, forked/joined with

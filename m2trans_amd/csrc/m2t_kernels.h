@@ -326,3 +326,10 @@ int launch_transpose_convert(int dt, const float* src, void* dst, int N, int K, 
 int launch_bicubic_resize_bwd(const float* gdst, float* gsrc, int NC, int Hin, int Win, int Hout, int Wout, hipStream_t st);
 int launch_add_output_grad(const float* pre, const float* g, float* gpre, int B, int Hp, int Wp, int gh, int gw, const M2TCropOrigins& org,
                            float scale, float R, hipStream_t st);
+// ---- k_ssim_loss.hip (the 1 - SSIM loss term and its gradient: m2t_ssim_loss_tensor / m2t_ssim_loss) ----------
+// x [B][C][H][W] with image stride xs_img, channel stride xs_img / C, row stride xs_row; y contiguous; gx_add (or nullptr) has x's strides:
+// gx_add[q] += -scale * d sum(S) / dx[q] (through the clamp mask when clamp); loss_out = (accumulate ? loss_out : 0) + scale * sum(1 - S).
+// scratch: ssim_loss_scratch_bytes(B, C, H, W) bytes (0 when H or W < 11).  Arguments are checked by the callers.
+size_t ssim_loss_scratch_bytes(int B, int C, int H, int W);
+int launch_ssim_loss(const float* x, const float* y, int B, int C, int H, int W, long long xs_img, int xs_row, float R, int clamp,
+                     double scale, float* gx_add, float* loss_out, int accumulate, void* scratch, hipStream_t st);

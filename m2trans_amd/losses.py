@@ -469,3 +469,61 @@ class _SemanticLossGrad(torch.autograd.Function):
     def backward(ctx, go):
         (g,) = ctx.saved_tensors
         return paste_crops(g * go.reshape(()), ctx.origins, ctx.shape).to(go.dtype), None, None, None
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The structural term: 1 - SSIM (the reference imports SSIMLoss / MultiScaleSSIMLoss from piq, losses.py:8, and scores every
+# epoch by SSIM, utils.py:232-234).  Value and gradient are HIP (m2t_ssim_loss_tensor, k_ssim_loss.hip); there is no torch fallback.
+# ---------------------------------------------------------------------------------------------------------------
+class _SSIMLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, data_range):
+        lib = _lib.load()
+        xc, yc = x.detach().contiguous().float(), y.detach().contiguous().float()
+        B, Cn, H, W = xc.shape
+        nbytes = lib.m2t_ssim_loss_scratch_bytes(B, Cn, H, W)
+        if nbytes == 0:
+            raise M2TError(f"ssim_loss: image {H}x{W} is smaller than the 11 x 11 window")
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=xc.device)
+        out = torch.empty(1, dtype=torch.float32, device=xc.device)
+        # value and gradient come from one launch; the gradient of the MEAN, scaled by the upstream gradient in backward
+        grad = torch.zeros_like(xc) if ctx.needs_input_grad[0] else None
+        n = B * Cn * (H - 10) * (W - 10)
+        with torch.cuda.device(xc.device):
+            _lib.check(lib.m2t_ssim_loss_tensor(_lib.ptr(xc), _lib.ptr(yc), B, Cn, H, W, Cn * H * W, W, float(data_range), 0, 1.0 / n,
+                                                _lib.ptr(grad), _lib.ptr(out), 0, _lib.ptr(scratch), _lib.stream_ptr()),
+                       "m2t_ssim_loss_tensor")
+        ctx.grad = grad
+        ctx.x_dtype = x.dtype
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        return (ctx.grad * g).to(ctx.x_dtype), None, None
+
+
+def ssim_loss(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0) -> torch.Tensor:
+    """mean(1 - SSIM(x, y)) over the per-channel VALID map, the ``pytorch_msssim.ssim`` / ``piq.ssim(downsample=False)`` form
+    (11-tap Gaussian sigma 1.5, K = (0.01, 0.03), no clamp of the map, inputs NOT clamped to the data range), for device tensors
+    [B,C,H,W] with H, W >= 11; differentiable with respect to ``x`` only.  ``piq.SSIMLoss``'s default ``downsample=True`` (an
+    average pooling in front, by 2 at 512 x 512) is not applied.  fp64 inside the kernel, fp32 in and out."""
+    if x.dim() != 4 or x.shape != y.shape:
+        raise M2TError(f"ssim_loss: expected two [B,C,H,W] tensors of equal shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if not (x.is_cuda and y.is_cuda):
+        raise M2TError("ssim_loss needs HIP device tensors (there is no host implementation)")
+    if y.requires_grad:
+        raise M2TError("ssim_loss gives the gradient with respect to x only: y must not require grad (detach it)")
+    if not (float(data_range) > 0.0):
+        raise M2TError(f"ssim_loss: data_range must be > 0, got {data_range!r}")
+    return _SSIMLossFn.apply(x, y, float(data_range))
+
+
+class SSIMLoss(nn.Module):
+    """``ssim_loss`` as a module (``piq.SSIMLoss(downsample=False, data_range=...)``'s value for inputs inside the data range)."""
+
+    def __init__(self, data_range: float = 1.0):
+        super().__init__()
+        self.data_range = float(data_range)
+
+    def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        return ssim_loss(x, y, self.data_range)

@@ -29,6 +29,12 @@ Pixel losses (``pixel_loss=``; the criteria the reference offers next to L1, los
 L1_Charbonnier_loss): the kind only selects the per-pixel function inside the kernel that takes the loss (m2t_pixel_loss /
 m2t_pixel_loss_deferred), so every kind runs the schedule of the L1 step -- the seed fused into the x4 tail backward, accumulation,
 the overlapped exchange and the optimizer options included.
+
+Structural term (``lambda_ssim``; the reference imports SSIMLoss from piq next to the pixel criteria, losses.py:8, and scores every
+epoch by SSIM, utils.py:232-234): ``lambda_ssim * (1 - mean SSIM)`` per RGB channel in the pytorch_msssim.ssim /
+piq.ssim(downsample=False) form -- piq.SSIMLoss's default ``downsample=True`` pooling is NOT applied -- with its gradient in HIP
+(m2t_ssim_loss, fp64 inside).  A step with lambda_ssim > 0 takes the MATERIALISED seed (immediate pixel loss, then m2t_ssim_loss adds
+into it): the seed fused into the x4 tail backward does not apply.  With lambda_ssim = 0 (the default) the step is the one above.
 """
 from __future__ import annotations
 
@@ -81,6 +87,17 @@ def resolve_pixel_loss(name, param=None):
     return kind, canon, value
 
 
+def resolve_lambda_ssim(value) -> float:
+    """TrainStep's ``lambda_ssim`` as a float; M2TError unless it is a finite number >= 0."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise _lib.M2TError(f"lambda_ssim must be a finite number >= 0, got {value!r}") from None
+    if not (math.isfinite(v) and v >= 0.0):
+        raise _lib.M2TError(f"lambda_ssim must be a finite number >= 0, got {value!r}")
+    return v
+
+
 _STREAMS: dict = {}
 
 
@@ -101,10 +118,15 @@ class TrainStep:
                  overlap_comm: bool = True, force_comm_path: bool = False, overlap_semantic: bool = True,
                  accum_steps: int = 1, max_grad_norm: Optional[float] = None, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, ema_decay: Optional[float] = None, skip_nonfinite: bool = False,
-                 track_grad_norm: bool = False, pixel_loss: str = "l1", pixel_loss_param: Optional[float] = None):
+                 track_grad_norm: bool = False, pixel_loss: str = "l1", pixel_loss_param: Optional[float] = None,
+                 lambda_ssim: float = 0.0):
         self.model = model
         # the pixel term: lambda_l1 (the reference's config key) stays its weight and l1_loss the tensor that holds it, whatever the kind
         self.set_pixel_loss(pixel_loss, pixel_loss_param)
+        # the structural term lambda_ssim * (1 - mean SSIM): 0 = off (nothing allocated, the step issues the calls it always issued)
+        self.ssim_loss = None                   # device float [1], already weighted (this rank's share of the global mean)
+        self._ssim_scratch = {}                 # (B, Hs, Ws) -> the kernel's partial-sum scratch, allocated once per plan shape
+        self.set_lambda_ssim(lambda_ssim)
         # gradient accumulation: one optimizer step consumes accum_steps equal micro-batches (forward_backward calls); the
         # gradients and the loss of calls 2..k of a cycle are added to the first call's by m2t_grad_accumulate
         if int(accum_steps) != accum_steps or int(accum_steps) < 1:
@@ -190,6 +212,38 @@ class TrainStep:
                                 "micro-batches since the last optimizer step)")
         self._pixel_kind, self.pixel_loss, self.pixel_loss_param = resolve_pixel_loss(name, param)
 
+    def set_lambda_ssim(self, value):
+        """Weight of the structural term (0 = off).  Takes effect with the next forward_backward (checkpoint.import_checkpoint
+        calls this); refused in the middle of an accumulation cycle."""
+        if getattr(self, "micro_count", 0) != 0:
+            raise _lib.M2TError(f"set_lambda_ssim in the middle of an accumulation cycle ({self.micro_count} of {self.accum_steps} "
+                                "micro-batches since the last optimizer step)")
+        self.lambda_ssim = resolve_lambda_ssim(value)
+        if self.lambda_ssim > 0.0:
+            if self.ssim_loss is None:
+                self.ssim_loss = torch.zeros(1, dtype=torch.float32, device=self.model.flat_params.device)
+        else:
+            self.ssim_loss, self._ssim_scratch = None, {}
+
+    def _ssim_loss_call(self, lib, plan, hr_img, first: bool, ws, st):
+        """m2t_ssim_loss of one (micro-)batch, behind the immediate pixel loss: adds into the materialised seed; the value is stored
+        by the first micro-batch of a cycle and added to by the others."""
+        B, _, Hs, Ws = hr_img.shape
+        key = (B, Hs, Ws)
+        if key not in self._ssim_scratch:
+            nbytes = int(lib.m2t_ssim_loss_scratch_bytes(B, 3, Hs, Ws))
+            if nbytes == 0:
+                raise _lib.M2TError(f"lambda_ssim > 0: the SR image {Hs}x{Ws} is smaller than the 11 x 11 SSIM window")
+            self._ssim_scratch[key] = torch.empty(nbytes, dtype=torch.uint8, device=hr_img.device)
+        divisor = global_divisor(B * 3 * (Hs - 10) * (Ws - 10), self.world_size, self.accum_steps)     # global number of map entries
+        _lib.check(lib.m2t_ssim_loss(plan.handle, _lib.ptr(hr_img), self.lambda_ssim, divisor, float(self.model.rgb_range),
+                                     _lib.ptr(self.ssim_loss), 0 if first else 1, _lib.ptr(self._ssim_scratch[key]), ws, st),
+                   "m2t_ssim_loss")
+
+    def _total_loss(self, with_clip: bool):
+        loss = self.l1_loss if self.ssim_loss is None else self.l1_loss + self.ssim_loss
+        return loss + self.clip_loss if with_clip else loss
+
     def _pixel_loss_call(self, lib, deferred: bool, plan, hr_img, divisor, l1_loss, ws, st):
         """The loss + seed request of one (micro-)batch.  'l1' calls the entry points it always called."""
         m = self.model
@@ -268,7 +322,11 @@ class TrainStep:
                                        float(m.rgb_range), 1, ws, st), "m2t_forward")
             # (deferred: the loss and the backward seed are produced inside m2t_backward, which follows at once -- on the bf16 x4
             #  path by the fused tail backward itself; hr_img stays alive until then)
-            self._pixel_loss_call(lib, True, plan, hr_img, divisor, l1_loss, ws, st)
+            # (lambda_ssim > 0: the materialised seed -- the immediate pixel loss, then the structural term added into it)
+            ssim = self.lambda_ssim > 0.0
+            self._pixel_loss_call(lib, not ssim, plan, hr_img, divisor, l1_loss, ws, st)
+            if ssim:
+                self._ssim_loss_call(lib, plan, hr_img, first, ws, st)
             fwd_done = torch.cuda.current_stream(lr_img.device).record_event() if (use_clip and self.overlap_semantic) else None
             _lib.check(lib.m2t_backward(plan.handle, _lib.ptr(m.flat_params), _lib.ptr(lr_img), _lib.ptr(grads),
                                         ws, st), "m2t_backward")
@@ -288,9 +346,9 @@ class TrainStep:
                 main.wait_stream(self.sem_stream)
             else:
                 self._add_clip(self.semantic_loss.batch(sr, hr_img, captions) * self.lambda_clip, first)
-            self.loss = self.l1_loss + self.clip_loss
+            self.loss = self._total_loss(True)
         else:
-            self.loss = self.l1_loss
+            self.loss = self._total_loss(False)
         return self.loss
 
     def _accumulate_micro(self, lib, first: bool, st):
@@ -328,6 +386,8 @@ class TrainStep:
                                        float(m.rgb_range), 1, ws, st), "m2t_forward")
             tot, g, origins = sl._value_and_grad(sr, hr_img, captions)
             self._pixel_loss_call(lib, False, plan, hr_img, divisor, l1_loss, ws, st)
+            if self.lambda_ssim > 0.0:
+                self._ssim_loss_call(lib, plan, hr_img, grads is self.grads, ws, st)
             g = g.contiguous()
             arr = None
             if origins is not None:
@@ -339,7 +399,7 @@ class TrainStep:
             first = grads is self.grads
             self._accumulate_micro(lib, first, st)
         self._add_clip(tot * self.lambda_clip, first)
-        self.loss = self.l1_loss + self.clip_loss
+        self.loss = self._total_loss(True)
         return self.loss
 
     def all_reduce_grads(self):
