@@ -1,4 +1,4 @@
-"""ctypes binding of libm2t.so (include/m2t.h).
+"""ctypes binding of libm2t.so (include/m2t.h, include/m2t_spectral.h).
 
 The product path has NO fallback: if the HIP library is missing, or a call fails, this
 module raises.  Build it with ``python -m m2trans_amd.build`` (hipcc, gfx950).
@@ -87,6 +87,16 @@ SIGNATURES = {
     "m2t_window_attention_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 
+# the second header, include/m2t_spectral.h (the frequency-domain entry points), bound on the same library; must list every
+# symbol that header declares.  SIGNATURES stays the table of include/m2t.h.
+SPECTRAL_SIGNATURES = {
+    "m2t_fft_loss_scratch_bytes": (C.c_size_t, [_i, _i, _i, _i]),
+    "m2t_rfft2": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "m2t_fft_loss_tensor": (_i, [_vp, _vp, _i, _i, _i, _i, _ll, _i, _f, _i, _i, _d, _vp, _vp, _i, _vp, _vp]),
+    "m2t_fft_loss": (_i, [_vp, _vp, _f, _d, _f, _i, _vp, _i, _vp, _vp, _vp]),
+}
+FFT_NORMS = {"backward": 0, "ortho": 1}     # the `norm` argument of the spectral entry points, by torch.fft's names
+
 _lib = None
 
 
@@ -108,7 +118,7 @@ def load():
     # Loaded the other way round the process ends up with two runtimes (and ours sees no device).
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -27,7 +27,9 @@ With a pixel loss other than L1 (TrainStep(pixel_loss=...)) the dict carries ``m
 beta / None}; ``import_checkpoint`` sets the TrainStep's loss from it and leaves the loss alone when the file has no such entry.
 An L1 run writes no entry: its dict is the one above.  With TrainStep(lambda_ssim > 0) the entry also carries ``"lambda_ssim"``
 (and then exists for an L1 pixel term too); ``import_checkpoint`` calls ``set_lambda_ssim`` with it.  With lambda_ssim = 0 the
-key is absent and the dict is the one described above, byte for byte.
+key is absent and the dict is the one described above, byte for byte.  TrainStep(lambda_fft > 0) adds ``"lambda_fft"`` and
+``"fft_norm"`` to the entry in the same way (``import_checkpoint`` calls ``set_lambda_fft``); with lambda_fft = 0 neither key is
+written.
 """
 from __future__ import annotations
 
@@ -64,11 +66,15 @@ def _pixel_loss(train_step):
     from .train_step import resolve_pixel_loss
     _, canon, value = resolve_pixel_loss(getattr(train_step, "pixel_loss", "l1"), getattr(train_step, "pixel_loss_param", None))
     lam = float(getattr(train_step, "lambda_ssim", 0.0) or 0.0)
-    if canon == "l1" and lam == 0.0:
+    lam_fft = float(getattr(train_step, "lambda_fft", 0.0) or 0.0)
+    if canon == "l1" and lam == 0.0 and lam_fft == 0.0:
         return None
     out = {"pixel_loss": canon, "param": value}
     if lam != 0.0:
         out["lambda_ssim"] = lam
+    if lam_fft != 0.0:
+        out["lambda_fft"] = lam_fft
+        out["fft_norm"] = str(getattr(train_step, "fft_norm", "backward"))
     return out
 
 
@@ -170,6 +176,13 @@ def import_checkpoint(ckpt: dict, model, train_step=None) -> int:
             else:
                 from .train_step import resolve_lambda_ssim
                 train_step.lambda_ssim = resolve_lambda_ssim(ml["lambda_ssim"])
+        if "lambda_fft" in ml:
+            if hasattr(train_step, "set_lambda_fft"):
+                train_step.set_lambda_fft(ml["lambda_fft"], ml.get("fft_norm"))
+            else:
+                from .train_step import resolve_fft_norm, resolve_lambda_fft
+                train_step.lambda_fft = resolve_lambda_fft(ml["lambda_fft"])
+                train_step.fft_norm = resolve_fft_norm(ml.get("fft_norm", "backward"))
     opt = ckpt.get("optimizer_state_dict") or {}
     sch = ckpt.get("scheduler_state_dict")
     if not opt.get("state") and not opt.get("param_groups") and sch is None:

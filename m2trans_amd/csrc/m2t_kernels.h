@@ -333,3 +333,12 @@ int launch_add_output_grad(const float* pre, const float* g, float* gpre, int B,
 size_t ssim_loss_scratch_bytes(int B, int C, int H, int W);
 int launch_ssim_loss(const float* x, const float* y, int B, int C, int H, int W, long long xs_img, int xs_row, float R, int clamp,
                      double scale, float* gx_add, float* loss_out, int accumulate, void* scratch, hipStream_t st);
+// ---- k_fft_loss.hip (the L1 loss on the coefficients of a 2-D real FFT and its gradient: m2t_fft_loss_tensor / m2t_fft_loss) ----------
+// x [B][C][H][W] with image stride xs_img, channel stride xs_img / C, row stride xs_row; y contiguous; gx_add (or nullptr) has x's strides:
+// gx_add[q] += scale * d sum(|Re D| + |Im D|) / dx[q] (through the clamp mask when clamp); loss_out = (accumulate ? loss_out : 0) + scale * sum.
+// norm 0 = "backward", 1 = "ortho".  scratch: fft_loss_scratch_bytes(B, C, H, W) bytes (0 for an unsupported size).  Arguments are
+// checked by the callers.
+bool fft_loss_size_supported(int H, int W);
+size_t fft_loss_scratch_bytes(int B, int C, int H, int W);
+int launch_fft_loss(const float* x, const float* y, int B, int C, int H, int W, long long xs_img, int xs_row, float R, int clamp, int norm,
+                    double scale, float* gx_add, float* loss_out, int accumulate, void* scratch, hipStream_t st);

@@ -527,3 +527,68 @@ class SSIMLoss(nn.Module):
 
     def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         return ssim_loss(x, y, self.data_range)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The frequency-domain term: an L1 on the coefficients of rfft2 (the reference imports torch.fft, losses.py:5, and never calls it;
+# MIMO-UNet's F.l1_loss(view_as_real(rfft2(x)), view_as_real(rfft2(y)))).  Value and gradient are HIP (m2t_fft_loss_tensor of
+# include/m2t_spectral.h, k_fft_loss.hip); there is no torch fallback.
+# ---------------------------------------------------------------------------------------------------------------
+class _FFTLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, data_range, norm):
+        lib = _lib.load()
+        xc, yc = x.detach().contiguous().float(), y.detach().contiguous().float()
+        B, Cn, H, W = xc.shape
+        nbytes = lib.m2t_fft_loss_scratch_bytes(B, Cn, H, W)
+        if nbytes == 0:
+            raise M2TError(f"fft_loss: no scratch size for [{B},{Cn},{H},{W}] (B * C must be 1 .. 65535)")
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=xc.device)
+        out = torch.empty(1, dtype=torch.float32, device=xc.device)
+        # value and gradient come from one call; the gradient of the MEAN, scaled by the upstream gradient in backward
+        grad = torch.zeros_like(xc) if ctx.needs_input_grad[0] else None
+        n = 2 * B * Cn * H * (W // 2 + 1)
+        with torch.cuda.device(xc.device):
+            _lib.check(lib.m2t_fft_loss_tensor(_lib.ptr(xc), _lib.ptr(yc), B, Cn, H, W, Cn * H * W, W, float(data_range), 0,
+                                               _lib.FFT_NORMS[norm], 1.0 / n, _lib.ptr(grad), _lib.ptr(out), 0, _lib.ptr(scratch),
+                                               _lib.stream_ptr()), "m2t_fft_loss_tensor")
+        ctx.grad = grad
+        ctx.x_dtype = x.dtype
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        return (ctx.grad * g).to(ctx.x_dtype), None, None, None
+
+
+def fft_loss(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0, norm: str = "backward") -> torch.Tensor:
+    """``F.l1_loss(view_as_real(rfft2(x / data_range, norm=norm)), view_as_real(rfft2(y / data_range, norm=norm)))`` as ONE transform
+    of the difference, for device tensors [B,C,H,W] (inputs NOT clamped to the data range); differentiable with respect to ``x``
+    only.  H and W must be even, 8 .. 2048 and of the form 2^a * 3^b.  The imaginary part of the four self-conjugate bins is
+    exactly 0 (torch leaves rounding noise there and takes its sign); sign(0) = 0.  fp32 butterflies, fp64 sums."""
+    from .train_step import FFT_SIZE_RULE, fft_size_supported, resolve_fft_norm
+    if x.dim() != 4 or x.shape != y.shape:
+        raise M2TError(f"fft_loss: expected two [B,C,H,W] tensors of equal shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if not (x.is_cuda and y.is_cuda):
+        raise M2TError("fft_loss needs HIP device tensors (there is no host implementation)")
+    if y.requires_grad:
+        raise M2TError("fft_loss gives the gradient with respect to x only: y must not require grad (detach it)")
+    if not (float(data_range) > 0.0):
+        raise M2TError(f"fft_loss: data_range must be > 0, got {data_range!r}")
+    H, W = int(x.shape[2]), int(x.shape[3])
+    if not (fft_size_supported(H) and fft_size_supported(W)):
+        raise M2TError(f"fft_loss: image size {H}x{W} is not supported by the HIP transform (height and width must be {FFT_SIZE_RULE})")
+    return _FFTLossFn.apply(x, y, float(data_range), resolve_fft_norm(norm))
+
+
+class FFTLoss(nn.Module):
+    """``fft_loss`` as a module."""
+
+    def __init__(self, data_range: float = 1.0, norm: str = "backward"):
+        super().__init__()
+        from .train_step import resolve_fft_norm
+        self.data_range = float(data_range)
+        self.norm = resolve_fft_norm(norm)
+
+    def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        return fft_loss(x, y, self.data_range, self.norm)

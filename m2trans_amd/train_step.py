@@ -35,6 +35,13 @@ epoch by SSIM, utils.py:232-234): ``lambda_ssim * (1 - mean SSIM)`` per RGB chan
 piq.ssim(downsample=False) form -- piq.SSIMLoss's default ``downsample=True`` pooling is NOT applied -- with its gradient in HIP
 (m2t_ssim_loss, fp64 inside).  A step with lambda_ssim > 0 takes the MATERIALISED seed (immediate pixel loss, then m2t_ssim_loss adds
 into it): the seed fused into the x4 tail backward does not apply.  With lambda_ssim = 0 (the default) the step is the one above.
+
+Frequency-domain term (``lambda_fft``, ``fft_norm``; the reference imports torch.fft in losses.py:5 and never calls it -- the term
+is MIMO-UNet's L1 on the Fourier coefficients): ``lambda_fft * mean(|Re D|, |Im D|)`` with ``D = rfft2(clamp(sr) / R - hr / R,
+norm=fft_norm)`` per RGB channel, value and gradient in HIP (m2t_fft_loss of include/m2t_spectral.h: a mixed-radix Stockham FFT in
+LDS; SR height and width even, 8 .. 2048, of the form 2^a 3^b).  Like lambda_ssim it takes the MATERIALISED seed, and the calls
+run in the order pixel -> SSIM (if on) -> FFT -> backward.  With lambda_fft = 0 (the default) nothing is allocated and the step
+issues the calls it issued before.
 """
 from __future__ import annotations
 
@@ -98,6 +105,40 @@ def resolve_lambda_ssim(value) -> float:
     return v
 
 
+def resolve_lambda_fft(value) -> float:
+    """TrainStep's ``lambda_fft`` as a float; M2TError unless it is a finite number >= 0."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise _lib.M2TError(f"lambda_fft must be a finite number >= 0, got {value!r}") from None
+    if not (math.isfinite(v) and v >= 0.0):
+        raise _lib.M2TError(f"lambda_fft must be a finite number >= 0, got {value!r}")
+    return v
+
+
+def resolve_fft_norm(name) -> str:
+    """TrainStep's ``fft_norm``: 'backward' (torch.fft's default, no scaling) or 'ortho' (1 / sqrt(H W)); M2TError otherwise."""
+    key = name.lower() if isinstance(name, str) else name
+    if not isinstance(key, str) or key not in _lib.FFT_NORMS:
+        raise _lib.M2TError(f"fft_norm must be one of {sorted(_lib.FFT_NORMS)}, got {name!r}")
+    return key
+
+
+FFT_SIZE_RULE = "even, 8 .. 2048 and of the form 2^a * 3^b"
+
+
+def fft_size_supported(n: int) -> bool:
+    """The sizes the HIP transform takes along one axis (the rule of include/m2t_spectral.h, decided on the host)."""
+    n = int(n)
+    if n < 8 or n > 2048 or n % 2:
+        return False
+    while n % 2 == 0:
+        n //= 2
+    while n % 3 == 0:
+        n //= 3
+    return n == 1
+
+
 _STREAMS: dict = {}
 
 
@@ -119,7 +160,7 @@ class TrainStep:
                  accum_steps: int = 1, max_grad_norm: Optional[float] = None, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, ema_decay: Optional[float] = None, skip_nonfinite: bool = False,
                  track_grad_norm: bool = False, pixel_loss: str = "l1", pixel_loss_param: Optional[float] = None,
-                 lambda_ssim: float = 0.0):
+                 lambda_ssim: float = 0.0, lambda_fft: float = 0.0, fft_norm: str = "backward"):
         self.model = model
         # the pixel term: lambda_l1 (the reference's config key) stays its weight and l1_loss the tensor that holds it, whatever the kind
         self.set_pixel_loss(pixel_loss, pixel_loss_param)
@@ -127,6 +168,11 @@ class TrainStep:
         self.ssim_loss = None                   # device float [1], already weighted (this rank's share of the global mean)
         self._ssim_scratch = {}                 # (B, Hs, Ws) -> the kernel's partial-sum scratch, allocated once per plan shape
         self.set_lambda_ssim(lambda_ssim)
+        # the frequency-domain term lambda_fft * mean |rfft2(sr - hr)|: 0 = off (nothing allocated, no call more)
+        self.fft_loss = None                    # device float [1], already weighted
+        self._fft_scratch = {}                  # (B, Hs, Ws) -> the half spectrum + partial sums, allocated once per plan shape
+        self.fft_norm = "backward"
+        self.set_lambda_fft(lambda_fft, fft_norm)
         # gradient accumulation: one optimizer step consumes accum_steps equal micro-batches (forward_backward calls); the
         # gradients and the loss of calls 2..k of a cycle are added to the first call's by m2t_grad_accumulate
         if int(accum_steps) != accum_steps or int(accum_steps) < 1:
@@ -240,8 +286,51 @@ class TrainStep:
                                      _lib.ptr(self.ssim_loss), 0 if first else 1, _lib.ptr(self._ssim_scratch[key]), ws, st),
                    "m2t_ssim_loss")
 
+    def set_lambda_fft(self, value, norm=None):
+        """Weight of the frequency-domain term (0 = off) and, when given, its normalisation ('backward' / 'ortho').  Takes effect
+        with the next forward_backward (checkpoint.import_checkpoint calls this); refused in the middle of an accumulation cycle."""
+        if getattr(self, "micro_count", 0) != 0:
+            raise _lib.M2TError(f"set_lambda_fft in the middle of an accumulation cycle ({self.micro_count} of {self.accum_steps} "
+                                "micro-batches since the last optimizer step)")
+        lam = resolve_lambda_fft(value)
+        if norm is not None:
+            self.fft_norm = resolve_fft_norm(norm)
+        self.lambda_fft = lam
+        if self.lambda_fft > 0.0:
+            if self.fft_loss is None:
+                self.fft_loss = torch.zeros(1, dtype=torch.float32, device=self.model.flat_params.device)
+        else:
+            self.fft_loss, self._fft_scratch = None, {}
+
+    def _fft_scratch_for(self, lib, hr_img):
+        """The scratch of the frequency-domain term for this (micro-)batch shape, allocated once; an SR size the HIP transform does
+        not take is refused here, on the host, before anything is launched."""
+        B, _, Hs, Ws = hr_img.shape
+        key = (B, Hs, Ws)
+        if key not in self._fft_scratch:
+            if not (fft_size_supported(Hs) and fft_size_supported(Ws)):
+                raise _lib.M2TError(f"lambda_fft > 0: the SR image {Hs}x{Ws} is not supported by the HIP transform (height and width "
+                                    f"must be {FFT_SIZE_RULE})")
+            nbytes = int(lib.m2t_fft_loss_scratch_bytes(B, 3, Hs, Ws))
+            if nbytes == 0:
+                raise _lib.M2TError(f"lambda_fft > 0: no scratch size for a batch of {B} SR images {Hs}x{Ws} (B * 3 <= 65535; height "
+                                    f"and width {FFT_SIZE_RULE})")
+            self._fft_scratch[key] = torch.empty(nbytes, dtype=torch.uint8, device=hr_img.device)
+        return self._fft_scratch[key]
+
+    def _fft_loss_call(self, lib, plan, hr_img, first: bool, ws, st):
+        """m2t_fft_loss of one (micro-)batch, behind the immediate pixel loss (and the structural term): adds into the materialised
+        seed; the value is stored by the first micro-batch of a cycle and added to by the others."""
+        B, _, Hs, Ws = hr_img.shape
+        divisor = global_divisor(B * 3 * Hs * (Ws // 2 + 1) * 2, self.world_size, self.accum_steps)     # global number of reals
+        _lib.check(lib.m2t_fft_loss(plan.handle, _lib.ptr(hr_img), self.lambda_fft, divisor, float(self.model.rgb_range),
+                                    _lib.FFT_NORMS[self.fft_norm], _lib.ptr(self.fft_loss), 0 if first else 1,
+                                    _lib.ptr(self._fft_scratch_for(lib, hr_img)), ws, st), "m2t_fft_loss")
+
     def _total_loss(self, with_clip: bool):
         loss = self.l1_loss if self.ssim_loss is None else self.l1_loss + self.ssim_loss
+        if self.fft_loss is not None:
+            loss = loss + self.fft_loss
         return loss + self.clip_loss if with_clip else loss
 
     def _pixel_loss_call(self, lib, deferred: bool, plan, hr_img, divisor, l1_loss, ws, st):
@@ -304,6 +393,8 @@ class TrainStep:
         B = lr_img.shape[0]
         if tuple(hr_img.shape) != (B, 3, lr_img.shape[2] * m.scale, lr_img.shape[3] * m.scale):
             raise _lib.M2TError("hr shape must be [B,3,H*scale,W*scale]")
+        if self.lambda_fft > 0.0:
+            self._fft_scratch_for(lib, hr_img)      # (refuses an SR size outside the transform's rule before any launch)
         divisor = global_divisor(hr_img.numel(), self.world_size, self.accum_steps)      # global mean (equal shards, equal micro-batches)
         use_clip = self.semantic_loss is not None and self.lambda_clip > 0 and captions is not None
         # (micro-batches 2..k of a cycle: a second gradient buffer and a second loss slot, added to the first ones below)
@@ -323,10 +414,13 @@ class TrainStep:
             # (deferred: the loss and the backward seed are produced inside m2t_backward, which follows at once -- on the bf16 x4
             #  path by the fused tail backward itself; hr_img stays alive until then)
             # (lambda_ssim > 0: the materialised seed -- the immediate pixel loss, then the structural term added into it)
-            ssim = self.lambda_ssim > 0.0
-            self._pixel_loss_call(lib, not ssim, plan, hr_img, divisor, l1_loss, ws, st)
+            # (lambda_fft > 0: the same route; the frequency-domain term goes last: pixel -> SSIM -> FFT -> backward)
+            ssim, fft = self.lambda_ssim > 0.0, self.lambda_fft > 0.0
+            self._pixel_loss_call(lib, not (ssim or fft), plan, hr_img, divisor, l1_loss, ws, st)
             if ssim:
                 self._ssim_loss_call(lib, plan, hr_img, first, ws, st)
+            if fft:
+                self._fft_loss_call(lib, plan, hr_img, first, ws, st)
             fwd_done = torch.cuda.current_stream(lr_img.device).record_event() if (use_clip and self.overlap_semantic) else None
             _lib.check(lib.m2t_backward(plan.handle, _lib.ptr(m.flat_params), _lib.ptr(lr_img), _lib.ptr(grads),
                                         ws, st), "m2t_backward")
@@ -388,6 +482,8 @@ class TrainStep:
             self._pixel_loss_call(lib, False, plan, hr_img, divisor, l1_loss, ws, st)
             if self.lambda_ssim > 0.0:
                 self._ssim_loss_call(lib, plan, hr_img, grads is self.grads, ws, st)
+            if self.lambda_fft > 0.0:
+                self._fft_loss_call(lib, plan, hr_img, grads is self.grads, ws, st)
             g = g.contiguous()
             arr = None
             if origins is not None:
