@@ -1,4 +1,4 @@
-"""ctypes binding of libm2t.so (include/m2t.h, include/m2t_spectral.h).
+"""ctypes binding of libm2t.so (include/m2t.h, include/m2t_spectral.h, include/m2t_resize.h).
 
 The product path has NO fallback: if the HIP library is missing, or a call fails, this
 module raises.  Build it with ``python -m m2trans_amd.build`` (hipcc, gfx950).
@@ -97,6 +97,13 @@ SPECTRAL_SIGNATURES = {
 }
 FFT_NORMS = {"backward": 0, "ortho": 1}     # the `norm` argument of the spectral entry points, by torch.fft's names
 
+# the third header, include/m2t_resize.h (the bicubic resampler), bound on the same library; must list every symbol that header
+# declares.  The two tables above stay as they are.
+RESIZE_SIGNATURES = {
+    "m2t_imresize_u8": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp]),
+    "m2t_imresize_f32": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _f, _vp]),
+}
+
 _lib = None
 
 
@@ -118,7 +125,7 @@ def load():
     # Loaded the other way round the process ends up with two runtimes (and ours sees no device).
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -32,15 +32,29 @@ def _load_rgb(npy_name: str, png_name: str) -> np.ndarray:
     return np.asarray(Image.open(png_name).convert("RGB"))
 
 
+def _modcrop_hr(hr: np.ndarray, scale: int, colors: int) -> np.ndarray:
+    """HR of a pair whose LR half is synthesised: the top-left multiple-of-scale part (the crop datas/benchmark.py:62-72 applies)."""
+    if not isinstance(hr, np.ndarray) or hr.dtype != np.uint8 or hr.ndim != 3 or hr.shape[2] != colors:
+        raise _lib.M2TError(f"images must be uint8 [H,W,{colors}], got {getattr(hr, 'dtype', type(hr))} {getattr(hr, 'shape', '')}")
+    if hr.shape[0] < scale or hr.shape[1] < scale:
+        raise _lib.M2TError(f"HR image {hr.shape} is smaller than one LR pixel at x{scale}")
+    from .resize import modcrop
+    return np.ascontiguousarray(modcrop(hr, scale))
+
+
 class US1K:
     """datas/us1k.py:39-170 for `train=True, colors=3`, with the cache in device memory.
 
-    `images`: optional list of (hr, lr) uint8 HWC arrays used instead of the folders (synthetic data, tests)."""
+    `images`: optional list of (hr, lr) uint8 HWC arrays used instead of the folders (synthetic data, tests).
+
+    From HR alone: with `LR_folder=None`, or an `images` entry `(hr, None)`, HR is mod-cropped to a multiple of `scale` on the host
+    and uploaded, and the LR image is computed on the device straight into its slot of `lr_pool` (one m2t_imresize_u8 launch per
+    image: MATLAB-style bicubic, resize.py); no LR cache is read or written.  Everything downstream is the same."""
 
     def __init__(self, HR_folder: Optional[str] = None, LR_folder: Optional[str] = None, CACHE_folder: Optional[str] = None,
                  train: bool = True, augment: bool = True, scale: int = 2, colors: int = 3, patch_size: int = 96,
                  repeat: int = 168, add_noise: bool = False, cutout: bool = False, device="cuda",
-                 images: Optional[Sequence[Tuple[np.ndarray, np.ndarray]]] = None):
+                 images: Optional[Sequence[Tuple[np.ndarray, Optional[np.ndarray]]]] = None):
         if colors != 3:
             raise _lib.M2TError("US1K (MI355X build): only colors=3 is built (configs/M2Trans_x4.yml:5)")
         if add_noise or cutout:
@@ -54,7 +68,14 @@ class US1K:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.M2TError("US1K (MI355X build) keeps its cache in HBM: a HIP device is required")
-        if images is None:
+        if images is None and LR_folder is None:
+            start, end = (1, 1001) if train else (801, 901)                       # datas/us1k.py:74-79
+            images = []
+            for i in range(start, end):
+                idx = str(i).zfill(4)
+                npy = os.path.join(CACHE_folder, "us1k_hr", "rgb", idx + ".npy") if CACHE_folder is not None else ""
+                images.append((_load_rgb(npy, os.path.join(HR_folder, idx + ".png")), None))
+        elif images is None:
             start, end = (1, 1001) if train else (801, 901)                       # datas/us1k.py:74-79
             hr_dir = os.path.join(CACHE_folder, "us1k_hr", "rgb")
             lr_dir = os.path.join(CACHE_folder, "us1k_lr_x{}".format(scale), "rgb")
@@ -65,6 +86,9 @@ class US1K:
                 lr = _load_rgb(os.path.join(lr_dir, f"{idx}x{scale}.npy"),
                                os.path.join(LR_folder, f"X{scale}", f"{idx}x{scale}.png"))
                 images.append((hr, lr))
+        synth = [lr is None for _, lr in images]
+        if any(synth):
+            images = [(_modcrop_hr(hr, scale, colors), lr) if lr is None else (hr, lr) for hr, lr in images]
         self.nums_trainset = len(images)
         if self.nums_trainset == 0:
             raise _lib.M2TError("empty dataset")
@@ -73,15 +97,26 @@ class US1K:
         lr_off = hr_off = 0
         for hr, lr in images:
             for a in (hr, lr):
-                if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != colors:
+                if a is not None and (a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != colors):
                     raise _lib.M2TError(f"cache entries must be uint8 [H,W,{colors}], got {a.dtype} {a.shape}")
-            if train and (lr.shape[0] < lp or lr.shape[1] < lp or hr.shape[0] < lr.shape[0] * scale or hr.shape[1] < lr.shape[1] * scale):
-                raise _lib.M2TError(f"image pair {lr.shape} / {hr.shape} too small for patch_size {patch_size} at x{scale}")
-            self._geo.append((lr_off, hr_off, lr.shape[0], lr.shape[1], hr.shape[0], hr.shape[1]))
-            lr_off += lr.size
+            lr_shape = lr.shape if lr is not None else (hr.shape[0] // scale, hr.shape[1] // scale, colors)
+            if train and (lr_shape[0] < lp or lr_shape[1] < lp or hr.shape[0] < lr_shape[0] * scale or hr.shape[1] < lr_shape[1] * scale):
+                raise _lib.M2TError(f"image pair {lr_shape} / {hr.shape} too small for patch_size {patch_size} at x{scale}")
+            self._geo.append((lr_off, hr_off, lr_shape[0], lr_shape[1], hr.shape[0], hr.shape[1]))
+            lr_off += lr_shape[0] * lr_shape[1] * lr_shape[2]
             hr_off += hr.size
-        self.lr_pool = torch.from_numpy(np.concatenate([np.ascontiguousarray(lr).reshape(-1) for _, lr in images])).to(self.device)
         self.hr_pool = torch.from_numpy(np.concatenate([np.ascontiguousarray(hr).reshape(-1) for hr, _ in images])).to(self.device)
+        if not any(synth):
+            self.lr_pool = torch.from_numpy(np.concatenate([np.ascontiguousarray(lr).reshape(-1) for _, lr in images])).to(self.device)
+        else:
+            from .resize import imresize_u8
+            self.lr_pool = torch.empty(lr_off, dtype=torch.uint8, device=self.device)
+            for (hr, lr), (lo, ho, lh, lw, hh, hw) in zip(images, self._geo):
+                slot = self.lr_pool[lo:lo + lh * lw * colors]
+                if lr is None:
+                    imresize_u8(self.hr_pool[ho:ho + hh * hw * colors].view(hh, hw, colors), scale, out=slot)
+                else:
+                    slot.copy_(torch.from_numpy(np.ascontiguousarray(lr).reshape(-1)))
 
     def __len__(self) -> int:                                                   # datas/us1k.py:140-144
         return self.nums_trainset * self.repeat if self.train else self.nums_trainset
@@ -130,7 +165,8 @@ class Benchmark:
     """datas/benchmark.py:17-72 with the images resident in HBM: `len()`, `ds[i] -> (lr [1,3,h,w], hr [1,3,h*s,w*s],
     name)` float32 in [0,1] on the device (the reference's DataLoader adds the batch dimension of 1), HR cropped to the
     LR size x scale, bit-identical to the reference's tensors.  `images`: optional list of (hr, lr, name) uint8 HWC
-    arrays instead of the folders."""
+    arrays instead of the folders.  With `LR_folder=None`, or an entry `(hr, None, name)`, the LR image is computed on the
+    device from the mod-cropped HR (m2t_imresize_u8: MATLAB-style bicubic, resize.py)."""
 
     def __init__(self, HR_folder: Optional[str] = None, LR_folder: Optional[str] = None, scale: int = 2, colors: int = 3,
                  device="cuda", images=None):
@@ -144,13 +180,21 @@ class Benchmark:
             images = []
             for tag in os.listdir(HR_folder):                                 # datas/benchmark.py:33-43
                 ext = ".png" if "US1K_23" in HR_folder else ".jpg"
-                lr_name = os.path.join(LR_folder, f"X{scale}", tag.replace(ext, f"x{scale}{ext}"))
                 hr = np.asarray(Image.open(os.path.join(HR_folder, tag)).convert("RGB"))
+                if LR_folder is None:
+                    images.append((hr, None, tag))
+                    continue
+                lr_name = os.path.join(LR_folder, f"X{scale}", tag.replace(ext, f"x{scale}{ext}"))
                 lr = np.asarray(Image.open(lr_name).convert("RGB"))
                 images.append((hr, lr, tag))
         self.img_name = [n for _, _, n in images]
         self._items = []
         for hr, lr, _ in images:
+            if lr is None:
+                from .resize import imresize_u8
+                hr_dev = torch.from_numpy(_modcrop_hr(hr, scale, colors)).to(self.device)
+                self._items.append((hr_dev, imresize_u8(hr_dev, scale)))
+                continue
             for a in (hr, lr):
                 if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != colors:
                     raise _lib.M2TError(f"images must be uint8 [H,W,{colors}], got {a.dtype} {a.shape}")

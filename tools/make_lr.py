@@ -1,0 +1,72 @@
+"""Write the bicubic LR folder of an HR folder, in the reference's layout, with the resize done on the device.
+
+    python tools/make_lr.py --hr DIR --out DIR --scale {2,3,4} [--npy-cache DIR]
+
+For every image ``<name>.<ext>`` (png / jpg / jpeg / bmp) of --hr: the top-left multiple-of-scale part is resized by
+m2t_imresize_u8 (MATLAB-style imresize(..., 'bicubic'), include/m2t_resize.h) and written to ``<out>/X{s}/<name>x{s}.png`` -- what
+datas/us1k.py:84 and datas/benchmark.py read as ``<LR_folder>/X{s}/...``.  With --npy-cache the same array is also saved as
+``<cache>/us1k_lr_x{s}/rgb/<name>x{s}.npy``, the reference's LR cache (datas/us1k.py:90-91,133-136), so that the reference's own
+loaders and this library's folder path (datas.US1K(HR_folder, LR_folder, CACHE_folder)) both consume the result.  PIL does the
+file I/O only.  Prints one JSON line.  Needs a device: without one it fails.  The output is always PNG: a lossy format would
+re-degrade the LR image.  Consequence for a .jpg HR folder: the reference's benchmark loader and this library's
+`datas.Benchmark(HR_folder, LR_folder)` look for ``<name>x{s}.jpg`` there (datas/benchmark.py:33-43; .png only when the HR path
+contains "US1K_23") and do not find these files; use `datas.Benchmark(HR_folder, None)`, which synthesises the same LR images."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp")
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--hr", required=True, help="folder of HR images")
+    ap.add_argument("--out", required=True, help="LR folder to write (X{s}/ is created below it)")
+    ap.add_argument("--scale", type=int, required=True, choices=[2, 3, 4])
+    ap.add_argument("--npy-cache", default=None, help="cache folder: also write us1k_lr_x{s}/rgb/<name>x{s}.npy")
+    return ap.parse_args(argv)
+
+
+def lr_paths(args, tag: str):
+    """(png path, npy path or None) of one HR file name."""
+    stem = os.path.splitext(tag)[0]
+    s = args.scale
+    png = os.path.join(args.out, f"X{s}", f"{stem}x{s}.png")
+    npy = os.path.join(args.npy_cache, f"us1k_lr_x{s}", "rgb", f"{stem}x{s}.npy") if args.npy_cache else None
+    return png, npy
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    import numpy as np
+    import torch
+    from PIL import Image
+    if not torch.cuda.is_available():
+        raise SystemExit("make_lr.py needs a HIP device: the resize runs there and has no host fallback")
+    from m2trans_amd.resize import imresize_u8, modcrop
+    tags = sorted(t for t in os.listdir(args.hr) if t.lower().endswith(EXTENSIONS))
+    if not tags:
+        raise SystemExit(f"no image in {args.hr}")
+    os.makedirs(os.path.join(args.out, f"X{args.scale}"), exist_ok=True)
+    if args.npy_cache:
+        os.makedirs(os.path.join(args.npy_cache, f"us1k_lr_x{args.scale}", "rgb"), exist_ok=True)
+    for tag in tags:
+        hr = modcrop(np.asarray(Image.open(os.path.join(args.hr, tag)).convert("RGB")), args.scale)
+        lr = imresize_u8(torch.from_numpy(np.ascontiguousarray(hr)).cuda(), args.scale).cpu().numpy()
+        png, npy = lr_paths(args, tag)
+        Image.fromarray(lr, "RGB").save(png)
+        if npy:
+            np.save(npy, lr)
+    print(json.dumps({"images": len(tags), "scale": args.scale, "out": os.path.join(args.out, f"X{args.scale}"),
+                      "npy_cache": os.path.join(args.npy_cache, f"us1k_lr_x{args.scale}", "rgb") if args.npy_cache else None}))
+
+
+if __name__ == "__main__":
+    main()
