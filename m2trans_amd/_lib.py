@@ -1,4 +1,4 @@
-"""ctypes binding of libm2t.so (include/m2t.h, include/m2t_spectral.h, include/m2t_resize.h).
+"""ctypes binding of libm2t.so (include/m2t.h, include/m2t_spectral.h, include/m2t_resize.h, include/m2t_msssim.h).
 
 The product path has NO fallback: if the HIP library is missing, or a call fails, this
 module raises.  Build it with ``python -m m2trans_amd.build`` (hipcc, gfx950).
@@ -104,6 +104,17 @@ RESIZE_SIGNATURES = {
     "m2t_imresize_f32": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _f, _vp]),
 }
 
+# the fourth header, include/m2t_msssim.h (the multi-scale structural loss term), bound on the same library; must list every symbol
+# that header declares.  The three tables above stay as they are.
+MSSSIM_SIGNATURES = {
+    "m2t_msssim_loss_scratch_bytes": (C.c_size_t, [_i, _i, _i, _i]),
+    "m2t_msssim_loss_scratch_offset": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
+    "m2t_msssim_loss_tensor": (_i, [_vp, _vp, _i, _i, _i, _i, _ll, _i, _f, _i, _d, _vp, _vp, _vp, _i, _vp, _vp]),
+    "m2t_msssim_loss": (_i, [_vp, _vp, _f, _d, _f, _vp, _i, _vp, _vp, _vp]),
+}
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)     # the five level weights of the term
+MSSSIM_MIN_SIDE = 161                                          # min(H, W) > 160 = (11 - 1) * 2^4
+
 _lib = None
 
 
@@ -125,7 +136,8 @@ def load():
     # Loaded the other way round the process ends up with two runtimes (and ours sees no device).
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) \
+            + list(MSSSIM_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

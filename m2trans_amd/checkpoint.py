@@ -29,7 +29,8 @@ An L1 run writes no entry: its dict is the one above.  With TrainStep(lambda_ssi
 (and then exists for an L1 pixel term too); ``import_checkpoint`` calls ``set_lambda_ssim`` with it.  With lambda_ssim = 0 the
 key is absent and the dict is the one described above, byte for byte.  TrainStep(lambda_fft > 0) adds ``"lambda_fft"`` and
 ``"fft_norm"`` to the entry in the same way (``import_checkpoint`` calls ``set_lambda_fft``); with lambda_fft = 0 neither key is
-written.
+written.  TrainStep(lambda_msssim > 0) adds ``"lambda_msssim"`` in the same way (``import_checkpoint`` calls ``set_lambda_msssim``);
+with lambda_msssim = 0 the key is absent.
 """
 from __future__ import annotations
 
@@ -67,11 +68,14 @@ def _pixel_loss(train_step):
     _, canon, value = resolve_pixel_loss(getattr(train_step, "pixel_loss", "l1"), getattr(train_step, "pixel_loss_param", None))
     lam = float(getattr(train_step, "lambda_ssim", 0.0) or 0.0)
     lam_fft = float(getattr(train_step, "lambda_fft", 0.0) or 0.0)
-    if canon == "l1" and lam == 0.0 and lam_fft == 0.0:
+    lam_ms = float(getattr(train_step, "lambda_msssim", 0.0) or 0.0)
+    if canon == "l1" and lam == 0.0 and lam_fft == 0.0 and lam_ms == 0.0:
         return None
     out = {"pixel_loss": canon, "param": value}
     if lam != 0.0:
         out["lambda_ssim"] = lam
+    if lam_ms != 0.0:
+        out["lambda_msssim"] = lam_ms
     if lam_fft != 0.0:
         out["lambda_fft"] = lam_fft
         out["fft_norm"] = str(getattr(train_step, "fft_norm", "backward"))
@@ -176,6 +180,12 @@ def import_checkpoint(ckpt: dict, model, train_step=None) -> int:
             else:
                 from .train_step import resolve_lambda_ssim
                 train_step.lambda_ssim = resolve_lambda_ssim(ml["lambda_ssim"])
+        if "lambda_msssim" in ml:
+            if hasattr(train_step, "set_lambda_msssim"):
+                train_step.set_lambda_msssim(ml["lambda_msssim"])
+            else:
+                from .train_step import resolve_lambda_msssim
+                train_step.lambda_msssim = resolve_lambda_msssim(ml["lambda_msssim"])
         if "lambda_fft" in ml:
             if hasattr(train_step, "set_lambda_fft"):
                 train_step.set_lambda_fft(ml["lambda_fft"], ml.get("fft_norm"))

@@ -331,8 +331,18 @@ int launch_add_output_grad(const float* pre, const float* g, float* gpre, int B,
 // gx_add[q] += -scale * d sum(S) / dx[q] (through the clamp mask when clamp); loss_out = (accumulate ? loss_out : 0) + scale * sum(1 - S).
 // scratch: ssim_loss_scratch_bytes(B, C, H, W) bytes (0 when H or W < 11).  Arguments are checked by the callers.
 size_t ssim_loss_scratch_bytes(int B, int C, int H, int W);
+void ssim_loss_taps(double* g11);      // the 11 taps of the window (the fp32 taps torch builds, widened), also those of k_msssim_loss.hip
 int launch_ssim_loss(const float* x, const float* y, int B, int C, int H, int W, long long xs_img, int xs_row, float R, int clamp,
                      double scale, float* gx_add, float* loss_out, int accumulate, void* scratch, hipStream_t st);
+// ---- k_msssim_loss.hip (the 1 - MS-SSIM loss term and its gradient: m2t_msssim_loss_tensor / m2t_msssim_loss) ----------
+// The strides, gx_add, loss_out and accumulate of launch_ssim_loss; loss_out = (accumulate ? loss_out : 0) + scale * sum_bc (1 - M_bc);
+// per_channel_out (or nullptr): double [B*C] = M_bc.  scratch: msssim_loss_scratch_bytes(B, C, H, W) bytes (0 when min(H, W) <= 160 or
+// B * C is outside 1 .. 65535).  Arguments are checked by the callers.
+bool msssim_loss_size_supported(int H, int W);
+size_t msssim_loss_scratch_bytes(int B, int C, int H, int W);
+int launch_msssim_loss(const float* x, const float* y, int B, int C, int H, int W, long long xs_img, int xs_row, float R, int clamp,
+                       double scale, float* gx_add, float* loss_out, double* per_channel_out, int accumulate, void* scratch,
+                       hipStream_t st);
 // ---- k_fft_loss.hip (the L1 loss on the coefficients of a 2-D real FFT and its gradient: m2t_fft_loss_tensor / m2t_fft_loss) ----------
 // x [B][C][H][W] with image stride xs_img, channel stride xs_img / C, row stride xs_row; y contiguous; gx_add (or nullptr) has x's strides:
 // gx_add[q] += scale * d sum(|Re D| + |Im D|) / dx[q] (through the clamp mask when clamp); loss_out = (accumulate ? loss_out : 0) + scale * sum.

@@ -530,6 +530,77 @@ class SSIMLoss(nn.Module):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# The multi-scale structural term: 1 - MS-SSIM (the reference imports MultiScaleSSIMLoss from piq, losses.py:8).  Value and gradient
+# are HIP (m2t_msssim_loss_tensor of include/m2t_msssim.h, k_msssim_loss.hip); there is no torch fallback.
+# ---------------------------------------------------------------------------------------------------------------
+def _msssim_call(x, y, data_range, want_grad, want_per_channel):
+    """(loss [1] float32, gradient of the mean or None, M_bc [B*C] float64 or None) of device tensors [B,C,H,W]."""
+    lib = _lib.load()
+    xc, yc = x.detach().contiguous().float(), y.detach().contiguous().float()
+    B, Cn, H, W = xc.shape
+    nbytes = lib.m2t_msssim_loss_scratch_bytes(B, Cn, H, W)
+    if nbytes == 0:
+        raise M2TError(f"ms_ssim: no scratch size for [{B},{Cn},{H},{W}] (height and width must be larger than 160, B * C at most 65535)")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=xc.device)
+    out = torch.empty(1, dtype=torch.float32, device=xc.device)
+    grad = torch.zeros_like(xc) if want_grad else None
+    per = torch.empty(B * Cn, dtype=torch.float64, device=xc.device) if want_per_channel else None
+    with torch.cuda.device(xc.device):
+        _lib.check(lib.m2t_msssim_loss_tensor(_lib.ptr(xc), _lib.ptr(yc), B, Cn, H, W, Cn * H * W, W, float(data_range), 0,
+                                              1.0 / (B * Cn), _lib.ptr(grad), _lib.ptr(out), _lib.ptr(per), 0, _lib.ptr(scratch),
+                                              _lib.stream_ptr()), "m2t_msssim_loss_tensor")
+    return out, grad, per
+
+
+def _msssim_check(what, x, y, data_range):
+    if x.dim() != 4 or x.shape != y.shape:
+        raise M2TError(f"{what}: expected two [B,C,H,W] tensors of equal shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if not (x.is_cuda and y.is_cuda):
+        raise M2TError(f"{what} needs HIP device tensors (there is no host implementation)")
+    if not (float(data_range) > 0.0):
+        raise M2TError(f"{what}: data_range must be > 0, got {data_range!r}")
+    H, W = int(x.shape[2]), int(x.shape[3])
+    if min(H, W) < _lib.MSSSIM_MIN_SIDE:
+        raise M2TError(f"{what}: image {H}x{W} is too small for five levels under the 11-tap window (height and width must be larger than 160)")
+
+
+class _MSSSIMLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, data_range):
+        # value and gradient come from one call; the gradient of the MEAN, scaled by the upstream gradient in backward
+        out, ctx.grad, _ = _msssim_call(x, y, data_range, ctx.needs_input_grad[0], False)
+        ctx.x_dtype = x.dtype
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        return (ctx.grad * g).to(ctx.x_dtype), None, None
+
+
+def ms_ssim_loss(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0) -> torch.Tensor:
+    """1 - mean over (image, channel) of MS-SSIM(x, y), the ``pytorch_msssim.ms_ssim`` / ``piq.multi_scale_ssim`` form (five levels,
+    weights 0.0448, 0.2856, 0.3001, 0.2363, 0.1333, 11-tap Gaussian sigma 1.5, K = (0.01, 0.03), the 2 x 2 average with padding
+    side % 2 between the levels, inputs NOT clamped to the data range), for device tensors [B,C,H,W] with H, W > 160; differentiable
+    with respect to ``x`` only.  An (image, channel) one of whose level means is not positive has MS-SSIM 0 and gradient 0 (torch's
+    autograd gives 0 * inf there).  fp64 inside the kernels, fp32 in and out."""
+    _msssim_check("ms_ssim_loss", x, y, data_range)
+    if y.requires_grad:
+        raise M2TError("ms_ssim_loss gives the gradient with respect to x only: y must not require grad (detach it)")
+    return _MSSSIMLossFn.apply(x, y, float(data_range))
+
+
+class MSSSIMLoss(nn.Module):
+    """``ms_ssim_loss`` as a module."""
+
+    def __init__(self, data_range: float = 1.0):
+        super().__init__()
+        self.data_range = float(data_range)
+
+    def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        return ms_ssim_loss(x, y, self.data_range)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # The frequency-domain term: an L1 on the coefficients of rfft2 (the reference imports torch.fft, losses.py:5, and never calls it;
 # MIMO-UNet's F.l1_loss(view_as_real(rfft2(x)), view_as_real(rfft2(y)))).  Value and gradient are HIP (m2t_fft_loss_tensor of
 # include/m2t_spectral.h, k_fft_loss.hip); there is no torch fallback.

@@ -107,6 +107,17 @@ def fsim_device(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0) -> to
     return out
 
 
+def ms_ssim_device(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0) -> torch.Tensor:
+    """``pytorch_msssim.ms_ssim(x, y, data_range=data_range, size_average=False)`` / ``piq.multi_scale_ssim(..., reduction='none')``
+    on the device: [B,C,H,W] float32 pairs with H, W > 160 -> float64 [B], the channel mean of the per-channel MS-SSIM (0 for a
+    channel one of whose level means is not positive).  The value-only path of `m2t_msssim_loss_tensor` (k_msssim_loss.hip);
+    parity with the packages is unpinned (neither is vendored)."""
+    from .losses import _msssim_call, _msssim_check
+    _msssim_check("ms_ssim_device", x, y, data_range)
+    _, _, per = _msssim_call(x, y, data_range, False, True)
+    return per.view(x.shape[0], x.shape[1]).mean(dim=1)
+
+
 def evaluate(model, pairs, scale: int, rgb_range: float = 1.0, with_gmsd: bool = False, with_fsim: bool = False):
     """The reference's test loop (test.py:77-122): `pairs` yields (lr, hr) device tensors [1,3,h,w] / [1,3,h*scale,w*scale];
     returns (avg_psnr, avg_ssim) -- with_gmsd: + avg_gmsd; with_fsim: + avg_fsim, in the order the reference prints them

@@ -42,6 +42,14 @@ norm=fft_norm)`` per RGB channel, value and gradient in HIP (m2t_fft_loss of inc
 LDS; SR height and width even, 8 .. 2048, of the form 2^a 3^b).  Like lambda_ssim it takes the MATERIALISED seed, and the calls
 run in the order pixel -> SSIM (if on) -> FFT -> backward.  With lambda_fft = 0 (the default) nothing is allocated and the step
 issues the calls it issued before.
+
+Multi-scale structural term (``lambda_msssim``; the reference imports MultiScaleSSIMLoss from piq in the same line, losses.py:8; L1 +
+MS-SSIM is the recipe of Zhao et al.): ``lambda_msssim * (1 - mean MS-SSIM)`` per image and RGB channel in the
+pytorch_msssim.ms_ssim / piq.multi_scale_ssim form (five levels, the 2 x 2 average between them), value and gradient in HIP
+(m2t_msssim_loss of include/m2t_msssim.h, fp64 inside; SR height and width > 160).  An (image, channel) with a non-positive level
+mean has MS-SSIM 0 and adds no gradient.  It takes the MATERIALISED seed like the other two terms; the calls run in the order
+pixel -> SSIM (if on) -> MS-SSIM (if on) -> FFT (if on) -> backward.  With lambda_msssim = 0 (the default) nothing is allocated and
+the step issues the calls it issued before.
 """
 from __future__ import annotations
 
@@ -105,6 +113,22 @@ def resolve_lambda_ssim(value) -> float:
     return v
 
 
+def resolve_lambda_msssim(value) -> float:
+    """TrainStep's ``lambda_msssim`` as a float; M2TError unless it is a finite number >= 0."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise _lib.M2TError(f"lambda_msssim must be a finite number >= 0, got {value!r}") from None
+    if not (math.isfinite(v) and v >= 0.0):
+        raise _lib.M2TError(f"lambda_msssim must be a finite number >= 0, got {value!r}")
+    return v
+
+
+def msssim_size_supported(h: int, w: int) -> bool:
+    """The sizes the multi-scale term takes (the rule of include/m2t_msssim.h, decided on the host): min(H, W) > 160."""
+    return min(int(h), int(w)) >= _lib.MSSSIM_MIN_SIDE
+
+
 def resolve_lambda_fft(value) -> float:
     """TrainStep's ``lambda_fft`` as a float; M2TError unless it is a finite number >= 0."""
     try:
@@ -160,7 +184,8 @@ class TrainStep:
                  accum_steps: int = 1, max_grad_norm: Optional[float] = None, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, ema_decay: Optional[float] = None, skip_nonfinite: bool = False,
                  track_grad_norm: bool = False, pixel_loss: str = "l1", pixel_loss_param: Optional[float] = None,
-                 lambda_ssim: float = 0.0, lambda_fft: float = 0.0, fft_norm: str = "backward"):
+                 lambda_ssim: float = 0.0, lambda_fft: float = 0.0, fft_norm: str = "backward",
+                 lambda_msssim: float = 0.0):
         self.model = model
         # the pixel term: lambda_l1 (the reference's config key) stays its weight and l1_loss the tensor that holds it, whatever the kind
         self.set_pixel_loss(pixel_loss, pixel_loss_param)
@@ -168,6 +193,10 @@ class TrainStep:
         self.ssim_loss = None                   # device float [1], already weighted (this rank's share of the global mean)
         self._ssim_scratch = {}                 # (B, Hs, Ws) -> the kernel's partial-sum scratch, allocated once per plan shape
         self.set_lambda_ssim(lambda_ssim)
+        # the multi-scale structural term lambda_msssim * (1 - mean MS-SSIM): 0 = off (nothing allocated, no call more)
+        self.msssim_loss = None                 # device float [1], already weighted
+        self._msssim_scratch = {}               # (B, Hs, Ws) -> pyramids, gradient levels, partial sums, record: once per plan shape
+        self.set_lambda_msssim(lambda_msssim)
         # the frequency-domain term lambda_fft * mean |rfft2(sr - hr)|: 0 = off (nothing allocated, no call more)
         self.fft_loss = None                    # device float [1], already weighted
         self._fft_scratch = {}                  # (B, Hs, Ws) -> the half spectrum + partial sums, allocated once per plan shape
@@ -286,6 +315,43 @@ class TrainStep:
                                      _lib.ptr(self.ssim_loss), 0 if first else 1, _lib.ptr(self._ssim_scratch[key]), ws, st),
                    "m2t_ssim_loss")
 
+    def set_lambda_msssim(self, value):
+        """Weight of the multi-scale structural term (0 = off).  Takes effect with the next forward_backward
+        (checkpoint.import_checkpoint calls this); refused in the middle of an accumulation cycle."""
+        if getattr(self, "micro_count", 0) != 0:
+            raise _lib.M2TError(f"set_lambda_msssim in the middle of an accumulation cycle ({self.micro_count} of {self.accum_steps} "
+                                "micro-batches since the last optimizer step)")
+        self.lambda_msssim = resolve_lambda_msssim(value)
+        if self.lambda_msssim > 0.0:
+            if self.msssim_loss is None:
+                self.msssim_loss = torch.zeros(1, dtype=torch.float32, device=self.model.flat_params.device)
+        else:
+            self.msssim_loss, self._msssim_scratch = None, {}
+
+    def _msssim_scratch_for(self, lib, hr_img):
+        """The scratch of the multi-scale term for this (micro-)batch shape, allocated once; an SR size below the five-level rule
+        is refused here, on the host, before anything is launched."""
+        B, _, Hs, Ws = hr_img.shape
+        key = (B, Hs, Ws)
+        if key not in self._msssim_scratch:
+            if not msssim_size_supported(Hs, Ws):
+                raise _lib.M2TError(f"lambda_msssim > 0: the SR image {Hs}x{Ws} is too small for five levels under the 11-tap window "
+                                    "(height and width must be larger than 160)")
+            nbytes = int(lib.m2t_msssim_loss_scratch_bytes(B, 3, Hs, Ws))
+            if nbytes == 0:
+                raise _lib.M2TError(f"lambda_msssim > 0: no scratch size for a batch of {B} SR images {Hs}x{Ws} (B * 3 <= 65535)")
+            self._msssim_scratch[key] = torch.empty(nbytes, dtype=torch.uint8, device=hr_img.device)
+        return self._msssim_scratch[key]
+
+    def _msssim_loss_call(self, lib, plan, hr_img, first: bool, ws, st):
+        """m2t_msssim_loss of one (micro-)batch, behind the immediate pixel loss (and the SSIM term): adds into the materialised
+        seed; the value is stored by the first micro-batch of a cycle and added to by the others."""
+        B = hr_img.shape[0]
+        divisor = global_divisor(B * 3, self.world_size, self.accum_steps)       # global number of (image, channel) pairs
+        _lib.check(lib.m2t_msssim_loss(plan.handle, _lib.ptr(hr_img), self.lambda_msssim, divisor, float(self.model.rgb_range),
+                                       _lib.ptr(self.msssim_loss), 0 if first else 1, _lib.ptr(self._msssim_scratch_for(lib, hr_img)),
+                                       ws, st), "m2t_msssim_loss")
+
     def set_lambda_fft(self, value, norm=None):
         """Weight of the frequency-domain term (0 = off) and, when given, its normalisation ('backward' / 'ortho').  Takes effect
         with the next forward_backward (checkpoint.import_checkpoint calls this); refused in the middle of an accumulation cycle."""
@@ -329,6 +395,8 @@ class TrainStep:
 
     def _total_loss(self, with_clip: bool):
         loss = self.l1_loss if self.ssim_loss is None else self.l1_loss + self.ssim_loss
+        if self.msssim_loss is not None:
+            loss = loss + self.msssim_loss
         if self.fft_loss is not None:
             loss = loss + self.fft_loss
         return loss + self.clip_loss if with_clip else loss
@@ -393,6 +461,8 @@ class TrainStep:
         B = lr_img.shape[0]
         if tuple(hr_img.shape) != (B, 3, lr_img.shape[2] * m.scale, lr_img.shape[3] * m.scale):
             raise _lib.M2TError("hr shape must be [B,3,H*scale,W*scale]")
+        if self.lambda_msssim > 0.0:
+            self._msssim_scratch_for(lib, hr_img)   # (refuses an SR size below the five-level rule before any launch)
         if self.lambda_fft > 0.0:
             self._fft_scratch_for(lib, hr_img)      # (refuses an SR size outside the transform's rule before any launch)
         divisor = global_divisor(hr_img.numel(), self.world_size, self.accum_steps)      # global mean (equal shards, equal micro-batches)
@@ -414,11 +484,13 @@ class TrainStep:
             # (deferred: the loss and the backward seed are produced inside m2t_backward, which follows at once -- on the bf16 x4
             #  path by the fused tail backward itself; hr_img stays alive until then)
             # (lambda_ssim > 0: the materialised seed -- the immediate pixel loss, then the structural term added into it)
-            # (lambda_fft > 0: the same route; the frequency-domain term goes last: pixel -> SSIM -> FFT -> backward)
-            ssim, fft = self.lambda_ssim > 0.0, self.lambda_fft > 0.0
-            self._pixel_loss_call(lib, not (ssim or fft), plan, hr_img, divisor, l1_loss, ws, st)
+            # (lambda_msssim / lambda_fft > 0: the same route; the order is pixel -> SSIM -> MS-SSIM -> FFT -> backward)
+            ssim, msssim, fft = self.lambda_ssim > 0.0, self.lambda_msssim > 0.0, self.lambda_fft > 0.0
+            self._pixel_loss_call(lib, not (ssim or msssim or fft), plan, hr_img, divisor, l1_loss, ws, st)
             if ssim:
                 self._ssim_loss_call(lib, plan, hr_img, first, ws, st)
+            if msssim:
+                self._msssim_loss_call(lib, plan, hr_img, first, ws, st)
             if fft:
                 self._fft_loss_call(lib, plan, hr_img, first, ws, st)
             fwd_done = torch.cuda.current_stream(lr_img.device).record_event() if (use_clip and self.overlap_semantic) else None
@@ -482,6 +554,8 @@ class TrainStep:
             self._pixel_loss_call(lib, False, plan, hr_img, divisor, l1_loss, ws, st)
             if self.lambda_ssim > 0.0:
                 self._ssim_loss_call(lib, plan, hr_img, grads is self.grads, ws, st)
+            if self.lambda_msssim > 0.0:
+                self._msssim_loss_call(lib, plan, hr_img, grads is self.grads, ws, st)
             if self.lambda_fft > 0.0:
                 self._fft_loss_call(lib, plan, hr_img, grads is self.grads, ws, st)
             g = g.contiguous()
