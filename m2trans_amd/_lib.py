@@ -1,4 +1,5 @@
-"""ctypes binding of libm2t.so (include/m2t.h, include/m2t_spectral.h, include/m2t_resize.h, include/m2t_msssim.h).
+"""ctypes binding of libm2t.so (include/m2t.h, include/m2t_spectral.h, include/m2t_resize.h, include/m2t_msssim.h,
+include/m2t_vif.h).
 
 The product path has NO fallback: if the HIP library is missing, or a call fails, this
 module raises.  Build it with ``python -m m2trans_amd.build`` (hipcc, gfx950).
@@ -115,6 +116,17 @@ MSSSIM_SIGNATURES = {
 MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)     # the five level weights of the term
 MSSSIM_MIN_SIDE = 161                                          # min(H, W) > 160 = (11 - 1) * 2^4
 
+# the fifth header, include/m2t_vif.h (the information-fidelity loss term), bound on the same library; must list every symbol that
+# header declares.  The four tables above stay as they are.
+VIF_SIGNATURES = {
+    "m2t_vif_loss_scratch_bytes": (C.c_size_t, [_i, _i, _i, _i]),
+    "m2t_vif_loss_scratch_offset": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
+    "m2t_vif_loss_tensor": (_i, [_vp, _vp, _i, _i, _i, _i, _ll, _i, _f, _d, _i, _d, _vp, _vp, _vp, _i, _vp, _vp]),
+    "m2t_vif_loss": (_i, [_vp, _vp, _f, _d, _f, _d, _vp, _i, _vp, _vp, _vp]),
+}
+VIF_MIN_SIDE = 41                                              # min(H, W) >= 41: the scale-3 map is then 1 x 1
+VIF_SIGMA_N_SQ = 2.0                                           # the default variance of the visual noise
+
 _lib = None
 
 
@@ -137,7 +149,7 @@ def load():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) \
-            + list(MSSSIM_SIGNATURES.items()):
+            + list(MSSSIM_SIGNATURES.items()) + list(VIF_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

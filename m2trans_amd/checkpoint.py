@@ -30,7 +30,8 @@ An L1 run writes no entry: its dict is the one above.  With TrainStep(lambda_ssi
 key is absent and the dict is the one described above, byte for byte.  TrainStep(lambda_fft > 0) adds ``"lambda_fft"`` and
 ``"fft_norm"`` to the entry in the same way (``import_checkpoint`` calls ``set_lambda_fft``); with lambda_fft = 0 neither key is
 written.  TrainStep(lambda_msssim > 0) adds ``"lambda_msssim"`` in the same way (``import_checkpoint`` calls ``set_lambda_msssim``);
-with lambda_msssim = 0 the key is absent.
+with lambda_msssim = 0 the key is absent.  TrainStep(lambda_vif > 0) adds ``"lambda_vif"`` after the other keys in the same way
+(``import_checkpoint`` calls ``set_lambda_vif``); with lambda_vif = 0 the key is absent.
 """
 from __future__ import annotations
 
@@ -69,7 +70,8 @@ def _pixel_loss(train_step):
     lam = float(getattr(train_step, "lambda_ssim", 0.0) or 0.0)
     lam_fft = float(getattr(train_step, "lambda_fft", 0.0) or 0.0)
     lam_ms = float(getattr(train_step, "lambda_msssim", 0.0) or 0.0)
-    if canon == "l1" and lam == 0.0 and lam_fft == 0.0 and lam_ms == 0.0:
+    lam_vif = float(getattr(train_step, "lambda_vif", 0.0) or 0.0)
+    if canon == "l1" and lam == 0.0 and lam_fft == 0.0 and lam_ms == 0.0 and lam_vif == 0.0:
         return None
     out = {"pixel_loss": canon, "param": value}
     if lam != 0.0:
@@ -79,6 +81,8 @@ def _pixel_loss(train_step):
     if lam_fft != 0.0:
         out["lambda_fft"] = lam_fft
         out["fft_norm"] = str(getattr(train_step, "fft_norm", "backward"))
+    if lam_vif != 0.0:
+        out["lambda_vif"] = lam_vif
     return out
 
 
@@ -186,6 +190,12 @@ def import_checkpoint(ckpt: dict, model, train_step=None) -> int:
             else:
                 from .train_step import resolve_lambda_msssim
                 train_step.lambda_msssim = resolve_lambda_msssim(ml["lambda_msssim"])
+        if "lambda_vif" in ml:
+            if hasattr(train_step, "set_lambda_vif"):
+                train_step.set_lambda_vif(ml["lambda_vif"])
+            else:
+                from .train_step import resolve_lambda_vif
+                train_step.lambda_vif = resolve_lambda_vif(ml["lambda_vif"])
         if "lambda_fft" in ml:
             if hasattr(train_step, "set_lambda_fft"):
                 train_step.set_lambda_fft(ml["lambda_fft"], ml.get("fft_norm"))

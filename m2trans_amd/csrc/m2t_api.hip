@@ -9,6 +9,7 @@
 #include "../../include/m2t.h"
 #include "../../include/m2t_spectral.h"
 #include "../../include/m2t_msssim.h"
+#include "../../include/m2t_vif.h"
 
 static thread_local std::string g_err;
 int m2t_set_hip_error(hipError_t e, const char* file, int line) {
@@ -740,6 +741,26 @@ extern "C" int m2t_msssim_loss(m2t_plan* p, const float* hr, float weight, doubl
   return launch_msssim_loss((const float*)(ws + p->hd.srpre), hr, p->B, 3, p->Hs, p->Ws, 3LL * p->Hsp * p->Wsp, p->Wsp, rgb_range, 1,
                             (double)weight / divisor, (float*)(ws + p->hd.gpre), loss_out, nullptr, accumulate ? 1 : 0, scratch,
                             (hipStream_t)stream);
+}
+
+// weight * (1 - mean VIF) (k_vif_loss.hip; include/m2t_vif.h) on the forward's pre-clamp output, added into the materialised seed: the
+// routine of m2t_vif_loss_tensor on ws:srpre (padded Hsp x Wsp, image in the top-left Hs x Ws) and ws:gpre.  State rules of
+// m2t_ssim_loss.  Scratch is the caller's: no plan option, no workspace region.
+extern "C" int m2t_vif_loss(m2t_plan* p, const float* hr, float weight, double divisor, float rgb_range, double sigma_n_sq,
+                            float* loss_out, int accumulate, void* scratch, void* workspace, void* stream) {
+  if (!p || !hr || !loss_out || !scratch || !workspace) return m2t_set_error(M2T_ERR_ARG, "m2t_vif_loss: null argument");
+  if (!(rgb_range > 0.f) || !std::isfinite(rgb_range) || !(divisor > 0.0) || !std::isfinite(divisor) || !std::isfinite(weight) ||
+      !(sigma_n_sq > 0.0) || !std::isfinite(sigma_n_sq))
+    return m2t_set_error(M2T_ERR_ARG, "m2t_vif_loss: rgb_range, divisor and sigma_n_sq must be finite numbers > 0, weight finite");
+  if (!vif_loss_size_supported(p->Hs, p->Ws))
+    return m2t_set_error(M2T_ERR_ARG, "m2t_vif_loss: the SR height and width must be at least 41 (four scales under the 17 / 9 / 5 / 3-tap windows)");
+  if (p->B > 65535) return m2t_set_error(M2T_ERR_ARG, "m2t_vif_loss: batch too large (B <= 65535)");
+  if (!p->have_acts || !p->have_seed || p->l1_deferred)
+    return m2t_set_error(M2T_ERR_STATE, "m2t_vif_loss: needs a materialised seed (m2t_l1_loss / m2t_pixel_loss or m2t_set_output_grad)");
+  char* const ws = (char*)workspace;
+  return launch_vif_loss((const float*)(ws + p->hd.srpre), hr, p->B, 3, p->Hs, p->Ws, 3LL * p->Hsp * p->Wsp, p->Wsp, rgb_range, sigma_n_sq,
+                         1, (double)weight / divisor, (float*)(ws + p->hd.gpre), loss_out, nullptr, accumulate ? 1 : 0, scratch,
+                         (hipStream_t)stream);
 }
 
 // weight * mean |rfft2(d)| (k_fft_loss.hip; include/m2t_spectral.h) on the forward's pre-clamp output, added into the materialised

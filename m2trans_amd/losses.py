@@ -25,6 +25,7 @@ from __future__ import annotations
 
 import ctypes as C
 import hashlib
+import math
 from typing import Dict, Iterable, List, Optional, Sequence
 
 import torch
@@ -598,6 +599,82 @@ class MSSSIMLoss(nn.Module):
 
     def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         return ms_ssim_loss(x, y, self.data_range)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The information-fidelity term: 1 - VIF, pixel domain (the reference imports VIFLoss from piq, losses.py:8).  Value and gradient are
+# HIP (m2t_vif_loss_tensor of include/m2t_vif.h, k_vif_loss.hip); there is no torch fallback.
+# ---------------------------------------------------------------------------------------------------------------
+def _vif_call(x, y, data_range, sigma_n_sq, want_grad, want_per_image):
+    """(loss [1] float32, gradient of the mean or None, VIF_b [B] float64 or None) of device tensors [B,C,H,W]."""
+    lib = _lib.load()
+    xc, yc = x.detach().contiguous().float(), y.detach().contiguous().float()
+    B, Cn, H, W = xc.shape
+    nbytes = lib.m2t_vif_loss_scratch_bytes(B, Cn, H, W)
+    if nbytes == 0:
+        raise M2TError(f"vif: no scratch size for [{B},{Cn},{H},{W}] (height and width at least 41, 1 or 3 channels, B at most 65535)")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=xc.device)
+    out = torch.empty(1, dtype=torch.float32, device=xc.device)
+    grad = torch.zeros_like(xc) if want_grad else None
+    per = torch.empty(B, dtype=torch.float64, device=xc.device) if want_per_image else None
+    with torch.cuda.device(xc.device):
+        _lib.check(lib.m2t_vif_loss_tensor(_lib.ptr(xc), _lib.ptr(yc), B, Cn, H, W, Cn * H * W, W, float(data_range), float(sigma_n_sq), 0,
+                                           1.0 / B, _lib.ptr(grad), _lib.ptr(out), _lib.ptr(per), 0, _lib.ptr(scratch),
+                                           _lib.stream_ptr()), "m2t_vif_loss_tensor")
+    return out, grad, per
+
+
+def _vif_check(what, x, y, data_range, sigma_n_sq):
+    if x.dim() != 4 or x.shape != y.shape:
+        raise M2TError(f"{what}: expected two [B,C,H,W] tensors of equal shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if not (x.is_cuda and y.is_cuda):
+        raise M2TError(f"{what} needs HIP device tensors (there is no host implementation)")
+    if not (math.isfinite(float(data_range)) and float(data_range) > 0.0):
+        raise M2TError(f"{what}: data_range must be a finite number > 0, got {data_range!r}")
+    if not (math.isfinite(float(sigma_n_sq)) and float(sigma_n_sq) > 0.0):
+        raise M2TError(f"{what}: sigma_n_sq must be a finite number > 0, got {sigma_n_sq!r}")
+    if int(x.shape[1]) not in (1, 3):
+        raise M2TError(f"{what}: VIF works on the luminance of 1 or 3 channels, got {int(x.shape[1])}")
+    H, W = int(x.shape[2]), int(x.shape[3])
+    if min(H, W) < _lib.VIF_MIN_SIDE:
+        raise M2TError(f"{what}: image {H}x{W} is too small for four scales under the 17 / 9 / 5 / 3-tap windows (height and width must be at least 41)")
+
+
+class _VIFLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, data_range, sigma_n_sq):
+        # value and gradient come from one call; the gradient of the MEAN, scaled by the upstream gradient in backward
+        out, ctx.grad, _ = _vif_call(x, y, data_range, sigma_n_sq, ctx.needs_input_grad[0], False)
+        ctx.x_dtype = x.dtype
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        return (ctx.grad * g).to(ctx.x_dtype), None, None, None
+
+
+def vif_loss(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0, sigma_n_sq: float = 2.0) -> torch.Tensor:
+    """1 - mean over the images of VIF(x, y), the pixel-domain visual information fidelity of Sheikh & Bovik in the ``piq.vif_p``
+    form (luminance of an RGB image on the 0 .. 255 scale, four scales with Gaussian windows of 17, 9, 5, 3 taps, a filtered and
+    decimated pyramid, inputs NOT clamped to the data range), for device tensors [B,C,H,W] with C = 1 or 3 and H, W >= 41;
+    differentiable with respect to ``x`` only.  VIF exceeds 1 for a contrast-enhanced ``x``: the value may be negative and is not
+    clipped.  fp64 inside the kernels, fp32 in and out."""
+    _vif_check("vif_loss", x, y, data_range, sigma_n_sq)
+    if y.requires_grad:
+        raise M2TError("vif_loss gives the gradient with respect to x only: y must not require grad (detach it)")
+    return _VIFLossFn.apply(x, y, float(data_range), float(sigma_n_sq))
+
+
+class VIFLoss(nn.Module):
+    """``vif_loss`` as a module."""
+
+    def __init__(self, data_range: float = 1.0, sigma_n_sq: float = 2.0):
+        super().__init__()
+        self.data_range = float(data_range)
+        self.sigma_n_sq = float(sigma_n_sq)
+
+    def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        return vif_loss(x, y, self.data_range, self.sigma_n_sq)
 
 
 # ---------------------------------------------------------------------------------------------------------------

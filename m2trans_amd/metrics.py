@@ -118,12 +118,25 @@ def ms_ssim_device(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0) ->
     return per.view(x.shape[0], x.shape[1]).mean(dim=1)
 
 
-def evaluate(model, pairs, scale: int, rgb_range: float = 1.0, with_gmsd: bool = False, with_fsim: bool = False):
+def vif_device(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0) -> torch.Tensor:
+    """``piq.vif_p(x, y, data_range=data_range, reduction='none')`` on the device: [B,C,H,W] float32 pairs with C = 1 or 3 and
+    H, W >= 41 -> float64 [B], the pixel-domain VIF of the luminance planes (sigma_n_sq = 2; it exceeds 1 for a contrast-enhanced
+    x).  The value-only path of `m2t_vif_loss_tensor` (k_vif_loss.hip); parity with the package is unpinned (it is not vendored)."""
+    from . import _lib
+    from .losses import _vif_call, _vif_check
+    _vif_check("vif_device", x, y, data_range, _lib.VIF_SIGMA_N_SQ)
+    _, _, per = _vif_call(x, y, data_range, _lib.VIF_SIGMA_N_SQ, False, True)
+    return per
+
+
+def evaluate(model, pairs, scale: int, rgb_range: float = 1.0, with_gmsd: bool = False, with_fsim: bool = False,
+             with_vif: bool = False):
     """The reference's test loop (test.py:77-122): `pairs` yields (lr, hr) device tensors [1,3,h,w] / [1,3,h*scale,w*scale];
     returns (avg_psnr, avg_ssim) -- with_gmsd: + avg_gmsd; with_fsim: + avg_fsim, in the order the reference prints them
-    (PSNR, SSIM, FSIM, GMSD; test.py:118-122) -- rounded as the reference rounds them.  One host synchronisation at the end
-    (the reference synchronises per image)."""
-    rows, grows, frows = [], [], []
+    (PSNR, SSIM, FSIM, GMSD; test.py:118-122) -- rounded as the reference rounds them; with_vif: + the average
+    pixel-domain VIF of (sr, hr) at data range `rgb_range`, after everything else, rounded like FSIM / GMSD (SR sides of at least
+    41).  One host synchronisation at the end (the reference synchronises per image)."""
+    rows, grows, frows, vrows = [], [], [], []
     with torch.no_grad():
         for lr, hr in pairs:
             sr = model(lr)
@@ -133,6 +146,8 @@ def evaluate(model, pairs, scale: int, rgb_range: float = 1.0, with_gmsd: bool =
                 frows.append(fsim_device(hr, sr, 1.0))          # BEFORE the Y conversion, on RGB, like test.py:95-99
             if with_gmsd:
                 grows.append(gmsd_device(hr, sr, 1.0))
+            if with_vif:
+                vrows.append(vif_device(sr, hr, rgb_range))
             rows.append(y_metrics_device(sr, hr, scale, rgb_range))
     if not rows:
         raise ValueError("no evaluation pairs")
@@ -145,4 +160,6 @@ def evaluate(model, pairs, scale: int, rgb_range: float = 1.0, with_gmsd: bool =
         out.append(round(float(torch.cat(frows).sum()) / len(psnr) + 5e-5, 4))
     if with_gmsd:
         out.append(round(float(torch.cat(grows).sum()) / len(psnr) + 5e-5, 4))
+    if with_vif:
+        out.append(round(float(torch.cat(vrows).sum()) / len(psnr) + 5e-5, 4))
     return tuple(out)

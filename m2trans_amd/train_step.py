@@ -50,6 +50,14 @@ pytorch_msssim.ms_ssim / piq.multi_scale_ssim form (five levels, the 2 x 2 avera
 mean has MS-SSIM 0 and adds no gradient.  It takes the MATERIALISED seed like the other two terms; the calls run in the order
 pixel -> SSIM (if on) -> MS-SSIM (if on) -> FFT (if on) -> backward.  With lambda_msssim = 0 (the default) nothing is allocated and
 the step issues the calls it issued before.
+
+Information-fidelity term (``lambda_vif``; the reference imports VIFLoss from piq in the same line, losses.py:8):
+``lambda_vif * (1 - mean VIF)`` per image, the pixel-domain VIF of Sheikh & Bovik in the piq.vif_p form on the luminance of
+``clamp(sr, 0, rgb_range)`` and ``hr`` (four scales, windows of 17 / 9 / 5 / 3 taps, sigma_n_sq = 2), value and gradient in HIP
+(m2t_vif_loss of include/m2t_vif.h, fp64 inside; SR height and width >= 41).  VIF exceeds 1 for a contrast-enhanced output, so the
+term may be negative; it is not clipped.  It takes the MATERIALISED seed like the other terms; the calls run in the order
+pixel -> SSIM -> MS-SSIM -> FFT -> VIF (each if on) -> backward.  With lambda_vif = 0 (the default) nothing is allocated and the
+step issues the calls it issued before.
 """
 from __future__ import annotations
 
@@ -129,6 +137,22 @@ def msssim_size_supported(h: int, w: int) -> bool:
     return min(int(h), int(w)) >= _lib.MSSSIM_MIN_SIDE
 
 
+def resolve_lambda_vif(value) -> float:
+    """TrainStep's ``lambda_vif`` as a float; M2TError unless it is a finite number >= 0."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise _lib.M2TError(f"lambda_vif must be a finite number >= 0, got {value!r}") from None
+    if not (math.isfinite(v) and v >= 0.0):
+        raise _lib.M2TError(f"lambda_vif must be a finite number >= 0, got {value!r}")
+    return v
+
+
+def vif_size_supported(h: int, w: int) -> bool:
+    """The sizes the information-fidelity term takes (the rule of include/m2t_vif.h, decided on the host): min(H, W) >= 41."""
+    return min(int(h), int(w)) >= _lib.VIF_MIN_SIDE
+
+
 def resolve_lambda_fft(value) -> float:
     """TrainStep's ``lambda_fft`` as a float; M2TError unless it is a finite number >= 0."""
     try:
@@ -177,6 +201,10 @@ def _shared_stream(device, role: str):
 
 
 class TrainStep:
+    # (defaults of the newest term for step objects assembled without __init__)
+    lambda_vif = 0.0
+    vif_loss = None
+
     def __init__(self, model: M2Trans, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  lambda_l1: float = 1.0, process_group=None, world_size: Optional[int] = None,
                  grad_bucket_dtype: torch.dtype = torch.float32, semantic_loss=None, lambda_clip: float = 0.0,
@@ -185,7 +213,7 @@ class TrainStep:
                  decoupled_weight_decay: bool = False, ema_decay: Optional[float] = None, skip_nonfinite: bool = False,
                  track_grad_norm: bool = False, pixel_loss: str = "l1", pixel_loss_param: Optional[float] = None,
                  lambda_ssim: float = 0.0, lambda_fft: float = 0.0, fft_norm: str = "backward",
-                 lambda_msssim: float = 0.0):
+                 lambda_msssim: float = 0.0, lambda_vif: float = 0.0):
         self.model = model
         # the pixel term: lambda_l1 (the reference's config key) stays its weight and l1_loss the tensor that holds it, whatever the kind
         self.set_pixel_loss(pixel_loss, pixel_loss_param)
@@ -202,6 +230,10 @@ class TrainStep:
         self._fft_scratch = {}                  # (B, Hs, Ws) -> the half spectrum + partial sums, allocated once per plan shape
         self.fft_norm = "backward"
         self.set_lambda_fft(lambda_fft, fft_norm)
+        # the information-fidelity term lambda_vif * (1 - mean VIF): 0 = off (nothing allocated, no call more)
+        self.vif_loss = None                    # device float [1], already weighted (may be negative: VIF can exceed 1)
+        self._vif_scratch = {}                  # (B, Hs, Ws) -> pyramids, gradient levels, partial sums, record: once per plan shape
+        self.set_lambda_vif(lambda_vif)
         # gradient accumulation: one optimizer step consumes accum_steps equal micro-batches (forward_backward calls); the
         # gradients and the loss of calls 2..k of a cycle are added to the first call's by m2t_grad_accumulate
         if int(accum_steps) != accum_steps or int(accum_steps) < 1:
@@ -393,12 +425,51 @@ class TrainStep:
                                     _lib.FFT_NORMS[self.fft_norm], _lib.ptr(self.fft_loss), 0 if first else 1,
                                     _lib.ptr(self._fft_scratch_for(lib, hr_img)), ws, st), "m2t_fft_loss")
 
+    def set_lambda_vif(self, value):
+        """Weight of the information-fidelity term (0 = off).  Takes effect with the next forward_backward
+        (checkpoint.import_checkpoint calls this); refused in the middle of an accumulation cycle."""
+        if getattr(self, "micro_count", 0) != 0:
+            raise _lib.M2TError(f"set_lambda_vif in the middle of an accumulation cycle ({self.micro_count} of {self.accum_steps} "
+                                "micro-batches since the last optimizer step)")
+        self.lambda_vif = resolve_lambda_vif(value)
+        if self.lambda_vif > 0.0:
+            if self.vif_loss is None:
+                self.vif_loss = torch.zeros(1, dtype=torch.float32, device=self.model.flat_params.device)
+        else:
+            self.vif_loss, self._vif_scratch = None, {}
+
+    def _vif_scratch_for(self, lib, hr_img):
+        """The scratch of the information-fidelity term for this (micro-)batch shape, allocated once; an SR size below the
+        four-scale rule is refused here, on the host, before anything is launched."""
+        B, _, Hs, Ws = hr_img.shape
+        key = (B, Hs, Ws)
+        if key not in self._vif_scratch:
+            if not vif_size_supported(Hs, Ws):
+                raise _lib.M2TError(f"lambda_vif > 0: the SR image {Hs}x{Ws} is too small for four scales under the 17 / 9 / 5 / 3-tap "
+                                    "windows (height and width must be at least 41)")
+            nbytes = int(lib.m2t_vif_loss_scratch_bytes(B, 3, Hs, Ws))
+            if nbytes == 0:
+                raise _lib.M2TError(f"lambda_vif > 0: no scratch size for a batch of {B} SR images {Hs}x{Ws} (B <= 65535)")
+            self._vif_scratch[key] = torch.empty(nbytes, dtype=torch.uint8, device=hr_img.device)
+        return self._vif_scratch[key]
+
+    def _vif_loss_call(self, lib, plan, hr_img, first: bool, ws, st):
+        """m2t_vif_loss of one (micro-)batch, behind the immediate pixel loss and the other terms: adds into the materialised seed;
+        the value is stored by the first micro-batch of a cycle and added to by the others."""
+        B = hr_img.shape[0]
+        divisor = global_divisor(B, self.world_size, self.accum_steps)           # global number of images (luminance: not times 3)
+        _lib.check(lib.m2t_vif_loss(plan.handle, _lib.ptr(hr_img), self.lambda_vif, divisor, float(self.model.rgb_range),
+                                    _lib.VIF_SIGMA_N_SQ, _lib.ptr(self.vif_loss), 0 if first else 1,
+                                    _lib.ptr(self._vif_scratch_for(lib, hr_img)), ws, st), "m2t_vif_loss")
+
     def _total_loss(self, with_clip: bool):
         loss = self.l1_loss if self.ssim_loss is None else self.l1_loss + self.ssim_loss
         if self.msssim_loss is not None:
             loss = loss + self.msssim_loss
         if self.fft_loss is not None:
             loss = loss + self.fft_loss
+        if self.vif_loss is not None:
+            loss = loss + self.vif_loss
         return loss + self.clip_loss if with_clip else loss
 
     def _pixel_loss_call(self, lib, deferred: bool, plan, hr_img, divisor, l1_loss, ws, st):
@@ -465,6 +536,8 @@ class TrainStep:
             self._msssim_scratch_for(lib, hr_img)   # (refuses an SR size below the five-level rule before any launch)
         if self.lambda_fft > 0.0:
             self._fft_scratch_for(lib, hr_img)      # (refuses an SR size outside the transform's rule before any launch)
+        if self.lambda_vif > 0.0:
+            self._vif_scratch_for(lib, hr_img)      # (refuses an SR size below the four-scale rule before any launch)
         divisor = global_divisor(hr_img.numel(), self.world_size, self.accum_steps)      # global mean (equal shards, equal micro-batches)
         use_clip = self.semantic_loss is not None and self.lambda_clip > 0 and captions is not None
         # (micro-batches 2..k of a cycle: a second gradient buffer and a second loss slot, added to the first ones below)
@@ -484,15 +557,17 @@ class TrainStep:
             # (deferred: the loss and the backward seed are produced inside m2t_backward, which follows at once -- on the bf16 x4
             #  path by the fused tail backward itself; hr_img stays alive until then)
             # (lambda_ssim > 0: the materialised seed -- the immediate pixel loss, then the structural term added into it)
-            # (lambda_msssim / lambda_fft > 0: the same route; the order is pixel -> SSIM -> MS-SSIM -> FFT -> backward)
-            ssim, msssim, fft = self.lambda_ssim > 0.0, self.lambda_msssim > 0.0, self.lambda_fft > 0.0
-            self._pixel_loss_call(lib, not (ssim or msssim or fft), plan, hr_img, divisor, l1_loss, ws, st)
+            # (lambda_msssim / lambda_fft / lambda_vif > 0: the same route; the order is pixel -> SSIM -> MS-SSIM -> FFT -> VIF -> backward)
+            ssim, msssim, fft, vif = self.lambda_ssim > 0.0, self.lambda_msssim > 0.0, self.lambda_fft > 0.0, self.lambda_vif > 0.0
+            self._pixel_loss_call(lib, not (ssim or msssim or fft or vif), plan, hr_img, divisor, l1_loss, ws, st)
             if ssim:
                 self._ssim_loss_call(lib, plan, hr_img, first, ws, st)
             if msssim:
                 self._msssim_loss_call(lib, plan, hr_img, first, ws, st)
             if fft:
                 self._fft_loss_call(lib, plan, hr_img, first, ws, st)
+            if vif:
+                self._vif_loss_call(lib, plan, hr_img, first, ws, st)
             fwd_done = torch.cuda.current_stream(lr_img.device).record_event() if (use_clip and self.overlap_semantic) else None
             _lib.check(lib.m2t_backward(plan.handle, _lib.ptr(m.flat_params), _lib.ptr(lr_img), _lib.ptr(grads),
                                         ws, st), "m2t_backward")
@@ -558,6 +633,8 @@ class TrainStep:
                 self._msssim_loss_call(lib, plan, hr_img, grads is self.grads, ws, st)
             if self.lambda_fft > 0.0:
                 self._fft_loss_call(lib, plan, hr_img, grads is self.grads, ws, st)
+            if self.lambda_vif > 0.0:
+                self._vif_loss_call(lib, plan, hr_img, grads is self.grads, ws, st)
             g = g.contiguous()
             arr = None
             if origins is not None:
