@@ -1,5 +1,5 @@
 """ctypes binding of libm2t.so (include/m2t.h, include/m2t_spectral.h, include/m2t_resize.h, include/m2t_msssim.h,
-include/m2t_vif.h).
+include/m2t_vif.h, include/m2t_groups.h).
 
 The product path has NO fallback: if the HIP library is missing, or a call fails, this
 module raises.  Build it with ``python -m m2trans_amd.build`` (hipcc, gfx950).
@@ -127,6 +127,18 @@ VIF_SIGNATURES = {
 VIF_MIN_SIDE = 41                                              # min(H, W) >= 41: the scale-3 map is then 1 x 1
 VIF_SIGMA_N_SQ = 2.0                                           # the default variance of the visual noise
 
+# the sixth header, include/m2t_groups.h (parameter groups and frozen ranges for the optimizer end), bound on the same library; must
+# list every symbol that header declares.  The five tables above stay as they are.
+GROUPS_SIGNATURES = {
+    "m2t_group_table_bytes": (C.c_size_t, [_i]),
+    "m2t_group_table_pack": (_i, [C.POINTER(_ll), C.POINTER(_i), _i, _ll, _i, _vp]),
+    "m2t_adam_step_groups": (_i, [_vp, _vp, _vp, _vp, _ll, C.POINTER(_f), _f, _f, _f, _i, _f, _vp, C.POINTER(_f), _i, _f, _vp,
+                                  C.POINTER(C.c_ubyte), _i, _vp, _i, _vp]),
+    "m2t_grad_norm_groups": (_i, [_vp, _ll, _f, _f, _i, _i, _f, _f, _vp, _vp, C.POINTER(C.c_ubyte), _i, _vp, _i, _vp]),
+}
+MAX_GROUPS = 8                                                 # M2T_MAX_GROUPS
+MAX_SEGMENTS = 1024                                            # M2T_MAX_SEGMENTS
+
 _lib = None
 
 
@@ -149,7 +161,7 @@ def load():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) \
-            + list(MSSSIM_SIGNATURES.items()) + list(VIF_SIGNATURES.items()):
+            + list(MSSSIM_SIGNATURES.items()) + list(VIF_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

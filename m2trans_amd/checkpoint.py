@@ -32,6 +32,15 @@ key is absent and the dict is the one described above, byte for byte.  TrainStep
 written.  TrainStep(lambda_msssim > 0) adds ``"lambda_msssim"`` in the same way (``import_checkpoint`` calls ``set_lambda_msssim``);
 with lambda_msssim = 0 the key is absent.  TrainStep(lambda_vif > 0) adds ``"lambda_vif"`` after the other keys in the same way
 (``import_checkpoint`` calls ``set_lambda_vif``); with lambda_vif = 0 the key is absent.
+
+With TrainStep(param_groups=...) the optimizer dict comes from a real ``torch.optim.Adam`` with ONE TORCH PARAM GROUP PER GROUP, each
+carrying its own ``lr`` (= step.lr * lr_scale) and ``weight_decay``; the parameter ids run through the groups in order (torch's own
+numbering), the 4 frozen MeanShift tensors at the end of the last group.  Frozen tensors are listed in their group's ``params`` and
+have no ``state`` entry, like a torch Adam that never saw their gradient; ``import_checkpoint`` reads a missing entry as zero
+moments.  The dict gains ``m2t_groups`` = {"spec": the spec as given, "groups": the resolved groups (tensor names, lr_scale,
+weight_decay or None = the step's, frozen), "lr", "weight_decay", "decoupled_weight_decay": the step's own values}.
+``import_checkpoint`` requires the step it loads into to have been built with the same groups: a mismatch is an M2TError that names
+the difference.  Without groups the dict is the one above, key for key.
 """
 from __future__ import annotations
 
@@ -52,6 +61,38 @@ def ema_state_dict(model, ema_params) -> dict:
     for n, (o, k, shp) in zip(model._names, model._slots):
         sd[n] = ema_params[o:o + k].view(shp).detach().clone()
     return sd
+
+
+def _groups(train_step):
+    return getattr(train_step, "groups", None)
+
+
+def _torch_group_names(model, groups) -> list:
+    """Tensor names of each torch param group of a grouped export, in torch's id order: the groups' members, then -- at the end of
+    the last group -- every parameter outside the flat buffer (the frozen MeanShift tensors)."""
+    out = [list(m) for m in groups.members]
+    flat = set(model._names)
+    out[-1] = out[-1] + [n for n, _ in model.named_parameters() if n not in flat]
+    return out
+
+
+def _check_groups(ckpt: dict, train_step):
+    """A grouped optimizer state loads only into a step built with the same groups (and a group-free one into a group-free step)."""
+    from ._lib import M2TError
+    from .param_groups import describe_difference
+    mg, g = ckpt.get("m2t_groups"), _groups(train_step)
+    if mg is None and g is None:
+        return
+    if mg is None:
+        raise M2TError("import_checkpoint: the checkpoint was written without parameter groups, this TrainStep was built with "
+                       f"param_groups={g.spec!r}")
+    if g is None:
+        raise M2TError(f"import_checkpoint: the checkpoint was written with param_groups={mg.get('spec')!r}, this TrainStep was "
+                       "built without parameter groups")
+    diff = describe_difference(mg["groups"], g.describe())
+    if diff is not None:
+        raise M2TError(f"import_checkpoint: the checkpoint's parameter groups are not this TrainStep's: {diff} (checkpoint spec "
+                       f"{mg.get('spec')!r}, this step's {g.spec!r})")
 
 
 def _optim_options(train_step) -> dict:
@@ -125,7 +166,16 @@ def export_checkpoint(model, train_step=None, epoch: int = 1, stat_dict: Optiona
         oo = _optim_options(train_step)
         options_on = (oo["max_grad_norm"] is not None or oo["weight_decay"] != 0.0 or oo["ema_decay"] is not None
                       or oo["skip_nonfinite"])
-        if oo["weight_decay"] != 0.0:
+        groups = _groups(train_step)
+        by_name = dict(model.named_parameters())
+        if groups is not None:
+            # one torch param group per group, with its own lr and weight decay (the schedule scales each group's lr0 alike)
+            wds = groups.group_weight_decay(oo["weight_decay"])
+            tg = [{"params": [by_name[n] for n in names], "lr": lr0 * groups.lr_scale[g], "weight_decay": wds[g]}
+                  for g, names in enumerate(_torch_group_names(model, groups))]
+            kw = {"decoupled_weight_decay": oo["decoupled_weight_decay"]} if any(w != 0.0 for w in wds) else {}
+            opt = torch.optim.Adam(tg, lr=lr0, weight_decay=0, **kw)
+        elif oo["weight_decay"] != 0.0:
             # torch's own param_groups carry the decay (decoupled_weight_decay is Adam's AdamW switch)
             opt = torch.optim.Adam(params, lr=lr0, weight_decay=oo["weight_decay"],
                                    decoupled_weight_decay=oo["decoupled_weight_decay"])
@@ -139,11 +189,20 @@ def export_checkpoint(model, train_step=None, epoch: int = 1, stat_dict: Optiona
             for _ in range(max(0, int(epoch) - 1)):                       # epochs 1 .. E-1 have stepped the scheduler
                 sched.step()
         # the learning rate the step driver really used (equals the schedule's when the caller follows cosine_lr)
-        opt.param_groups[0]["lr"] = float(train_step.lr)
-        sched._last_lr = [float(train_step.lr)]
+        if groups is not None:
+            lrs = groups.group_lr(train_step.lr)
+            for pg, lr_g in zip(opt.param_groups, lrs):
+                pg["lr"] = lr_g
+            sched._last_lr = list(lrs)
+        else:
+            opt.param_groups[0]["lr"] = float(train_step.lr)
+            sched._last_lr = [float(train_step.lr)]
         if applied > 0:
             idx = _param_index(model)
+            frozen = set(groups.frozen_names()) if groups is not None else ()
             for n, (o, k, shp) in zip(model._names, model._slots):
+                if n in frozen:
+                    continue                                              # like a torch Adam that never saw this gradient
                 p = params[idx[n]]
                 opt.state[p] = {"step": torch.tensor(float(applied)),
                                 "exp_avg": train_step.exp_avg[o:o + k].view(shp).detach().cpu().clone(),
@@ -158,6 +217,10 @@ def export_checkpoint(model, train_step=None, epoch: int = 1, stat_dict: Optiona
                             "skip_nonfinite": oo["skip_nonfinite"], "skipped_steps": skipped}
     if train_step is not None and _pixel_loss(train_step) is not None:
         out["m2t_loss"] = _pixel_loss(train_step)
+    if train_step is not None and _groups(train_step) is not None:
+        g = _groups(train_step)
+        out["m2t_groups"] = {"spec": g.spec, "groups": g.describe(), "lr": float(train_step.lr),
+                             "weight_decay": oo["weight_decay"], "decoupled_weight_decay": oo["decoupled_weight_decay"]}
     return out
 
 
@@ -214,6 +277,8 @@ def import_checkpoint(ckpt: dict, model, train_step=None) -> int:
         train_step.scheduler_last_epoch = 0
         _reset_optim_state(train_step, model, ckpt.get("ema_state_dict"))
         return 1
+    _check_groups(ckpt, train_step)
+    groups, mg = _groups(train_step), ckpt.get("m2t_groups")
     if sch is None:
         # Adam state without the schedule it belongs to: the reference's --resume (train.py:97-103) always loads both, and
         # continuing epoch-N moments / learning rate on a schedule restarted at 0 would silently train something else
@@ -221,11 +286,16 @@ def import_checkpoint(ckpt: dict, model, train_step=None) -> int:
                          "train.py:341-349; pass the model weights alone (a --pretrain load) or a complete checkpoint")
     if opt.get("state"):
         idx = _param_index(model)
+        if groups is not None:                                            # torch numbers the parameters through the groups in order
+            idx = {n: i for i, n in enumerate(n for names in _torch_group_names(model, groups) for n in names)}
         st = opt["state"]
         step = 0
         for n, (o, k, shp) in zip(model._names, model._slots):
             s = st.get(idx[n]) or st.get(str(idx[n]))
             if s is None:
+                if groups is not None:                                    # no state entry = zero moments (a frozen tensor)
+                    train_step.exp_avg[o:o + k].zero_()
+                    train_step.exp_avg_sq[o:o + k].zero_()
                 continue
             train_step.exp_avg[o:o + k].copy_(s["exp_avg"].reshape(-1).to(train_step.exp_avg))
             train_step.exp_avg_sq[o:o + k].copy_(s["exp_avg_sq"].reshape(-1).to(train_step.exp_avg_sq))
@@ -238,15 +308,20 @@ def import_checkpoint(ckpt: dict, model, train_step=None) -> int:
         train_step.exp_avg_sq.zero_()
         train_step.step_count = 0
     pg = opt.get("param_groups")
-    if pg:
+    if mg is not None:
+        train_step.set_lr(mg["lr"])                                       # the step's own rate: each group's is lr * lr_scale
+    elif pg:
         train_step.set_lr(pg[0]["lr"])
     mo = ckpt.get("m2t_optim")
     wd = float(pg[0].get("weight_decay", 0.0) or 0.0) if pg else 0.0
+    if mg is not None:                                                    # (torch's groups carry each group's decay; the step's own:)
+        wd = float(mg["weight_decay"])
     if mo is not None or wd != 0.0:
         # the options the run was saved with (a file without them leaves the TrainStep's own untouched)
         mo = mo or {}
         new = {"max_grad_norm": mo.get("max_grad_norm", getattr(train_step, "max_grad_norm", None)), "weight_decay": wd,
-               "decoupled_weight_decay": bool(pg[0].get("decoupled_weight_decay", False)) if pg else False,
+               "decoupled_weight_decay": bool(mg["decoupled_weight_decay"]) if mg is not None else
+                                         bool(pg[0].get("decoupled_weight_decay", False)) if pg else False,
                "ema_decay": mo.get("ema_decay", getattr(train_step, "ema_decay", None)),
                "skip_nonfinite": bool(mo.get("skip_nonfinite", getattr(train_step, "skip_nonfinite", False)))}
         if new != _optim_options(train_step):

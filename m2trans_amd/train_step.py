@@ -58,6 +58,15 @@ Information-fidelity term (``lambda_vif``; the reference imports VIFLoss from pi
 term may be negative; it is not clipped.  It takes the MATERIALISED seed like the other terms; the calls run in the order
 pixel -> SSIM -> MS-SSIM -> FFT -> VIF (each if on) -> backward.  With lambda_vif = 0 (the default) nothing is allocated and the
 step issues the calls it issued before.
+
+Parameter groups and frozen tensors (``param_groups=``; replaces ``torch.optim.Adam([{"params": ..., "lr": ...,
+"weight_decay": ...}, ...])`` over a model part of which has ``requires_grad = False``; param_groups.py resolves the spec by name):
+a group has its own ``lr_scale`` and ``weight_decay`` and may be ``frozen``.  The flat buffer is described by a segment table that
+is uploaded ONCE at construction; each step hands the groups' values over by value: m2t_grad_norm_groups (the norm over the
+trainable elements) and ONE m2t_adam_step_groups pass (include/m2t_groups.h), which neither read nor write a frozen element.  When
+a whole stage (head / body.b / tail) is frozen, every route of forward_backward calls m2t_backward_ex with the stage flags instead
+of m2t_backward.  ``param_groups="requires_grad"`` freezes the trainable tensors whose ``requires_grad`` is False.  With
+``param_groups=None`` (the default) nothing is allocated and the step issues the calls it issued before.
 """
 from __future__ import annotations
 
@@ -70,6 +79,7 @@ import torch
 from . import _lib
 from .dist import GradBucket, global_divisor
 from .M2Trans_network import M2Trans
+from .param_groups import resolve_param_groups
 
 
 def cosine_lr(epoch: int, lr0: float = 1e-4, eta_min: float = 1e-6, t_max: float = 200.0) -> float:
@@ -204,6 +214,8 @@ class TrainStep:
     # (defaults of the newest term for step objects assembled without __init__)
     lambda_vif = 0.0
     vif_loss = None
+    groups = None
+    _need_stage = None
 
     def __init__(self, model: M2Trans, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  lambda_l1: float = 1.0, process_group=None, world_size: Optional[int] = None,
@@ -213,8 +225,11 @@ class TrainStep:
                  decoupled_weight_decay: bool = False, ema_decay: Optional[float] = None, skip_nonfinite: bool = False,
                  track_grad_norm: bool = False, pixel_loss: str = "l1", pixel_loss_param: Optional[float] = None,
                  lambda_ssim: float = 0.0, lambda_fft: float = 0.0, fft_norm: str = "backward",
-                 lambda_msssim: float = 0.0, lambda_vif: float = 0.0):
+                 lambda_msssim: float = 0.0, lambda_vif: float = 0.0, param_groups=None):
         self.model = model
+        # parameter groups / frozen tensors (param_groups.py): resolved against the model's names here, on the host, fixed for the
+        # life of this object.  None (the default): nothing is allocated and the step issues the calls it always issued
+        self.groups = resolve_param_groups(model, param_groups)
         # the pixel term: lambda_l1 (the reference's config key) stays its weight and l1_loss the tensor that holds it, whatever the kind
         self.set_pixel_loss(pixel_loss, pixel_loss_param)
         # the structural term lambda_ssim * (1 - mean SSIM): 0 = off (nothing allocated, the step issues the calls it always issued)
@@ -268,7 +283,9 @@ class TrainStep:
         self.l1_loss = torch.zeros(1, dtype=torch.float32, device=flat.device)
         self.loss = self.l1_loss
         # where micro-batches 2..k of a cycle put their gradients and their L1 loss (nothing is allocated for accum_steps = 1)
-        self.micro_grads = torch.empty_like(self.grads) if self.accum_steps > 1 else None
+        # (with frozen tensors a partial backward pass never writes their ranges: zeros, not stale memory, for whoever looks at them)
+        frozen_any = self.groups is not None and self.groups.any_frozen
+        self.micro_grads = (torch.zeros_like(self.grads) if frozen_any else torch.empty_like(self.grads)) if self.accum_steps > 1 else None
         self.micro_loss = torch.zeros(1, dtype=torch.float32, device=flat.device) if self.accum_steps > 1 else None
         # force_comm_path: build the exchange machinery even for one rank (tests exercise the stream / event logic)
         self.bucket = GradBucket(self.grads, process_group, grad_bucket_dtype, force=force_comm_path,
@@ -282,6 +299,36 @@ class TrainStep:
         self.measure_exposed_comm = False
         self.exposed_comm_events = []
         self._init_optim_options(max_grad_norm, weight_decay, decoupled_weight_decay, ema_decay, skip_nonfinite, track_grad_norm)
+        self._init_groups()
+
+    def _init_groups(self):
+        """The device copy of the segment table (uploaded ONCE, here), the frozen flags and the stage flags of the backward pass."""
+        self._group_table = self._group_frozen = self._need_stage = None
+        g = self.groups
+        if g is None:
+            return
+        flat = self.model.flat_params
+        if flat.numel() != g.n:
+            raise _lib.M2TError(f"param_groups: resolved for {g.n} elements, the flat buffer holds {flat.numel()}")
+        self._group_table = torch.frombuffer(bytearray(g.pack()), dtype=torch.uint8).to(flat.device)
+        self._group_frozen = (C.c_ubyte * g.n_groups)(*[1 if f else 0 for f in g.frozen])
+        if not all(g.stage_flags):
+            # a stage with any trainable tensor still computes all its gradients; a stage without one does no parameter-gradient work
+            self._need_stage = (C.c_ubyte * len(g.stage_flags))(*[1 if f else 0 for f in g.stage_flags])
+        if g.any_frozen:
+            self.grads.zero_()
+
+    def _backward_call(self, lib, plan, lr_img, grads, ws, st):
+        """m2t_backward, or -- when a whole stage is frozen -- m2t_backward_ex with the stage flags of the groups.  A deferred pixel
+        loss survives a partial pass: it is taken in front of the first fork (or inside the fused tail backward, which runs for
+        its data gradient whatever the tail's flag says) before any stage flag is looked at."""
+        m = self.model
+        if self._need_stage is None:
+            _lib.check(lib.m2t_backward(plan.handle, _lib.ptr(m.flat_params), _lib.ptr(lr_img), _lib.ptr(grads),
+                                        ws, st), "m2t_backward")
+            return
+        _lib.check(lib.m2t_backward_ex(plan.handle, _lib.ptr(m.flat_params), _lib.ptr(lr_img), _lib.ptr(grads), None,
+                                       self._need_stage, ws, st), "m2t_backward_ex")
 
     def _init_optim_options(self, max_grad_norm, weight_decay, decoupled_weight_decay, ema_decay, skip_nonfinite, track_grad_norm):
         """Gradient-norm clipping, weight decay, EMA weights and the non-finite skip (m2t_grad_norm + m2t_adam_step_ex).  With
@@ -569,8 +616,7 @@ class TrainStep:
             if vif:
                 self._vif_loss_call(lib, plan, hr_img, first, ws, st)
             fwd_done = torch.cuda.current_stream(lr_img.device).record_event() if (use_clip and self.overlap_semantic) else None
-            _lib.check(lib.m2t_backward(plan.handle, _lib.ptr(m.flat_params), _lib.ptr(lr_img), _lib.ptr(grads),
-                                        ws, st), "m2t_backward")
+            self._backward_call(lib, plan, lr_img, grads, ws, st)
             self._accumulate_micro(lib, first, st)
         if use_clip:
             # clip_loss += loss_clip(sr[i], hr[i], caption_i) * lambda_clip  (train.py:203-205); no gradient
@@ -641,8 +687,7 @@ class TrainStep:
                 arr = (C.c_int * (2 * len(origins)))(*[int(v) for o in origins for v in o])
             _lib.check(lib.m2t_add_output_grad(plan.handle, _lib.ptr(g), g.shape[2], g.shape[3], arr, self.lambda_clip,
                                                float(m.rgb_range), ws, st), "m2t_add_output_grad")
-            _lib.check(lib.m2t_backward(plan.handle, _lib.ptr(m.flat_params), _lib.ptr(lr_img), _lib.ptr(grads),
-                                        ws, st), "m2t_backward")
+            self._backward_call(lib, plan, lr_img, grads, ws, st)
             first = grads is self.grads
             self._accumulate_micro(lib, first, st)
         self._add_clip(tot * self.lambda_clip, first)
@@ -705,6 +750,9 @@ class TrainStep:
         self.step_count += 1
         lib = _lib.load()
         with torch.cuda.device(self.grads.device):
+            if self.groups is not None:
+                self._optimizer_step_groups(lib, _lib.stream_ptr())
+                return
             if self._optim_ex:
                 self._optimizer_step_ex(lib, _lib.stream_ptr())
                 return
@@ -727,6 +775,26 @@ class TrainStep:
                                         self.step_count, 1.0, _lib.ptr(self.ema_params), self.weight_decay,
                                         int(self.decoupled_weight_decay), self.ema_decay or 0.0, _lib.ptr(self.optim_record), st),
                    "m2t_adam_step_ex")
+
+    def _optimizer_step_groups(self, lib, st):
+        """The step with parameter groups: the norm over the trainable elements (if clip / skip / track is on) into the record,
+        then ONE grouped pass.  Each group's lr / weight decay is evaluated here in Python floats and travels by value; the table
+        is the device copy made at construction.  Nothing reads a frozen range of the gradient buffer."""
+        g = self.groups
+        n, ng = self.grads.numel(), g.n_groups
+        table = _lib.ptr(self._group_table)
+        if self._use_norm:
+            _lib.check(lib.m2t_grad_norm_groups(_lib.ptr(self.grads), n, 1.0, self.max_grad_norm or 0.0, int(self.skip_nonfinite),
+                                                self.step_count, self.betas[0], self.betas[1], _lib.ptr(self.optim_record),
+                                                _lib.ptr(self._norm_ws), self._group_frozen, ng, table, g.n_seg, st),
+                       "m2t_grad_norm_groups")
+        lrs = (C.c_float * ng)(*g.group_lr(self.lr))
+        wds = (C.c_float * ng)(*g.group_weight_decay(self.weight_decay))
+        _lib.check(lib.m2t_adam_step_groups(_lib.ptr(self.model.flat_params), _lib.ptr(self.grads), _lib.ptr(self.exp_avg),
+                                            _lib.ptr(self.exp_avg_sq), n, lrs, self.betas[0], self.betas[1], self.eps,
+                                            self.step_count, 1.0, _lib.ptr(self.ema_params), wds, int(self.decoupled_weight_decay),
+                                            self.ema_decay or 0.0, _lib.ptr(self.optim_record), self._group_frozen, ng, table,
+                                            g.n_seg, st), "m2t_adam_step_groups")
 
     # -- the step ----------------------------------------------------------------------------
     def step(self, lr_img: torch.Tensor, hr_img: torch.Tensor, captions=None) -> torch.Tensor:
