@@ -1,5 +1,5 @@
 """ctypes binding of libm2t.so (include/m2t.h, include/m2t_spectral.h, include/m2t_resize.h, include/m2t_msssim.h,
-include/m2t_vif.h, include/m2t_groups.h).
+include/m2t_vif.h, include/m2t_groups.h, include/m2t_perceptual.h).
 
 The product path has NO fallback: if the HIP library is missing, or a call fails, this
 module raises.  Build it with ``python -m m2trans_amd.build`` (hipcc, gfx950).
@@ -139,6 +139,29 @@ GROUPS_SIGNATURES = {
 MAX_GROUPS = 8                                                 # M2T_MAX_GROUPS
 MAX_SEGMENTS = 1024                                            # M2T_MAX_SEGMENTS
 
+# the seventh header, include/m2t_perceptual.h (the VGG19 feature loss), bound on the same library; must list every symbol that header
+# declares.  The six tables above stay as they are.
+PERCEPTUAL_SIGNATURES = {
+    "m2t_vgg_create": (_i, [C.POINTER(_vp), _i]),
+    "m2t_vgg_destroy": (None, [_vp]),
+    "m2t_vgg_query": (_ll, [_vp, C.c_char_p]),
+    "m2t_vgg_param_name": (C.c_char_p, [_vp, _i]),
+    "m2t_vgg_load_weights": (_i, [_vp, _vp, _vp, _vp]),
+    "m2t_vgg_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
+    "m2t_vgg_workspace_offset": (C.c_size_t, [_i, _i, _i, _i, _i]),
+    "m2t_vgg_loss_tensor": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _ll, _i, _f, _i, _i, _f, C.POINTER(_d), _d, _vp, _vp, _vp, _i, _vp, _vp]),
+    "m2t_vgg_loss": (_i, [_vp, _vp, _vp, _f, _d, _f, _i, _f, C.POINTER(_d), _vp, _i, _vp, _vp, _vp]),
+    "m2t_vgg_conv_forward": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "m2t_vgg_conv_backward": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "m2t_vgg_pool_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "m2t_vgg_pool_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+}
+VGG_MIN_SIDE = 16                                              # min(H, W) >= 16: relu5_1 is then 1 x 1
+VGG_LAYERS = (0, 2, 5, 7, 10, 12, 14, 16, 19, 21, 23, 25, 28)  # torchvision vgg19: features.<i> of the 13 convolutions up to conv5_1
+VGG_CHANNELS = (64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 512, 512, 512)
+VGG_LEVEL = (0, 0, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4)            # 2 x 2 pools before the layer
+VGG_TAP_LAYERS = (0, 2, 4, 8, 12)                              # relu1_1, relu2_1, relu3_1, relu4_1, relu5_1
+
 _lib = None
 
 
@@ -161,7 +184,8 @@ def load():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) \
-            + list(MSSSIM_SIGNATURES.items()) + list(VIF_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()):
+            + list(MSSSIM_SIGNATURES.items()) + list(VIF_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()) \
+            + list(PERCEPTUAL_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

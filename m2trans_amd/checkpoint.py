@@ -31,7 +31,9 @@ key is absent and the dict is the one described above, byte for byte.  TrainStep
 ``"fft_norm"`` to the entry in the same way (``import_checkpoint`` calls ``set_lambda_fft``); with lambda_fft = 0 neither key is
 written.  TrainStep(lambda_msssim > 0) adds ``"lambda_msssim"`` in the same way (``import_checkpoint`` calls ``set_lambda_msssim``);
 with lambda_msssim = 0 the key is absent.  TrainStep(lambda_vif > 0) adds ``"lambda_vif"`` after the other keys in the same way
-(``import_checkpoint`` calls ``set_lambda_vif``); with lambda_vif = 0 the key is absent.
+(``import_checkpoint`` calls ``set_lambda_vif``); with lambda_vif = 0 the key is absent.  TrainStep(lambda_perceptual > 0) adds ``"lambda_perceptual"``,
+``"perceptual_criterion"``, ``"perceptual_weights"`` and ``"perceptual_resize"`` (never the VGG19 weights; ``import_checkpoint`` sets them
+on the step's ``perceptual_loss`` object and calls ``set_lambda_perceptual``); with lambda_perceptual = 0 the keys are absent.
 
 With TrainStep(param_groups=...) the optimizer dict comes from a real ``torch.optim.Adam`` with ONE TORCH PARAM GROUP PER GROUP, each
 carrying its own ``lr`` (= step.lr * lr_scale) and ``weight_decay``; the parameter ids run through the groups in order (torch's own
@@ -112,7 +114,8 @@ def _pixel_loss(train_step):
     lam_fft = float(getattr(train_step, "lambda_fft", 0.0) or 0.0)
     lam_ms = float(getattr(train_step, "lambda_msssim", 0.0) or 0.0)
     lam_vif = float(getattr(train_step, "lambda_vif", 0.0) or 0.0)
-    if canon == "l1" and lam == 0.0 and lam_fft == 0.0 and lam_ms == 0.0 and lam_vif == 0.0:
+    lam_perc = float(getattr(train_step, "lambda_perceptual", 0.0) or 0.0)
+    if canon == "l1" and lam == 0.0 and lam_fft == 0.0 and lam_ms == 0.0 and lam_vif == 0.0 and lam_perc == 0.0:
         return None
     out = {"pixel_loss": canon, "param": value}
     if lam != 0.0:
@@ -124,6 +127,13 @@ def _pixel_loss(train_step):
         out["fft_norm"] = str(getattr(train_step, "fft_norm", "backward"))
     if lam_vif != 0.0:
         out["lambda_vif"] = lam_vif
+    if lam_perc != 0.0:
+        # the settings of the term, never the VGG19 weights (an integrator loads those: INTEGRATION.md)
+        p = train_step.perceptual_loss
+        out["lambda_perceptual"] = lam_perc
+        out["perceptual_criterion"] = str(p.criterion)
+        out["perceptual_weights"] = [float(w) for w in p.weights]
+        out["perceptual_resize"] = bool(p.resize)
     return out
 
 
@@ -259,6 +269,15 @@ def import_checkpoint(ckpt: dict, model, train_step=None) -> int:
             else:
                 from .train_step import resolve_lambda_vif
                 train_step.lambda_vif = resolve_lambda_vif(ml["lambda_vif"])
+        if "lambda_perceptual" in ml:
+            p = getattr(train_step, "perceptual_loss", None)
+            if p is None:
+                from ._lib import M2TError
+                raise M2TError("import_checkpoint: the file was saved with lambda_perceptual > 0; build the TrainStep with "
+                               "perceptual_loss= (a losses.PerceptualLoss with VGG19 weights loaded: the file carries none)")
+            p.configure(ml.get("perceptual_weights", p.weights), ml.get("perceptual_criterion", p.criterion),
+                        ml.get("perceptual_resize", p.resize))
+            train_step.set_lambda_perceptual(ml["lambda_perceptual"])
         if "lambda_fft" in ml:
             if hasattr(train_step, "set_lambda_fft"):
                 train_step.set_lambda_fft(ml["lambda_fft"], ml.get("fft_norm"))

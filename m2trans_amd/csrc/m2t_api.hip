@@ -10,6 +10,7 @@
 #include "../../include/m2t_spectral.h"
 #include "../../include/m2t_msssim.h"
 #include "../../include/m2t_vif.h"
+#include "../../include/m2t_perceptual.h"
 
 static thread_local std::string g_err;
 int m2t_set_hip_error(hipError_t e, const char* file, int line) {
@@ -761,6 +762,27 @@ extern "C" int m2t_vif_loss(m2t_plan* p, const float* hr, float weight, double d
   return launch_vif_loss((const float*)(ws + p->hd.srpre), hr, p->B, 3, p->Hs, p->Ws, 3LL * p->Hsp * p->Wsp, p->Wsp, rgb_range, sigma_n_sq,
                          1, (double)weight / divisor, (float*)(ws + p->hd.gpre), loss_out, nullptr, accumulate ? 1 : 0, scratch,
                          (hipStream_t)stream);
+}
+
+// weight * sum_k w_k mean(rho(F_k(sr) - F_k(hr))) on VGG19 features (k_vgg.hip, m2t_vgg.hip; include/m2t_perceptual.h) on the forward's
+// pre-clamp output, added into the materialised seed: the routine of m2t_vgg_loss_tensor on ws:srpre and ws:gpre.  State rules of
+// m2t_ssim_loss.  The tower's workspace is the caller's: no plan option, no workspace region.
+extern "C" int m2t_vgg_loss(m2t_plan* p, const m2t_vgg* v, const float* hr, float weight, double divisor, float rgb_range, int kind,
+                            float param, const double* tap_weights, float* loss_out, int accumulate, void* vgg_workspace, void* workspace,
+                            void* stream) {
+  if (!p || !v || !hr || !loss_out || !vgg_workspace || !workspace) return m2t_set_error(M2T_ERR_ARG, "m2t_vgg_loss: null argument");
+  if (!(divisor > 0.0) || !std::isfinite(divisor)) return m2t_set_error(M2T_ERR_ARG, "m2t_vgg_loss: divisor must be a finite number > 0");
+  if (int rc = vgg_check_common("m2t_vgg_loss", tap_weights, (double)weight, rgb_range, kind, param)) return rc;
+  if (!vgg_size_supported(p->Hs, p->Ws))
+    return m2t_set_error(M2T_ERR_ARG, "m2t_vgg_loss: the SR height and width must be at least 16 (four 2 x 2 pools before relu5_1)");
+  if (p->B > 32767) return m2t_set_error(M2T_ERR_ARG, "m2t_vgg_loss: batch too large (B <= 32767)");
+  if (!vgg_loaded(v)) return m2t_set_error(M2T_ERR_STATE, "m2t_vgg_loss: call m2t_vgg_load_weights first (no VGG19 weights ship with the library)");
+  if (!p->have_acts || !p->have_seed || p->l1_deferred)
+    return m2t_set_error(M2T_ERR_STATE, "m2t_vgg_loss: needs a materialised seed (m2t_l1_loss / m2t_pixel_loss or m2t_set_output_grad)");
+  char* const ws = (char*)workspace;
+  return launch_vgg_loss(v, (const float*)(ws + p->hd.srpre), hr, p->B, 3, p->Hs, p->Ws, 3LL * p->Hsp * p->Wsp, p->Wsp, rgb_range, 1, kind,
+                         param, tap_weights, (double)weight, divisor, (float*)(ws + p->hd.gpre), loss_out, nullptr, accumulate ? 1 : 0,
+                         vgg_workspace, (hipStream_t)stream);
 }
 
 // weight * mean |rfft2(d)| (k_fft_loss.hip; include/m2t_spectral.h) on the forward's pre-clamp output, added into the materialised

@@ -361,3 +361,31 @@ bool fft_loss_size_supported(int H, int W);
 size_t fft_loss_scratch_bytes(int B, int C, int H, int W);
 int launch_fft_loss(const float* x, const float* y, int B, int C, int H, int W, long long xs_img, int xs_row, float R, int clamp, int norm,
                     double scale, float* gx_add, float* loss_out, int accumulate, void* scratch, hipStream_t st);
+// ---- k_vgg.hip (the VGG19 feature loss: include/m2t_perceptual.h, host layer m2t_vgg.hip) ----------
+// bf16 NHWC activations, packed bf16 weights [Cout / 64][Cin / 32][9][64][32]; Cin and Cout multiples of 64.  epi 0: bias + ReLU;
+// epi 1 (data gradient on flipped, transposed weights): + sd.gscale * rho'(mask - ytap) where ytap != nullptr, times [mask > 0] where
+// mask != nullptr.  Arguments are checked by the callers.
+int launch_vgg_conv(int epi, const void* in, const void* wpk, void* out, int N, int H, int W, int Cin, int Cout, const float* bias,
+                    const void* mask, const void* ytap, const M2TPixelLoss& sd, hipStream_t st);
+int launch_vgg_pack(const float* w, void* dst, int Cout, int Cin, int flip, hipStream_t st);
+int launch_vgg_pack_first(const float* w, float* dst, hipStream_t st);
+// conv1_1 on (c(x) / R - mean) / std (chs = channel stride, 0 repeats one channel) and its data gradient, added into gx
+int launch_vgg_first_fwd(const float* x, long long img, long long chs, int row, float R, int clamp, const float* w0, const float* bias,
+                         void* out, int N, int H, int W, hipStream_t st);
+int launch_vgg_first_bwd(const void* g, const float* w0, const float* x, float* gx, long long img, long long chs, int row, float R, int clamp,
+                         int N, int H, int W, hipStream_t st);
+int launch_vgg_pool_fwd(const void* in, void* out, int N, int H, int W, int C, hipStream_t st);
+int launch_vgg_pool_bwd(const void* a, const void* gout, void* gin, int N, int H, int W, int C, int relu, hipStream_t st);
+int vgg_tap_blocks(long long n_elems);
+int launch_vgg_tap_partial(const void* fx, const void* fy, long long n_elems, const M2TPixelLoss& sd, double* part, hipStream_t st);
+int launch_vgg_finish(const double* part, const int* nblk, const double* wn, const double* inv_n, int accumulate, float* loss_out,
+                      double* per_tap_out, hipStream_t st);
+int launch_vgg_tap_seed(const void* fx, const void* fy, long long n_elems, const M2TPixelLoss& sd, void* gout, hipStream_t st);
+// ---- m2t_vgg.hip: the routine behind m2t_vgg_loss_tensor and m2t_vgg_loss (tap k's mean divides by divisor * C_k H_k W_k) ----------
+struct m2t_vgg;
+bool vgg_loaded(const m2t_vgg* v);
+bool vgg_size_supported(int H, int W);
+int vgg_check_common(const char* who, const double* tw, double scale, float R, int kind, float param);
+int launch_vgg_loss(const m2t_vgg* v, const float* x, const float* y, int B, int C, int H, int W, long long xs_img, int xs_row, float R,
+                    int clamp, int kind, float param, const double* tw, double scale, double divisor, float* gx_add, float* loss_out,
+                    double* per_tap_out, int accumulate, void* workspace, hipStream_t st);

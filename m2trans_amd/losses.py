@@ -740,3 +740,188 @@ class FFTLoss(nn.Module):
 
     def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         return fft_loss(x, y, self.data_range, self.norm)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The VGG19 feature ("perceptual") term: PerceptualLoss of the reference's losses.py:222-270.  Value and gradient are HIP
+# (m2t_vgg_loss_tensor of include/m2t_perceptual.h; k_vgg.hip, m2t_vgg.hip: bf16 MFMA convolutions); there is no torch fallback.
+# Inference semantics: plain vgg19 weights, or vgg19_bn weights folded on the host in fp64; training-mode batch statistics are not
+# reproduced.  No weights ship: load_vgg_state_dict first.
+# ---------------------------------------------------------------------------------------------------------------
+PERCEPTUAL_CRITERIA = {"l1": (0, 0.0), "sl1": (3, 1.0), "l2": (1, 0.0)}     # (M2T_LOSS_* kind, param); nn.SmoothL1Loss: beta = 1
+_VGG19_BN_CONVS = (0, 3, 7, 10, 14, 17, 20, 23, 27, 30, 33, 36, 40)         # torchvision vgg19_bn: features.<i> of the same convolutions
+
+
+def vgg_param_names() -> List[str]:
+    """The 26 tensors the tower takes, torchvision ``vgg19`` naming, in flat order."""
+    return [f"features.{i}.{k}" for i in _lib.VGG_LAYERS for k in ("weight", "bias")]
+
+
+def _vgg_strip(key: str) -> str:
+    for prefix in ("module.", "vgg."):
+        if key.startswith(prefix):
+            key = key[len(prefix):]
+    if not key.startswith("features.") and key[:1].isdigit():
+        key = "features." + key
+    return key
+
+
+def vgg_fold_state_dict(state: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """A ``vgg19`` or ``vgg19_bn`` state dict (keys with or without a ``features.`` / ``vgg.`` prefix; classifier and deeper layers
+    ignored) -> the 26 float32 tensors under ``vgg19`` names.  Batch norm is folded in fp64 with its running statistics (eval mode):
+    w' = w * gamma / sqrt(var + eps), b' = (b - mean) * gamma / sqrt(var + eps) + beta, eps = 1e-5."""
+    sd = {_vgg_strip(k): v for k, v in state.items()}
+    is_bn = any(k.endswith("running_mean") for k in sd)
+    out = {}
+    for plain, bn in zip(_lib.VGG_LAYERS, _VGG19_BN_CONVS):
+        src = bn if is_bn else plain
+        try:
+            w = sd[f"features.{src}.weight"].detach().double().cpu()
+            b = sd[f"features.{src}.bias"].detach().double().cpu()
+            if is_bn:
+                g, beta = sd[f"features.{src + 1}.weight"].detach().double().cpu(), sd[f"features.{src + 1}.bias"].detach().double().cpu()
+                mean, var = sd[f"features.{src + 1}.running_mean"].detach().double().cpu(), sd[f"features.{src + 1}.running_var"].detach().double().cpu()
+                s = g / torch.sqrt(var + 1e-5)
+                w, b = w * s.view(-1, 1, 1, 1), (b - mean) * s + beta
+        except KeyError as e:
+            raise M2TError(f"load_vgg_state_dict: missing {e.args[0]} ({'vgg19_bn' if is_bn else 'vgg19'} naming)") from None
+        if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or b.shape[0] != w.shape[0]:
+            raise M2TError(f"load_vgg_state_dict: features.{src} is not a 3x3 convolution: {tuple(w.shape)}")
+        out[f"features.{plain}.weight"], out[f"features.{plain}.bias"] = w.float(), b.float()
+    return out
+
+
+class _PerceptualFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, mod):
+        out, ctx.grad = mod._call(x, y, ctx.needs_input_grad[0])
+        ctx.x_dtype = x.dtype
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        return (ctx.grad * g).to(ctx.x_dtype), None, None
+
+
+class PerceptualLoss(nn.Module):
+    """The reference's ``PerceptualLoss(weights, resize, criterion)`` plus ``data_range``: ``sum_k weights[k] * crit(F_k(x), F_k(y))`` on
+    VGG19's relu1_1, relu2_1, relu3_1, relu4_1, relu5_1 of ``((t / data_range) - mean) / std`` (one channel repeated to three; inputs
+    not clamped), ``crit`` the mean L1 / smooth-L1 / L2.  ``resize=True`` takes both images to 224 x 224 first (bicubic,
+    align_corners).  bf16 compute; differentiable with respect to ``x`` only.  Call ``load_vgg_state_dict`` first."""
+
+    def __init__(self, weights=(1.0, 1.0, 1.0, 1.0, 1.0), resize: bool = False, criterion: str = "l1", data_range: float = 1.0, device=None):
+        super().__init__()
+        if criterion not in PERCEPTUAL_CRITERIA:
+            raise NotImplementedError("Loss [{}] is not implemented".format(criterion))
+        weights = [float(w) for w in weights]
+        if len(weights) != 5 or not all(math.isfinite(w) for w in weights):
+            raise M2TError(f"PerceptualLoss: weights must be five finite numbers (relu1_1 .. relu5_1), got {weights!r}")
+        if not (math.isfinite(float(data_range)) and float(data_range) > 0.0):
+            raise M2TError(f"PerceptualLoss: data_range must be a finite number > 0, got {data_range!r}")
+        self.weights, self.resize, self.criterion, self.data_range = weights, bool(resize), criterion, float(data_range)
+        self.kind, self.param = PERCEPTUAL_CRITERIA[criterion]
+        self.device = torch.device(device) if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
+        h = C.c_void_p()
+        _lib.check(_lib.load().m2t_vgg_create(C.byref(h), _lib.BF16), "m2t_vgg_create")
+        self.handle = h
+        self.flat = self.packed = None
+        self._ws: Dict[tuple, torch.Tensor] = {}
+
+    @property
+    def loaded(self) -> bool:
+        return self.packed is not None
+
+    def configure(self, weights, criterion: str, resize: bool):
+        """Replace the tap weights, the criterion and the resize flag (checkpoint.import_checkpoint); the tower's weights stay."""
+        if criterion not in PERCEPTUAL_CRITERIA:
+            raise NotImplementedError("Loss [{}] is not implemented".format(criterion))
+        weights = [float(w) for w in weights]
+        if len(weights) != 5 or not all(math.isfinite(w) for w in weights):
+            raise M2TError(f"PerceptualLoss: weights must be five finite numbers (relu1_1 .. relu5_1), got {weights!r}")
+        self.weights, self.resize, self.criterion = weights, bool(resize), criterion
+        self.kind, self.param = PERCEPTUAL_CRITERIA[criterion]
+
+    def tap_weights(self):
+        return (C.c_double * 5)(*self.weights)
+
+    def query(self, key: str) -> int:
+        return int(_lib.load().m2t_vgg_query(self.handle, key.encode()))
+
+    def load_vgg_state_dict(self, sd: Dict[str, torch.Tensor]):
+        folded = vgg_fold_state_dict(sd)
+        if self.device.type != "cuda":
+            raise M2TError("PerceptualLoss needs a HIP device (there is no host implementation)")
+        lib = _lib.load()
+        flat = torch.zeros(self.query("num_params"), dtype=torch.float32, device=self.device)
+        for i in range(self.query("num_param_tensors")):
+            n = lib.m2t_vgg_param_name(self.handle, i).decode()
+            o, cnt = self.query("param:" + n), self.query("numel:" + n)
+            if folded[n].numel() != cnt:
+                raise M2TError(f"load_vgg_state_dict: shape mismatch for {n}: {tuple(folded[n].shape)}")
+            flat[o:o + cnt].copy_(folded[n].reshape(-1))
+        packed = torch.empty(self.query("packed_bytes"), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(lib.m2t_vgg_load_weights(self.handle, _lib.ptr(flat), _lib.ptr(packed), _lib.stream_ptr()), "m2t_vgg_load_weights")
+        self.flat, self.packed = flat, packed
+        return self
+
+    def workspace(self, B: int, H: int, W: int, want_grad: bool) -> torch.Tensor:
+        """The device workspace of one shape, cached."""
+        key = (B, H, W, bool(want_grad))
+        if key not in self._ws:
+            nbytes = _lib.load().m2t_vgg_workspace_bytes(B, H, W, 1 if want_grad else 0)
+            if nbytes == 0:
+                raise M2TError(f"PerceptualLoss: no workspace for [{B},*,{H},{W}] (height and width at least {_lib.VGG_MIN_SIDE}, B at most 32767)")
+            self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._ws[key]
+
+    def check(self, x, y):
+        if x.dim() != 4 or x.shape != y.shape:
+            raise M2TError(f"PerceptualLoss: expected two [B,C,H,W] tensors of equal shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+        if int(x.shape[1]) not in (1, 3):
+            raise M2TError(f"PerceptualLoss: 1 or 3 channels, got {int(x.shape[1])}")
+        H, W = (224, 224) if self.resize else (int(x.shape[2]), int(x.shape[3]))
+        if min(H, W) < _lib.VGG_MIN_SIDE or min(int(x.shape[2]), int(x.shape[3])) < 1:
+            raise M2TError(f"PerceptualLoss: image {H}x{W} is too small (height and width must be at least {_lib.VGG_MIN_SIDE}: four pools before relu5_1)")
+        if not self.loaded:
+            raise M2TError("PerceptualLoss: no VGG19 weights loaded (none ship with the library): call load_vgg_state_dict first")
+        if not (x.is_cuda and y.is_cuda):
+            raise M2TError("PerceptualLoss needs HIP device tensors (there is no host implementation)")
+        if y.requires_grad:
+            raise M2TError("PerceptualLoss gives the gradient with respect to x only: y must not require grad (detach it)")
+
+    def _call(self, x, y, want_grad):
+        """(loss [1] float32, gradient or None) of device tensors [B,C,H,W]."""
+        lib = _lib.load()
+        xc, yc = x.detach().contiguous().float(), y.detach().contiguous().float()
+        B, Cn, H, W = xc.shape
+        with torch.cuda.device(xc.device):
+            st = _lib.stream_ptr()
+            xs, ys, Ht, Wt = xc, yc, H, W
+            if self.resize:
+                Ht = Wt = 224
+                xs, ys = torch.empty(B, Cn, 224, 224, dtype=torch.float32, device=xc.device), torch.empty(B, Cn, 224, 224, dtype=torch.float32, device=xc.device)
+                _lib.check(lib.m2t_bicubic_resize(_lib.ptr(xc), _lib.ptr(xs), B * Cn, H, W, 224, 224, st), "m2t_bicubic_resize")
+                _lib.check(lib.m2t_bicubic_resize(_lib.ptr(yc), _lib.ptr(ys), B * Cn, H, W, 224, 224, st), "m2t_bicubic_resize")
+            out = torch.empty(1, dtype=torch.float32, device=xc.device)
+            gs = torch.zeros_like(xs) if want_grad else None
+            _lib.check(lib.m2t_vgg_loss_tensor(self.handle, _lib.ptr(xs), _lib.ptr(ys), B, Cn, Ht, Wt, Cn * Ht * Wt, Wt, self.data_range, 0,
+                                               self.kind, self.param, self.tap_weights(), 1.0, _lib.ptr(gs), _lib.ptr(out), None, 0,
+                                               _lib.ptr(self.workspace(B, Ht, Wt, want_grad)), st), "m2t_vgg_loss_tensor")
+            grad = gs
+            if want_grad and self.resize:
+                grad = torch.empty_like(xc)
+                _lib.check(lib.m2t_bicubic_resize_backward(_lib.ptr(gs), _lib.ptr(grad), B * Cn, H, W, 224, 224, st), "m2t_bicubic_resize_backward")
+        return out, grad
+
+    def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        self.check(x, y)
+        return _PerceptualFn.apply(x, y, self)
+
+    def __del__(self):
+        try:
+            if self.handle:
+                _lib.load().m2t_vgg_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass

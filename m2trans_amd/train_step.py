@@ -158,6 +158,22 @@ def resolve_lambda_vif(value) -> float:
     return v
 
 
+def resolve_lambda_perceptual(value) -> float:
+    """TrainStep's ``lambda_perceptual`` as a float; M2TError unless it is a finite number >= 0."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise _lib.M2TError(f"lambda_perceptual must be a finite number >= 0, got {value!r}") from None
+    if not (math.isfinite(v) and v >= 0.0):
+        raise _lib.M2TError(f"lambda_perceptual must be a finite number >= 0, got {value!r}")
+    return v
+
+
+def perceptual_size_supported(h: int, w: int) -> bool:
+    """The sizes the VGG19 feature term takes (the rule of include/m2t_perceptual.h, decided on the host): min(H, W) >= 16."""
+    return min(int(h), int(w)) >= _lib.VGG_MIN_SIDE
+
+
 def vif_size_supported(h: int, w: int) -> bool:
     """The sizes the information-fidelity term takes (the rule of include/m2t_vif.h, decided on the host): min(H, W) >= 41."""
     return min(int(h), int(w)) >= _lib.VIF_MIN_SIDE
@@ -214,6 +230,9 @@ class TrainStep:
     # (defaults of the newest term for step objects assembled without __init__)
     lambda_vif = 0.0
     vif_loss = None
+    lambda_perceptual = 0.0
+    perceptual_loss = None
+    perceptual_loss_value = None
     groups = None
     _need_stage = None
 
@@ -225,7 +244,8 @@ class TrainStep:
                  decoupled_weight_decay: bool = False, ema_decay: Optional[float] = None, skip_nonfinite: bool = False,
                  track_grad_norm: bool = False, pixel_loss: str = "l1", pixel_loss_param: Optional[float] = None,
                  lambda_ssim: float = 0.0, lambda_fft: float = 0.0, fft_norm: str = "backward",
-                 lambda_msssim: float = 0.0, lambda_vif: float = 0.0, param_groups=None):
+                 lambda_msssim: float = 0.0, lambda_vif: float = 0.0, param_groups=None, perceptual_loss=None,
+                 lambda_perceptual: float = 0.0):
         self.model = model
         # parameter groups / frozen tensors (param_groups.py): resolved against the model's names here, on the host, fixed for the
         # life of this object.  None (the default): nothing is allocated and the step issues the calls it always issued
@@ -249,6 +269,11 @@ class TrainStep:
         self.vif_loss = None                    # device float [1], already weighted (may be negative: VIF can exceed 1)
         self._vif_scratch = {}                  # (B, Hs, Ws) -> pyramids, gradient levels, partial sums, record: once per plan shape
         self.set_lambda_vif(lambda_vif)
+        # the VGG19 feature term lambda_perceptual * sum_k w_k mean(crit(F_k(sr) - F_k(hr))): 0 = off (nothing allocated, no call more);
+        # the tower, its weights, the criterion and the tap weights are those of the losses.PerceptualLoss object
+        self.perceptual_loss = perceptual_loss
+        self.perceptual_loss_value = None       # device float [1], already weighted
+        self.set_lambda_perceptual(lambda_perceptual)
         # gradient accumulation: one optimizer step consumes accum_steps equal micro-batches (forward_backward calls); the
         # gradients and the loss of calls 2..k of a cycle are added to the first call's by m2t_grad_accumulate
         if int(accum_steps) != accum_steps or int(accum_steps) < 1:
@@ -509,6 +534,48 @@ class TrainStep:
                                     _lib.VIF_SIGMA_N_SQ, _lib.ptr(self.vif_loss), 0 if first else 1,
                                     _lib.ptr(self._vif_scratch_for(lib, hr_img)), ws, st), "m2t_vif_loss")
 
+    def set_lambda_perceptual(self, value):
+        """Weight of the VGG19 feature term (0 = off); needs ``perceptual_loss=`` (a losses.PerceptualLoss with weights loaded, resize
+        off, data_range = the model's rgb_range).  Takes effect with the next forward_backward; refused in the middle of an
+        accumulation cycle."""
+        if getattr(self, "micro_count", 0) != 0:
+            raise _lib.M2TError(f"set_lambda_perceptual in the middle of an accumulation cycle ({self.micro_count} of {self.accum_steps} "
+                                "micro-batches since the last optimizer step)")
+        self.lambda_perceptual = resolve_lambda_perceptual(value)
+        if self.lambda_perceptual > 0.0:
+            p = self.perceptual_loss
+            if p is None:
+                raise _lib.M2TError("lambda_perceptual > 0 needs perceptual_loss= (a losses.PerceptualLoss with VGG19 weights loaded)")
+            if not p.loaded:
+                raise _lib.M2TError("lambda_perceptual > 0: the PerceptualLoss has no VGG19 weights loaded (none ship): call load_vgg_state_dict first")
+            if p.resize:
+                raise _lib.M2TError("lambda_perceptual > 0: resize=True is not built into the training step (use resize=False)")
+            if float(p.data_range) != float(self.model.rgb_range):
+                raise _lib.M2TError(f"lambda_perceptual > 0: the PerceptualLoss's data_range {p.data_range} is not the model's rgb_range "
+                                    f"{self.model.rgb_range}")
+            if self.perceptual_loss_value is None:
+                self.perceptual_loss_value = torch.zeros(1, dtype=torch.float32, device=self.model.flat_params.device)
+        else:
+            self.perceptual_loss_value = None
+
+    def _perceptual_workspace_for(self, hr_img):
+        """The tower's workspace for this (micro-)batch shape (cached by the PerceptualLoss object); an SR size below 16 is refused
+        here, on the host, before anything is launched."""
+        B, _, Hs, Ws = hr_img.shape
+        if not perceptual_size_supported(Hs, Ws):
+            raise _lib.M2TError(f"lambda_perceptual > 0: the SR image {Hs}x{Ws} is too small (height and width must be at least 16: four "
+                                "pools before relu5_1)")
+        return self.perceptual_loss.workspace(B, Hs, Ws, True)
+
+    def _perceptual_loss_call(self, lib, plan, hr_img, first: bool, ws, st):
+        """m2t_vgg_loss of one (micro-)batch, behind the immediate pixel loss and the other terms: adds into the materialised seed;
+        the value is stored by the first micro-batch of a cycle and added to by the others."""
+        p = self.perceptual_loss
+        divisor = global_divisor(hr_img.shape[0], self.world_size, self.accum_steps)     # global number of images
+        _lib.check(lib.m2t_vgg_loss(plan.handle, p.handle, _lib.ptr(hr_img), self.lambda_perceptual, divisor, float(self.model.rgb_range),
+                                    p.kind, p.param, p.tap_weights(), _lib.ptr(self.perceptual_loss_value), 0 if first else 1,
+                                    _lib.ptr(self._perceptual_workspace_for(hr_img)), ws, st), "m2t_vgg_loss")
+
     def _total_loss(self, with_clip: bool):
         loss = self.l1_loss if self.ssim_loss is None else self.l1_loss + self.ssim_loss
         if self.msssim_loss is not None:
@@ -517,6 +584,8 @@ class TrainStep:
             loss = loss + self.fft_loss
         if self.vif_loss is not None:
             loss = loss + self.vif_loss
+        if self.perceptual_loss_value is not None:
+            loss = loss + self.perceptual_loss_value
         return loss + self.clip_loss if with_clip else loss
 
     def _pixel_loss_call(self, lib, deferred: bool, plan, hr_img, divisor, l1_loss, ws, st):
@@ -585,6 +654,8 @@ class TrainStep:
             self._fft_scratch_for(lib, hr_img)      # (refuses an SR size outside the transform's rule before any launch)
         if self.lambda_vif > 0.0:
             self._vif_scratch_for(lib, hr_img)      # (refuses an SR size below the four-scale rule before any launch)
+        if self.lambda_perceptual > 0.0:
+            self._perceptual_workspace_for(hr_img)  # (refuses an SR size below 16 before any launch)
         divisor = global_divisor(hr_img.numel(), self.world_size, self.accum_steps)      # global mean (equal shards, equal micro-batches)
         use_clip = self.semantic_loss is not None and self.lambda_clip > 0 and captions is not None
         # (micro-batches 2..k of a cycle: a second gradient buffer and a second loss slot, added to the first ones below)
@@ -605,8 +676,10 @@ class TrainStep:
             #  path by the fused tail backward itself; hr_img stays alive until then)
             # (lambda_ssim > 0: the materialised seed -- the immediate pixel loss, then the structural term added into it)
             # (lambda_msssim / lambda_fft / lambda_vif > 0: the same route; the order is pixel -> SSIM -> MS-SSIM -> FFT -> VIF -> backward)
+            # (lambda_perceptual > 0: the same route again, after VIF)
             ssim, msssim, fft, vif = self.lambda_ssim > 0.0, self.lambda_msssim > 0.0, self.lambda_fft > 0.0, self.lambda_vif > 0.0
-            self._pixel_loss_call(lib, not (ssim or msssim or fft or vif), plan, hr_img, divisor, l1_loss, ws, st)
+            perc = self.lambda_perceptual > 0.0
+            self._pixel_loss_call(lib, not (ssim or msssim or fft or vif or perc), plan, hr_img, divisor, l1_loss, ws, st)
             if ssim:
                 self._ssim_loss_call(lib, plan, hr_img, first, ws, st)
             if msssim:
@@ -615,6 +688,8 @@ class TrainStep:
                 self._fft_loss_call(lib, plan, hr_img, first, ws, st)
             if vif:
                 self._vif_loss_call(lib, plan, hr_img, first, ws, st)
+            if perc:
+                self._perceptual_loss_call(lib, plan, hr_img, first, ws, st)
             fwd_done = torch.cuda.current_stream(lr_img.device).record_event() if (use_clip and self.overlap_semantic) else None
             self._backward_call(lib, plan, lr_img, grads, ws, st)
             self._accumulate_micro(lib, first, st)
@@ -681,6 +756,8 @@ class TrainStep:
                 self._fft_loss_call(lib, plan, hr_img, grads is self.grads, ws, st)
             if self.lambda_vif > 0.0:
                 self._vif_loss_call(lib, plan, hr_img, grads is self.grads, ws, st)
+            if self.lambda_perceptual > 0.0:
+                self._perceptual_loss_call(lib, plan, hr_img, grads is self.grads, ws, st)
             g = g.contiguous()
             arr = None
             if origins is not None:
