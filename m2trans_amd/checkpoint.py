@@ -25,15 +25,12 @@ above, key for key.
 
 With a pixel loss other than L1 (TrainStep(pixel_loss=...)) the dict carries ``m2t_loss`` = {"pixel_loss": name, "param": eps /
 beta / None}; ``import_checkpoint`` sets the TrainStep's loss from it and leaves the loss alone when the file has no such entry.
-An L1 run writes no entry: its dict is the one above.  With TrainStep(lambda_ssim > 0) the entry also carries ``"lambda_ssim"``
-(and then exists for an L1 pixel term too); ``import_checkpoint`` calls ``set_lambda_ssim`` with it.  With lambda_ssim = 0 the
-key is absent and the dict is the one described above, byte for byte.  TrainStep(lambda_fft > 0) adds ``"lambda_fft"`` and
-``"fft_norm"`` to the entry in the same way (``import_checkpoint`` calls ``set_lambda_fft``); with lambda_fft = 0 neither key is
-written.  TrainStep(lambda_msssim > 0) adds ``"lambda_msssim"`` in the same way (``import_checkpoint`` calls ``set_lambda_msssim``);
-with lambda_msssim = 0 the key is absent.  TrainStep(lambda_vif > 0) adds ``"lambda_vif"`` after the other keys in the same way
-(``import_checkpoint`` calls ``set_lambda_vif``); with lambda_vif = 0 the key is absent.  TrainStep(lambda_perceptual > 0) adds ``"lambda_perceptual"``,
-``"perceptual_criterion"``, ``"perceptual_weights"`` and ``"perceptual_resize"`` (never the VGG19 weights; ``import_checkpoint`` sets them
-on the step's ``perceptual_loss`` object and calls ``set_lambda_perceptual``); with lambda_perceptual = 0 the keys are absent.
+An L1 run writes no entry: its dict is the one above.  Every optional loss term of the step that is on (train_step.LOSS_TERMS, in
+that order, then the perceptual term) adds its weight to the entry as ``"lambda_<term>"`` (and the entry then exists for an L1 pixel
+term too); ``import_checkpoint`` calls the step's ``set_lambda_<term>`` with it.  ``"lambda_fft"`` is followed by ``"fft_norm"``;
+``"lambda_perceptual"`` by ``"perceptual_criterion"``, ``"perceptual_weights"`` and ``"perceptual_resize"`` (never the VGG19 weights;
+``import_checkpoint`` sets them on the step's ``perceptual_loss`` object first).  The keys of a term whose weight is 0 are absent, so
+with every weight 0 the dict is the one described above, byte for byte.
 
 With TrainStep(param_groups=...) the optimizer dict comes from a real ``torch.optim.Adam`` with ONE TORCH PARAM GROUP PER GROUP, each
 carrying its own ``lr`` (= step.lr * lr_scale) and ``weight_decay``; the parameter ids run through the groups in order (torch's own
@@ -107,33 +104,27 @@ def _optim_options(train_step) -> dict:
 
 
 def _pixel_loss(train_step):
-    """The ``m2t_loss`` entry of a step object, or None for L1 (and for an object that knows no pixel losses)."""
-    from .train_step import resolve_pixel_loss
+    """The ``m2t_loss`` entry of a step object, or None for L1 with every optional term off (and for an object that knows no pixel
+    losses)."""
+    from .train_step import LOSS_TERMS, resolve_pixel_loss
     _, canon, value = resolve_pixel_loss(getattr(train_step, "pixel_loss", "l1"), getattr(train_step, "pixel_loss_param", None))
-    lam = float(getattr(train_step, "lambda_ssim", 0.0) or 0.0)
-    lam_fft = float(getattr(train_step, "lambda_fft", 0.0) or 0.0)
-    lam_ms = float(getattr(train_step, "lambda_msssim", 0.0) or 0.0)
-    lam_vif = float(getattr(train_step, "lambda_vif", 0.0) or 0.0)
-    lam_perc = float(getattr(train_step, "lambda_perceptual", 0.0) or 0.0)
-    if canon == "l1" and lam == 0.0 and lam_fft == 0.0 and lam_ms == 0.0 and lam_vif == 0.0 and lam_perc == 0.0:
+    names = [t.name for t in LOSS_TERMS] + ["perceptual"]
+    lam = {n: float(getattr(train_step, f"lambda_{n}", 0.0) or 0.0) for n in names}
+    if canon == "l1" and not any(lam.values()):
         return None
     out = {"pixel_loss": canon, "param": value}
-    if lam != 0.0:
-        out["lambda_ssim"] = lam
-    if lam_ms != 0.0:
-        out["lambda_msssim"] = lam_ms
-    if lam_fft != 0.0:
-        out["lambda_fft"] = lam_fft
-        out["fft_norm"] = str(getattr(train_step, "fft_norm", "backward"))
-    if lam_vif != 0.0:
-        out["lambda_vif"] = lam_vif
-    if lam_perc != 0.0:
-        # the settings of the term, never the VGG19 weights (an integrator loads those: INTEGRATION.md)
-        p = train_step.perceptual_loss
-        out["lambda_perceptual"] = lam_perc
-        out["perceptual_criterion"] = str(p.criterion)
-        out["perceptual_weights"] = [float(w) for w in p.weights]
-        out["perceptual_resize"] = bool(p.resize)
+    for n in names:
+        if lam[n] == 0.0:
+            continue
+        out[f"lambda_{n}"] = lam[n]
+        if n == "fft":
+            out["fft_norm"] = str(getattr(train_step, "fft_norm", "backward"))
+        if n == "perceptual":
+            # the settings of the term, never the VGG19 weights (an integrator loads those: INTEGRATION.md)
+            p = train_step.perceptual_loss
+            out["perceptual_criterion"] = str(p.criterion)
+            out["perceptual_weights"] = [float(w) for w in p.weights]
+            out["perceptual_resize"] = bool(p.resize)
     return out
 
 
@@ -251,24 +242,18 @@ def import_checkpoint(ckpt: dict, model, train_step=None) -> int:
         else:
             from .train_step import resolve_pixel_loss
             _, train_step.pixel_loss, train_step.pixel_loss_param = resolve_pixel_loss(ml["pixel_loss"], ml.get("param"))
-        if "lambda_ssim" in ml:
-            if hasattr(train_step, "set_lambda_ssim"):
-                train_step.set_lambda_ssim(ml["lambda_ssim"])
+        from .train_step import LOSS_TERMS, resolve_fft_norm, resolve_lambda
+        for t in LOSS_TERMS:
+            key = f"lambda_{t.name}"
+            if key not in ml:
+                continue
+            if hasattr(train_step, f"set_{key}"):
+                getattr(train_step, f"set_{key}")(ml[key], *((ml.get("fft_norm"),) if t.name == "fft" else ()))
             else:
-                from .train_step import resolve_lambda_ssim
-                train_step.lambda_ssim = resolve_lambda_ssim(ml["lambda_ssim"])
-        if "lambda_msssim" in ml:
-            if hasattr(train_step, "set_lambda_msssim"):
-                train_step.set_lambda_msssim(ml["lambda_msssim"])
-            else:
-                from .train_step import resolve_lambda_msssim
-                train_step.lambda_msssim = resolve_lambda_msssim(ml["lambda_msssim"])
-        if "lambda_vif" in ml:
-            if hasattr(train_step, "set_lambda_vif"):
-                train_step.set_lambda_vif(ml["lambda_vif"])
-            else:
-                from .train_step import resolve_lambda_vif
-                train_step.lambda_vif = resolve_lambda_vif(ml["lambda_vif"])
+                # a stand-in step object without the setters receives the attributes
+                setattr(train_step, key, resolve_lambda(t.name, ml[key]))
+                if t.name == "fft":
+                    train_step.fft_norm = resolve_fft_norm(ml.get("fft_norm", "backward"))
         if "lambda_perceptual" in ml:
             p = getattr(train_step, "perceptual_loss", None)
             if p is None:
@@ -278,13 +263,6 @@ def import_checkpoint(ckpt: dict, model, train_step=None) -> int:
             p.configure(ml.get("perceptual_weights", p.weights), ml.get("perceptual_criterion", p.criterion),
                         ml.get("perceptual_resize", p.resize))
             train_step.set_lambda_perceptual(ml["lambda_perceptual"])
-        if "lambda_fft" in ml:
-            if hasattr(train_step, "set_lambda_fft"):
-                train_step.set_lambda_fft(ml["lambda_fft"], ml.get("fft_norm"))
-            else:
-                from .train_step import resolve_fft_norm, resolve_lambda_fft
-                train_step.lambda_fft = resolve_lambda_fft(ml["lambda_fft"])
-                train_step.fft_norm = resolve_fft_norm(ml.get("fft_norm", "backward"))
     opt = ckpt.get("optimizer_state_dict") or {}
     sch = ckpt.get("scheduler_state_dict")
     if not opt.get("state") and not opt.get("param_groups") and sch is None:

@@ -298,13 +298,10 @@ extern "C" size_t m2t_msssim_loss_scratch_offset(int B, int C, int H, int W, int
 extern "C" int m2t_msssim_loss_tensor(const float* x, const float* y, int B, int C, int H, int W, long long x_image_stride,
                                       int x_row_stride, float data_range, int clamp, double scale, float* gx_add, float* loss_out,
                                       double* per_channel_out, int accumulate, void* scratch, void* stream) {
-  if (!x || !y || !loss_out || !scratch) return m2t_set_error(M2T_ERR_ARG, "m2t_msssim_loss_tensor: null argument");
-  if (B < 1 || C < 1 || (long long)B * C > 65535) return m2t_set_error(M2T_ERR_ARG, "m2t_msssim_loss_tensor: need 1 <= B * C <= 65535");
-  if (!msssim_loss_size_supported(H, W))
-    return m2t_set_error(M2T_ERR_ARG, "m2t_msssim_loss_tensor: H and W must be larger than 160 (five levels under the 11-tap window)");
-  if (!(data_range > 0.f) || !isfinite(data_range)) return m2t_set_error(M2T_ERR_ARG, "m2t_msssim_loss_tensor: data_range must be a finite number > 0");
-  if (x_row_stride < W || x_image_stride % C != 0 || x_image_stride / C < (long long)(H - 1) * x_row_stride + W)
-    return m2t_set_error(M2T_ERR_ARG, "m2t_msssim_loss_tensor: strides of x do not hold a [C][H][W] image (channel stride = x_image_stride / C)");
+  const char* const shape = (B < 1 || C < 1 || (long long)B * C > 65535) ? "need 1 <= B * C <= 65535" :
+                            !msssim_loss_size_supported(H, W) ? "H and W must be larger than 160 (five levels under the 11-tap window)" : nullptr;
+  if (int rc = loss_tensor_check(__func__, x, y, loss_out, scratch, C, H, W, x_image_stride, x_row_stride, data_range, shape))
+    return rc;
   return launch_msssim_loss(x, y, B, C, H, W, x_image_stride, x_row_stride, data_range, clamp ? 1 : 0, scale, gx_add, loss_out,
                             per_channel_out, accumulate ? 1 : 0, scratch, (hipStream_t)stream);
 }

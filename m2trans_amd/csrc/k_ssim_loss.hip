@@ -104,17 +104,26 @@ int launch_ssim_loss(const float* x, const float* y, int B, int C, int H, int W,
   return 0;
 }
 
+int loss_tensor_check(const char* who, const float* x, const float* y, const float* loss_out, const void* scratch, int C, int H, int W,
+                      long long x_image_stride, int x_row_stride, float data_range, const char* shape_refusal, const char* more_refusal) {
+  if (!x || !y || !loss_out || !scratch) return m2t_set_error_at(M2T_ERR_ARG, who, "null argument");
+  if (shape_refusal) return m2t_set_error_at(M2T_ERR_ARG, who, shape_refusal);       // (from here on C >= 1)
+  if (!(data_range > 0.f) || !isfinite(data_range)) return m2t_set_error_at(M2T_ERR_ARG, who, "data_range must be a finite number > 0");
+  if (more_refusal) return m2t_set_error_at(M2T_ERR_ARG, who, more_refusal);
+  if (x_row_stride < W || x_image_stride % C != 0 || x_image_stride / C < (long long)(H - 1) * x_row_stride + W)
+    return m2t_set_error_at(M2T_ERR_ARG, who, "strides of x do not hold a [C][H][W] image (channel stride = x_image_stride / C)");
+  return 0;
+}
+
 extern "C" size_t m2t_ssim_loss_scratch_bytes(int B, int C, int H, int W) { return ssim_loss_scratch_bytes(B, C, H, W); }
 
 extern "C" int m2t_ssim_loss_tensor(const float* x, const float* y, int B, int C, int H, int W, long long x_image_stride, int x_row_stride,
                                     float data_range, int clamp, double scale, float* gx_add, float* loss_out, int accumulate,
                                     void* scratch, void* stream) {
-  if (!x || !y || !loss_out || !scratch) return m2t_set_error(M2T_ERR_ARG, "m2t_ssim_loss_tensor: null argument");
-  if (B < 1 || C < 1 || (long long)B * C > 65535) return m2t_set_error(M2T_ERR_ARG, "m2t_ssim_loss_tensor: need 1 <= B * C <= 65535");
-  if (H < WIN || W < WIN) return m2t_set_error(M2T_ERR_ARG, "m2t_ssim_loss_tensor: H and W must be at least 11 (the window)");
-  if (!(data_range > 0.f) || !isfinite(data_range)) return m2t_set_error(M2T_ERR_ARG, "m2t_ssim_loss_tensor: data_range must be a finite number > 0");
-  if (x_row_stride < W || x_image_stride % C != 0 || x_image_stride / C < (long long)(H - 1) * x_row_stride + W)
-    return m2t_set_error(M2T_ERR_ARG, "m2t_ssim_loss_tensor: strides of x do not hold a [C][H][W] image (channel stride = x_image_stride / C)");
+  const char* const shape = (B < 1 || C < 1 || (long long)B * C > 65535) ? "need 1 <= B * C <= 65535" :
+                            (H < WIN || W < WIN) ? "H and W must be at least 11 (the window)" : nullptr;
+  if (int rc = loss_tensor_check(__func__, x, y, loss_out, scratch, C, H, W, x_image_stride, x_row_stride, data_range, shape))
+    return rc;
   return launch_ssim_loss(x, y, B, C, H, W, x_image_stride, x_row_stride, data_range, clamp ? 1 : 0, scale, gx_add, loss_out,
                           accumulate ? 1 : 0, scratch, (hipStream_t)stream);
 }

@@ -279,15 +279,12 @@ extern "C" size_t m2t_vif_loss_scratch_offset(int B, int C, int H, int W, int re
 extern "C" int m2t_vif_loss_tensor(const float* x, const float* y, int B, int C, int H, int W, long long x_image_stride, int x_row_stride,
                                    float data_range, double sigma_n_sq, int clamp, double scale, float* gx_add, float* loss_out,
                                    double* per_image_out, int accumulate, void* scratch, void* stream) {
-  if (!x || !y || !loss_out || !scratch) return m2t_set_error(M2T_ERR_ARG, "m2t_vif_loss_tensor: null argument");
-  if (B < 1 || B > 65535) return m2t_set_error(M2T_ERR_ARG, "m2t_vif_loss_tensor: need 1 <= B <= 65535");
-  if (C != 1 && C != 3) return m2t_set_error(M2T_ERR_ARG, "m2t_vif_loss_tensor: C must be 1 or 3 (luminance of a grey or an RGB image)");
-  if (!vif_loss_size_supported(H, W))
-    return m2t_set_error(M2T_ERR_ARG, "m2t_vif_loss_tensor: H and W must be at least 41 (four scales under the 17 / 9 / 5 / 3-tap windows)");
-  if (!(data_range > 0.f) || !isfinite(data_range)) return m2t_set_error(M2T_ERR_ARG, "m2t_vif_loss_tensor: data_range must be a finite number > 0");
-  if (!(sigma_n_sq > 0.0) || !isfinite(sigma_n_sq)) return m2t_set_error(M2T_ERR_ARG, "m2t_vif_loss_tensor: sigma_n_sq must be a finite number > 0");
-  if (x_row_stride < W || x_image_stride % C != 0 || x_image_stride / C < (long long)(H - 1) * x_row_stride + W)
-    return m2t_set_error(M2T_ERR_ARG, "m2t_vif_loss_tensor: strides of x do not hold a [C][H][W] image (channel stride = x_image_stride / C)");
+  const char* const shape = (B < 1 || B > 65535) ? "need 1 <= B <= 65535" :
+                            (C != 1 && C != 3) ? "C must be 1 or 3 (luminance of a grey or an RGB image)" :
+                            !vif_loss_size_supported(H, W) ? "H and W must be at least 41 (four scales under the 17 / 9 / 5 / 3-tap windows)" : nullptr;
+  const char* const more = (!(sigma_n_sq > 0.0) || !isfinite(sigma_n_sq)) ? "sigma_n_sq must be a finite number > 0" : nullptr;
+  if (int rc = loss_tensor_check(__func__, x, y, loss_out, scratch, C, H, W, x_image_stride, x_row_stride, data_range, shape, more))
+    return rc;
   return launch_vif_loss(x, y, B, C, H, W, x_image_stride, x_row_stride, data_range, sigma_n_sq, clamp ? 1 : 0, scale, gx_add, loss_out,
                          per_image_out, accumulate ? 1 : 0, scratch, (hipStream_t)stream);
 }

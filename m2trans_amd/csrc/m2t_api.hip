@@ -20,6 +20,7 @@ int m2t_set_hip_error(hipError_t e, const char* file, int line) {
   return (int)e;
 }
 int m2t_set_error(int code, const char* msg) { g_err = msg; return code; }
+int m2t_set_error_at(int code, const char* who, const char* what) { g_err = std::string(who) + ": " + what; return code; }
 
 int m2t_ensure_dynamic_lds(const void* kernel, int bytes) {
   static thread_local std::map<std::pair<int, const void*>, int> done;
@@ -708,100 +709,98 @@ extern "C" int m2t_add_output_grad(m2t_plan* p, const float* g, int gh, int gw, 
   return 0;
 }
 
-// weight * (1 - mean SSIM) (k_ssim_loss.hip; losses.py:8, utils.py:232-234) on the forward's pre-clamp output, added into the
-// materialised seed: the routine of m2t_ssim_loss_tensor on ws:srpre (padded Hsp x Wsp, image in the top-left Hs x Ws) and ws:gpre.
-// State rules of m2t_add_output_grad.  Scratch is the caller's: no plan option, no workspace region.
+// ---- the optional loss terms on the forward's pre-clamp output, each added into the materialised seed -------------------------------
+// m2t_<term>_loss runs the routine of m2t_<term>_loss_tensor on ws:srpre (padded Hsp x Wsp, image in the top-left Hs x Ws) and ws:gpre.
+// Scratch is the caller's: no plan option, no workspace region.  Every entry makes its refusals in one order: 1 null, 2 finite numbers,
+// 3 the term's own argument rule, 4 size, 5 batch cap, 6 the term's own state rule, 7 the seed state (that of m2t_add_output_grad).
+// loss_entry_args is 1 + 2 (m2t_vgg_loss leaves its numbers to vgg_check_common), loss_entry_seed is 5 .. 7 and hands back where the term
+// reads and adds; 3, 4 and the decision of 6 stay in the entry.  `who` is the entry's __func__.
+struct LossSeed { const float* x; long long xs_img; int xs_row; float* gx; };
+
+static int loss_entry_args(const char* who, bool any_null, float rgb_range, double divisor, float weight, double more = 1.0,
+                           const char* rule = "rgb_range and divisor must be finite numbers > 0, weight finite") {
+  if (any_null) return m2t_set_error_at(M2T_ERR_ARG, who, "null argument");
+  if (!(rgb_range > 0.f) || !std::isfinite(rgb_range) || !(divisor > 0.0) || !std::isfinite(divisor) || !std::isfinite(weight) ||
+      !(more > 0.0) || !std::isfinite(more))
+    return m2t_set_error_at(M2T_ERR_ARG, who, rule);
+  return 0;
+}
+
+static int loss_entry_seed(const char* who, const m2t_plan* p, bool batch_ok, const char* batch_cap, void* workspace, LossSeed* s,
+                           const char* term_state_refusal = nullptr) {
+  if (!batch_ok) return m2t_set_error_at(M2T_ERR_ARG, who, batch_cap);
+  if (term_state_refusal) return m2t_set_error_at(M2T_ERR_STATE, who, term_state_refusal);
+  if (!p->have_acts || !p->have_seed || p->l1_deferred)
+    return m2t_set_error_at(M2T_ERR_STATE, who, "needs a materialised seed (m2t_l1_loss / m2t_pixel_loss or m2t_set_output_grad)");
+  char* const ws = (char*)workspace;
+  *s = LossSeed{(const float*)(ws + p->hd.srpre), 3LL * p->Hsp * p->Wsp, p->Wsp, (float*)(ws + p->hd.gpre)};
+  return 0;
+}
+
+// weight * (1 - mean SSIM) (k_ssim_loss.hip; losses.py:8, utils.py:232-234)
 extern "C" int m2t_ssim_loss(m2t_plan* p, const float* hr, float weight, double divisor, float rgb_range, float* loss_out, int accumulate,
                              void* scratch, void* workspace, void* stream) {
-  if (!p || !hr || !loss_out || !scratch || !workspace) return m2t_set_error(M2T_ERR_ARG, "m2t_ssim_loss: null argument");
-  if (!(rgb_range > 0.f) || !std::isfinite(rgb_range) || !(divisor > 0.0) || !std::isfinite(divisor) || !std::isfinite(weight))
-    return m2t_set_error(M2T_ERR_ARG, "m2t_ssim_loss: rgb_range and divisor must be finite numbers > 0, weight finite");
-  if (p->Hs < 11 || p->Ws < 11) return m2t_set_error(M2T_ERR_ARG, "m2t_ssim_loss: the SR image is smaller than the 11 x 11 window");
-  if (p->B * 3 > 65535) return m2t_set_error(M2T_ERR_ARG, "m2t_ssim_loss: batch too large (B * 3 <= 65535)");
-  if (!p->have_acts || !p->have_seed || p->l1_deferred)
-    return m2t_set_error(M2T_ERR_STATE, "m2t_ssim_loss: needs a materialised seed (m2t_l1_loss / m2t_pixel_loss or m2t_set_output_grad)");
-  char* const ws = (char*)workspace;
-  return launch_ssim_loss((const float*)(ws + p->hd.srpre), hr, p->B, 3, p->Hs, p->Ws, 3LL * p->Hsp * p->Wsp, p->Wsp, rgb_range, 1,
-                          (double)weight / divisor, (float*)(ws + p->hd.gpre), loss_out, accumulate ? 1 : 0, scratch, (hipStream_t)stream);
+  CK(loss_entry_args(__func__, !p || !hr || !loss_out || !scratch || !workspace, rgb_range, divisor, weight));
+  if (p->Hs < 11 || p->Ws < 11) return m2t_set_error_at(M2T_ERR_ARG, __func__, "the SR image is smaller than the 11 x 11 window");
+  LossSeed s;
+  CK(loss_entry_seed(__func__, p, p->B * 3 <= 65535, "batch too large (B * 3 <= 65535)", workspace, &s));
+  return launch_ssim_loss(s.x, hr, p->B, 3, p->Hs, p->Ws, s.xs_img, s.xs_row, rgb_range, 1, (double)weight / divisor, s.gx, loss_out,
+                          accumulate ? 1 : 0, scratch, (hipStream_t)stream);
 }
 
-// weight * (1 - mean MS-SSIM) (k_msssim_loss.hip; include/m2t_msssim.h) on the forward's pre-clamp output, added into the materialised
-// seed: the routine of m2t_msssim_loss_tensor on ws:srpre (padded Hsp x Wsp, image in the top-left Hs x Ws) and ws:gpre.  State rules
-// of m2t_ssim_loss.  Scratch is the caller's: no plan option, no workspace region.
+// weight * (1 - mean MS-SSIM) (k_msssim_loss.hip; include/m2t_msssim.h)
 extern "C" int m2t_msssim_loss(m2t_plan* p, const float* hr, float weight, double divisor, float rgb_range, float* loss_out,
                                int accumulate, void* scratch, void* workspace, void* stream) {
-  if (!p || !hr || !loss_out || !scratch || !workspace) return m2t_set_error(M2T_ERR_ARG, "m2t_msssim_loss: null argument");
-  if (!(rgb_range > 0.f) || !std::isfinite(rgb_range) || !(divisor > 0.0) || !std::isfinite(divisor) || !std::isfinite(weight))
-    return m2t_set_error(M2T_ERR_ARG, "m2t_msssim_loss: rgb_range and divisor must be finite numbers > 0, weight finite");
+  CK(loss_entry_args(__func__, !p || !hr || !loss_out || !scratch || !workspace, rgb_range, divisor, weight));
   if (!msssim_loss_size_supported(p->Hs, p->Ws))
-    return m2t_set_error(M2T_ERR_ARG, "m2t_msssim_loss: the SR height and width must be larger than 160 (five levels under the 11-tap window)");
-  if (p->B * 3 > 65535) return m2t_set_error(M2T_ERR_ARG, "m2t_msssim_loss: batch too large (B * 3 <= 65535)");
-  if (!p->have_acts || !p->have_seed || p->l1_deferred)
-    return m2t_set_error(M2T_ERR_STATE, "m2t_msssim_loss: needs a materialised seed (m2t_l1_loss / m2t_pixel_loss or m2t_set_output_grad)");
-  char* const ws = (char*)workspace;
-  return launch_msssim_loss((const float*)(ws + p->hd.srpre), hr, p->B, 3, p->Hs, p->Ws, 3LL * p->Hsp * p->Wsp, p->Wsp, rgb_range, 1,
-                            (double)weight / divisor, (float*)(ws + p->hd.gpre), loss_out, nullptr, accumulate ? 1 : 0, scratch,
-                            (hipStream_t)stream);
+    return m2t_set_error_at(M2T_ERR_ARG, __func__, "the SR height and width must be larger than 160 (five levels under the 11-tap window)");
+  LossSeed s;
+  CK(loss_entry_seed(__func__, p, p->B * 3 <= 65535, "batch too large (B * 3 <= 65535)", workspace, &s));
+  return launch_msssim_loss(s.x, hr, p->B, 3, p->Hs, p->Ws, s.xs_img, s.xs_row, rgb_range, 1, (double)weight / divisor, s.gx, loss_out,
+                            nullptr, accumulate ? 1 : 0, scratch, (hipStream_t)stream);
 }
 
-// weight * (1 - mean VIF) (k_vif_loss.hip; include/m2t_vif.h) on the forward's pre-clamp output, added into the materialised seed: the
-// routine of m2t_vif_loss_tensor on ws:srpre (padded Hsp x Wsp, image in the top-left Hs x Ws) and ws:gpre.  State rules of
-// m2t_ssim_loss.  Scratch is the caller's: no plan option, no workspace region.
+// weight * (1 - mean VIF) (k_vif_loss.hip; include/m2t_vif.h)
 extern "C" int m2t_vif_loss(m2t_plan* p, const float* hr, float weight, double divisor, float rgb_range, double sigma_n_sq,
                             float* loss_out, int accumulate, void* scratch, void* workspace, void* stream) {
-  if (!p || !hr || !loss_out || !scratch || !workspace) return m2t_set_error(M2T_ERR_ARG, "m2t_vif_loss: null argument");
-  if (!(rgb_range > 0.f) || !std::isfinite(rgb_range) || !(divisor > 0.0) || !std::isfinite(divisor) || !std::isfinite(weight) ||
-      !(sigma_n_sq > 0.0) || !std::isfinite(sigma_n_sq))
-    return m2t_set_error(M2T_ERR_ARG, "m2t_vif_loss: rgb_range, divisor and sigma_n_sq must be finite numbers > 0, weight finite");
+  CK(loss_entry_args(__func__, !p || !hr || !loss_out || !scratch || !workspace, rgb_range, divisor, weight, sigma_n_sq,
+                     "rgb_range, divisor and sigma_n_sq must be finite numbers > 0, weight finite"));
   if (!vif_loss_size_supported(p->Hs, p->Ws))
-    return m2t_set_error(M2T_ERR_ARG, "m2t_vif_loss: the SR height and width must be at least 41 (four scales under the 17 / 9 / 5 / 3-tap windows)");
-  if (p->B > 65535) return m2t_set_error(M2T_ERR_ARG, "m2t_vif_loss: batch too large (B <= 65535)");
-  if (!p->have_acts || !p->have_seed || p->l1_deferred)
-    return m2t_set_error(M2T_ERR_STATE, "m2t_vif_loss: needs a materialised seed (m2t_l1_loss / m2t_pixel_loss or m2t_set_output_grad)");
-  char* const ws = (char*)workspace;
-  return launch_vif_loss((const float*)(ws + p->hd.srpre), hr, p->B, 3, p->Hs, p->Ws, 3LL * p->Hsp * p->Wsp, p->Wsp, rgb_range, sigma_n_sq,
-                         1, (double)weight / divisor, (float*)(ws + p->hd.gpre), loss_out, nullptr, accumulate ? 1 : 0, scratch,
-                         (hipStream_t)stream);
+    return m2t_set_error_at(M2T_ERR_ARG, __func__, "the SR height and width must be at least 41 (four scales under the 17 / 9 / 5 / 3-tap windows)");
+  LossSeed s;
+  CK(loss_entry_seed(__func__, p, p->B <= 65535, "batch too large (B <= 65535)", workspace, &s));
+  return launch_vif_loss(s.x, hr, p->B, 3, p->Hs, p->Ws, s.xs_img, s.xs_row, rgb_range, sigma_n_sq, 1, (double)weight / divisor, s.gx,
+                         loss_out, nullptr, accumulate ? 1 : 0, scratch, (hipStream_t)stream);
 }
 
-// weight * sum_k w_k mean(rho(F_k(sr) - F_k(hr))) on VGG19 features (k_vgg.hip, m2t_vgg.hip; include/m2t_perceptual.h) on the forward's
-// pre-clamp output, added into the materialised seed: the routine of m2t_vgg_loss_tensor on ws:srpre and ws:gpre.  State rules of
-// m2t_ssim_loss.  The tower's workspace is the caller's: no plan option, no workspace region.
+// weight * sum_k w_k mean(rho(F_k(sr) - F_k(hr))) on VGG19 features (k_vgg.hip, m2t_vgg.hip; include/m2t_perceptual.h).  The tower's
+// workspace is the caller's.
 extern "C" int m2t_vgg_loss(m2t_plan* p, const m2t_vgg* v, const float* hr, float weight, double divisor, float rgb_range, int kind,
                             float param, const double* tap_weights, float* loss_out, int accumulate, void* vgg_workspace, void* workspace,
                             void* stream) {
-  if (!p || !v || !hr || !loss_out || !vgg_workspace || !workspace) return m2t_set_error(M2T_ERR_ARG, "m2t_vgg_loss: null argument");
-  if (!(divisor > 0.0) || !std::isfinite(divisor)) return m2t_set_error(M2T_ERR_ARG, "m2t_vgg_loss: divisor must be a finite number > 0");
-  if (int rc = vgg_check_common("m2t_vgg_loss", tap_weights, (double)weight, rgb_range, kind, param)) return rc;
+  if (!p || !v || !hr || !loss_out || !vgg_workspace || !workspace) return m2t_set_error_at(M2T_ERR_ARG, __func__, "null argument");
+  if (!(divisor > 0.0) || !std::isfinite(divisor)) return m2t_set_error_at(M2T_ERR_ARG, __func__, "divisor must be a finite number > 0");
+  CK(vgg_check_common(__func__, tap_weights, (double)weight, rgb_range, kind, param));
   if (!vgg_size_supported(p->Hs, p->Ws))
-    return m2t_set_error(M2T_ERR_ARG, "m2t_vgg_loss: the SR height and width must be at least 16 (four 2 x 2 pools before relu5_1)");
-  if (p->B > 32767) return m2t_set_error(M2T_ERR_ARG, "m2t_vgg_loss: batch too large (B <= 32767)");
-  if (!vgg_loaded(v)) return m2t_set_error(M2T_ERR_STATE, "m2t_vgg_loss: call m2t_vgg_load_weights first (no VGG19 weights ship with the library)");
-  if (!p->have_acts || !p->have_seed || p->l1_deferred)
-    return m2t_set_error(M2T_ERR_STATE, "m2t_vgg_loss: needs a materialised seed (m2t_l1_loss / m2t_pixel_loss or m2t_set_output_grad)");
-  char* const ws = (char*)workspace;
-  return launch_vgg_loss(v, (const float*)(ws + p->hd.srpre), hr, p->B, 3, p->Hs, p->Ws, 3LL * p->Hsp * p->Wsp, p->Wsp, rgb_range, 1, kind,
-                         param, tap_weights, (double)weight, divisor, (float*)(ws + p->hd.gpre), loss_out, nullptr, accumulate ? 1 : 0,
-                         vgg_workspace, (hipStream_t)stream);
+    return m2t_set_error_at(M2T_ERR_ARG, __func__, "the SR height and width must be at least 16 (four 2 x 2 pools before relu5_1)");
+  LossSeed s;
+  CK(loss_entry_seed(__func__, p, p->B <= 32767, "batch too large (B <= 32767)", workspace, &s,
+                     vgg_loaded(v) ? nullptr : "call m2t_vgg_load_weights first (no VGG19 weights ship with the library)"));
+  return launch_vgg_loss(v, s.x, hr, p->B, 3, p->Hs, p->Ws, s.xs_img, s.xs_row, rgb_range, 1, kind, param, tap_weights, (double)weight,
+                         divisor, s.gx, loss_out, nullptr, accumulate ? 1 : 0, vgg_workspace, (hipStream_t)stream);
 }
 
-// weight * mean |rfft2(d)| (k_fft_loss.hip; include/m2t_spectral.h) on the forward's pre-clamp output, added into the materialised
-// seed: the routine of m2t_fft_loss_tensor on ws:srpre (padded Hsp x Wsp, image in the top-left Hs x Ws) and ws:gpre.  State rules of
-// m2t_ssim_loss.  Scratch is the caller's: no plan option, no workspace region.
+// weight * mean |rfft2(d)| (k_fft_loss.hip; include/m2t_spectral.h)
 extern "C" int m2t_fft_loss(m2t_plan* p, const float* hr, float weight, double divisor, float rgb_range, int norm, float* loss_out,
                             int accumulate, void* scratch, void* workspace, void* stream) {
-  if (!p || !hr || !loss_out || !scratch || !workspace) return m2t_set_error(M2T_ERR_ARG, "m2t_fft_loss: null argument");
-  if (!(rgb_range > 0.f) || !std::isfinite(rgb_range) || !(divisor > 0.0) || !std::isfinite(divisor) || !std::isfinite(weight))
-    return m2t_set_error(M2T_ERR_ARG, "m2t_fft_loss: rgb_range and divisor must be finite numbers > 0, weight finite");
-  if (norm != 0 && norm != 1) return m2t_set_error(M2T_ERR_ARG, "m2t_fft_loss: norm must be 0 (backward) or 1 (ortho)");
+  CK(loss_entry_args(__func__, !p || !hr || !loss_out || !scratch || !workspace, rgb_range, divisor, weight));
+  if (norm != 0 && norm != 1) return m2t_set_error_at(M2T_ERR_ARG, __func__, "norm must be 0 (backward) or 1 (ortho)");
   if (!fft_loss_size_supported(p->Hs, p->Ws))
-    return m2t_set_error(M2T_ERR_ARG, "m2t_fft_loss: the SR height and width must be even, 8 .. 2048 and of the form 2^a * 3^b");
-  if (p->B * 3 > 65535) return m2t_set_error(M2T_ERR_ARG, "m2t_fft_loss: batch too large (B * 3 <= 65535)");
-  if (!p->have_acts || !p->have_seed || p->l1_deferred)
-    return m2t_set_error(M2T_ERR_STATE, "m2t_fft_loss: needs a materialised seed (m2t_l1_loss / m2t_pixel_loss or m2t_set_output_grad)");
-  char* const ws = (char*)workspace;
-  return launch_fft_loss((const float*)(ws + p->hd.srpre), hr, p->B, 3, p->Hs, p->Ws, 3LL * p->Hsp * p->Wsp, p->Wsp, rgb_range, 1, norm,
-                         (double)weight / divisor, (float*)(ws + p->hd.gpre), loss_out, accumulate ? 1 : 0, scratch, (hipStream_t)stream);
+    return m2t_set_error_at(M2T_ERR_ARG, __func__, "the SR height and width must be even, 8 .. 2048 and of the form 2^a * 3^b");
+  LossSeed s;
+  CK(loss_entry_seed(__func__, p, p->B * 3 <= 65535, "batch too large (B * 3 <= 65535)", workspace, &s));
+  return launch_fft_loss(s.x, hr, p->B, 3, p->Hs, p->Ws, s.xs_img, s.xs_row, rgb_range, 1, norm, (double)weight / divisor, s.gx, loss_out,
+                         accumulate ? 1 : 0, scratch, (hipStream_t)stream);
 }
 
 // Two-stream backward.  The data-gradient chain (what the next kernel needs) runs on the

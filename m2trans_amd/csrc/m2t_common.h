@@ -393,6 +393,7 @@ __device__ __forceinline__ int xcd_block_index() {
 
 int m2t_set_hip_error(hipError_t e, const char* file, int line);
 int m2t_set_error(int code, const char* msg);
+int m2t_set_error_at(int code, const char* who, const char* what);   // the message "who: what"
 // Raises the dynamic-LDS limit of `kernel` to `bytes` on the CURRENT device, once per (calling thread, device, kernel):
 // the attribute is per device, and the cache is thread-local, so the library keeps no process-global mutable state
 // (two host threads driving two GPUs each set it for their own device).  Returns 0 or the hipError_t.

@@ -331,6 +331,12 @@ int launch_add_output_grad(const float* pre, const float* g, float* gpre, int B,
 // gx_add[q] += -scale * d sum(S) / dx[q] (through the clamp mask when clamp); loss_out = (accumulate ? loss_out : 0) + scale * sum(1 - S).
 // scratch: ssim_loss_scratch_bytes(B, C, H, W) bytes (0 when H or W < 11).  Arguments are checked by the callers.
 size_t ssim_loss_scratch_bytes(int B, int C, int H, int W);
+// The refusals the plan-free m2t_<term>_loss_tensor entries share, in the order they always made them: null argument, the term's batch /
+// size rule, data_range, the term's further argument rule, the strides of x.  The two rules of the term are decided at the call site and
+// come in as the refusal's text (nullptr: passed); `who` prefixes every message.  0 or M2T_ERR_ARG.
+int loss_tensor_check(const char* who, const float* x, const float* y, const float* loss_out, const void* scratch, int C, int H, int W,
+                      long long x_image_stride, int x_row_stride, float data_range, const char* shape_refusal,
+                      const char* more_refusal = nullptr);
 void ssim_loss_taps(double* g11);      // the 11 taps of the window (the fp32 taps torch builds, widened), also those of k_msssim_loss.hip
 int launch_ssim_loss(const float* x, const float* y, int B, int C, int H, int W, long long xs_img, int xs_row, float R, int clamp,
                      double scale, float* gx_add, float* loss_out, int accumulate, void* scratch, hipStream_t st);

@@ -473,34 +473,67 @@ class _SemanticLossGrad(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# The structural term: 1 - SSIM (the reference imports SSIMLoss / MultiScaleSSIMLoss from piq, losses.py:8, and scores every
-# epoch by SSIM, utils.py:232-234).  Value and gradient are HIP (m2t_ssim_loss_tensor, k_ssim_loss.hip); there is no torch fallback.
+# What the image-pair losses below share: the refusals of a pair of tensors, the buffers around one m2t_*_loss_tensor call, and the
+# autograd edge of a loss whose value and gradient come from that one call.
 # ---------------------------------------------------------------------------------------------------------------
-class _SSIMLossFn(torch.autograd.Function):
+def _pair_check(what, x, y, device=True, y_no_grad=True):
+    """Two [B,C,H,W] tensors of equal shape; on a HIP device; y without grad (a metric passes y_no_grad=False; a caller with rules
+    of its own between the shape and the device refusal passes device=False first and comes back)."""
+    if x.dim() != 4 or x.shape != y.shape:
+        raise M2TError(f"{what}: expected two [B,C,H,W] tensors of equal shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if device and not (x.is_cuda and y.is_cuda):
+        raise M2TError(f"{what} needs HIP device tensors (there is no host implementation)")
+    if device and y_no_grad and y.requires_grad:
+        raise M2TError(f"{what} gives the gradient with respect to x only: y must not require grad (detach it)")
+
+
+def _tensor_loss(name, no_scratch, x, y, want_grad, per_count, args):
+    """One ``m2t_<name>_loss_tensor`` call on device tensors [B,C,H,W] -> (loss [1] float32, gradient or None, per-item float64 or
+    None).  Made here: the contiguous fp32 copies, the entry's scratch (a shape it names no size for is refused with ``no_scratch``),
+    the value, the zeroed gradient if wanted, ``per_count(B, C)`` per-item results if wanted.  ``args(B, C, H, W, grad, out, per,
+    scratch)`` gives the entry's arguments behind x_row_stride, the four buffers as pointers."""
+    lib = _lib.load()
+    xc, yc = x.detach().contiguous().float(), y.detach().contiguous().float()
+    B, Cn, H, W = xc.shape
+    nbytes = getattr(lib, f"m2t_{name}_loss_scratch_bytes")(B, Cn, H, W)
+    if nbytes == 0:
+        raise M2TError(no_scratch.format(B=B, C=Cn, H=H, W=W))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=xc.device)
+    out = torch.empty(1, dtype=torch.float32, device=xc.device)
+    grad = torch.zeros_like(xc) if want_grad else None
+    per = torch.empty(per_count(B, Cn), dtype=torch.float64, device=xc.device) if per_count is not None else None
+    entry = f"m2t_{name}_loss_tensor"
+    with torch.cuda.device(xc.device):
+        _lib.check(getattr(lib, entry)(_lib.ptr(xc), _lib.ptr(yc), B, Cn, H, W, Cn * H * W, W,
+                                       *args(B, Cn, H, W, _lib.ptr(grad), _lib.ptr(out), _lib.ptr(per), _lib.ptr(scratch)),
+                                       _lib.stream_ptr()), entry)
+    return out, grad, per
+
+
+class _EagerGradFn(torch.autograd.Function):
+    """Edge from a loss to ``x`` when value and gradient come from one eager call: ``call(want_grad) -> (out [1], gradient of the
+    value or None)``.  Nothing else is kept; backward scales that gradient by the upstream one."""
+
     @staticmethod
-    def forward(ctx, x, y, data_range):
-        lib = _lib.load()
-        xc, yc = x.detach().contiguous().float(), y.detach().contiguous().float()
-        B, Cn, H, W = xc.shape
-        nbytes = lib.m2t_ssim_loss_scratch_bytes(B, Cn, H, W)
-        if nbytes == 0:
-            raise M2TError(f"ssim_loss: image {H}x{W} is smaller than the 11 x 11 window")
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=xc.device)
-        out = torch.empty(1, dtype=torch.float32, device=xc.device)
-        # value and gradient come from one launch; the gradient of the MEAN, scaled by the upstream gradient in backward
-        grad = torch.zeros_like(xc) if ctx.needs_input_grad[0] else None
-        n = B * Cn * (H - 10) * (W - 10)
-        with torch.cuda.device(xc.device):
-            _lib.check(lib.m2t_ssim_loss_tensor(_lib.ptr(xc), _lib.ptr(yc), B, Cn, H, W, Cn * H * W, W, float(data_range), 0, 1.0 / n,
-                                                _lib.ptr(grad), _lib.ptr(out), 0, _lib.ptr(scratch), _lib.stream_ptr()),
-                       "m2t_ssim_loss_tensor")
-        ctx.grad = grad
+    def forward(ctx, x, call):
+        out, ctx.grad = call(ctx.needs_input_grad[0])
         ctx.x_dtype = x.dtype
         return out[0]
 
     @staticmethod
     def backward(ctx, g):
-        return (ctx.grad * g).to(ctx.x_dtype), None, None
+        return (ctx.grad * g).to(ctx.x_dtype), None
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The structural term: 1 - SSIM (the reference imports SSIMLoss / MultiScaleSSIMLoss from piq, losses.py:8, and scores every
+# epoch by SSIM, utils.py:232-234).  Value and gradient are HIP (m2t_ssim_loss_tensor, k_ssim_loss.hip); there is no torch fallback.
+# ---------------------------------------------------------------------------------------------------------------
+def _ssim_call(x, y, data_range, want_grad):
+    """(loss [1] float32, gradient of the mean or None) of device tensors [B,C,H,W]."""
+    return _tensor_loss("ssim", "ssim_loss: image {H}x{W} is smaller than the 11 x 11 window", x, y, want_grad, None,
+                        lambda B, Cn, H, W, grad, out, per, scratch:
+                        (float(data_range), 0, 1.0 / (B * Cn * (H - 10) * (W - 10)), grad, out, 0, scratch))[:2]
 
 
 def ssim_loss(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0) -> torch.Tensor:
@@ -508,15 +541,10 @@ def ssim_loss(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0) -> torc
     (11-tap Gaussian sigma 1.5, K = (0.01, 0.03), no clamp of the map, inputs NOT clamped to the data range), for device tensors
     [B,C,H,W] with H, W >= 11; differentiable with respect to ``x`` only.  ``piq.SSIMLoss``'s default ``downsample=True`` (an
     average pooling in front, by 2 at 512 x 512) is not applied.  fp64 inside the kernel, fp32 in and out."""
-    if x.dim() != 4 or x.shape != y.shape:
-        raise M2TError(f"ssim_loss: expected two [B,C,H,W] tensors of equal shape, got {tuple(x.shape)} and {tuple(y.shape)}")
-    if not (x.is_cuda and y.is_cuda):
-        raise M2TError("ssim_loss needs HIP device tensors (there is no host implementation)")
-    if y.requires_grad:
-        raise M2TError("ssim_loss gives the gradient with respect to x only: y must not require grad (detach it)")
+    _pair_check("ssim_loss", x, y)
     if not (float(data_range) > 0.0):
         raise M2TError(f"ssim_loss: data_range must be > 0, got {data_range!r}")
-    return _SSIMLossFn.apply(x, y, float(data_range))
+    return _EagerGradFn.apply(x, lambda want_grad: _ssim_call(x, y, data_range, want_grad))
 
 
 class SSIMLoss(nn.Module):
@@ -536,46 +564,18 @@ class SSIMLoss(nn.Module):
 # ---------------------------------------------------------------------------------------------------------------
 def _msssim_call(x, y, data_range, want_grad, want_per_channel):
     """(loss [1] float32, gradient of the mean or None, M_bc [B*C] float64 or None) of device tensors [B,C,H,W]."""
-    lib = _lib.load()
-    xc, yc = x.detach().contiguous().float(), y.detach().contiguous().float()
-    B, Cn, H, W = xc.shape
-    nbytes = lib.m2t_msssim_loss_scratch_bytes(B, Cn, H, W)
-    if nbytes == 0:
-        raise M2TError(f"ms_ssim: no scratch size for [{B},{Cn},{H},{W}] (height and width must be larger than 160, B * C at most 65535)")
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=xc.device)
-    out = torch.empty(1, dtype=torch.float32, device=xc.device)
-    grad = torch.zeros_like(xc) if want_grad else None
-    per = torch.empty(B * Cn, dtype=torch.float64, device=xc.device) if want_per_channel else None
-    with torch.cuda.device(xc.device):
-        _lib.check(lib.m2t_msssim_loss_tensor(_lib.ptr(xc), _lib.ptr(yc), B, Cn, H, W, Cn * H * W, W, float(data_range), 0,
-                                              1.0 / (B * Cn), _lib.ptr(grad), _lib.ptr(out), _lib.ptr(per), 0, _lib.ptr(scratch),
-                                              _lib.stream_ptr()), "m2t_msssim_loss_tensor")
-    return out, grad, per
+    return _tensor_loss("msssim", "ms_ssim: no scratch size for [{B},{C},{H},{W}] (height and width must be larger than 160, B * C at most 65535)",
+                        x, y, want_grad, (lambda B, Cn: B * Cn) if want_per_channel else None,
+                        lambda B, Cn, H, W, grad, out, per, scratch: (float(data_range), 0, 1.0 / (B * Cn), grad, out, per, 0, scratch))
 
 
-def _msssim_check(what, x, y, data_range):
-    if x.dim() != 4 or x.shape != y.shape:
-        raise M2TError(f"{what}: expected two [B,C,H,W] tensors of equal shape, got {tuple(x.shape)} and {tuple(y.shape)}")
-    if not (x.is_cuda and y.is_cuda):
-        raise M2TError(f"{what} needs HIP device tensors (there is no host implementation)")
+def _msssim_check(what, x, y, data_range, y_no_grad=False):
+    _pair_check(what, x, y, y_no_grad=y_no_grad)
     if not (float(data_range) > 0.0):
         raise M2TError(f"{what}: data_range must be > 0, got {data_range!r}")
     H, W = int(x.shape[2]), int(x.shape[3])
     if min(H, W) < _lib.MSSSIM_MIN_SIDE:
         raise M2TError(f"{what}: image {H}x{W} is too small for five levels under the 11-tap window (height and width must be larger than 160)")
-
-
-class _MSSSIMLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, y, data_range):
-        # value and gradient come from one call; the gradient of the MEAN, scaled by the upstream gradient in backward
-        out, ctx.grad, _ = _msssim_call(x, y, data_range, ctx.needs_input_grad[0], False)
-        ctx.x_dtype = x.dtype
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        return (ctx.grad * g).to(ctx.x_dtype), None, None
 
 
 def ms_ssim_loss(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0) -> torch.Tensor:
@@ -584,10 +584,8 @@ def ms_ssim_loss(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0) -> t
     side % 2 between the levels, inputs NOT clamped to the data range), for device tensors [B,C,H,W] with H, W > 160; differentiable
     with respect to ``x`` only.  An (image, channel) one of whose level means is not positive has MS-SSIM 0 and gradient 0 (torch's
     autograd gives 0 * inf there).  fp64 inside the kernels, fp32 in and out."""
-    _msssim_check("ms_ssim_loss", x, y, data_range)
-    if y.requires_grad:
-        raise M2TError("ms_ssim_loss gives the gradient with respect to x only: y must not require grad (detach it)")
-    return _MSSSIMLossFn.apply(x, y, float(data_range))
+    _msssim_check("ms_ssim_loss", x, y, data_range, y_no_grad=True)
+    return _EagerGradFn.apply(x, lambda want_grad: _msssim_call(x, y, data_range, want_grad, False)[:2])
 
 
 class MSSSIMLoss(nn.Module):
@@ -607,28 +605,14 @@ class MSSSIMLoss(nn.Module):
 # ---------------------------------------------------------------------------------------------------------------
 def _vif_call(x, y, data_range, sigma_n_sq, want_grad, want_per_image):
     """(loss [1] float32, gradient of the mean or None, VIF_b [B] float64 or None) of device tensors [B,C,H,W]."""
-    lib = _lib.load()
-    xc, yc = x.detach().contiguous().float(), y.detach().contiguous().float()
-    B, Cn, H, W = xc.shape
-    nbytes = lib.m2t_vif_loss_scratch_bytes(B, Cn, H, W)
-    if nbytes == 0:
-        raise M2TError(f"vif: no scratch size for [{B},{Cn},{H},{W}] (height and width at least 41, 1 or 3 channels, B at most 65535)")
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=xc.device)
-    out = torch.empty(1, dtype=torch.float32, device=xc.device)
-    grad = torch.zeros_like(xc) if want_grad else None
-    per = torch.empty(B, dtype=torch.float64, device=xc.device) if want_per_image else None
-    with torch.cuda.device(xc.device):
-        _lib.check(lib.m2t_vif_loss_tensor(_lib.ptr(xc), _lib.ptr(yc), B, Cn, H, W, Cn * H * W, W, float(data_range), float(sigma_n_sq), 0,
-                                           1.0 / B, _lib.ptr(grad), _lib.ptr(out), _lib.ptr(per), 0, _lib.ptr(scratch),
-                                           _lib.stream_ptr()), "m2t_vif_loss_tensor")
-    return out, grad, per
+    return _tensor_loss("vif", "vif: no scratch size for [{B},{C},{H},{W}] (height and width at least 41, 1 or 3 channels, B at most 65535)",
+                        x, y, want_grad, (lambda B, Cn: B) if want_per_image else None,
+                        lambda B, Cn, H, W, grad, out, per, scratch:
+                        (float(data_range), float(sigma_n_sq), 0, 1.0 / B, grad, out, per, 0, scratch))
 
 
-def _vif_check(what, x, y, data_range, sigma_n_sq):
-    if x.dim() != 4 or x.shape != y.shape:
-        raise M2TError(f"{what}: expected two [B,C,H,W] tensors of equal shape, got {tuple(x.shape)} and {tuple(y.shape)}")
-    if not (x.is_cuda and y.is_cuda):
-        raise M2TError(f"{what} needs HIP device tensors (there is no host implementation)")
+def _vif_check(what, x, y, data_range, sigma_n_sq, y_no_grad=False):
+    _pair_check(what, x, y, y_no_grad=y_no_grad)
     if not (math.isfinite(float(data_range)) and float(data_range) > 0.0):
         raise M2TError(f"{what}: data_range must be a finite number > 0, got {data_range!r}")
     if not (math.isfinite(float(sigma_n_sq)) and float(sigma_n_sq) > 0.0):
@@ -640,29 +624,14 @@ def _vif_check(what, x, y, data_range, sigma_n_sq):
         raise M2TError(f"{what}: image {H}x{W} is too small for four scales under the 17 / 9 / 5 / 3-tap windows (height and width must be at least 41)")
 
 
-class _VIFLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, y, data_range, sigma_n_sq):
-        # value and gradient come from one call; the gradient of the MEAN, scaled by the upstream gradient in backward
-        out, ctx.grad, _ = _vif_call(x, y, data_range, sigma_n_sq, ctx.needs_input_grad[0], False)
-        ctx.x_dtype = x.dtype
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        return (ctx.grad * g).to(ctx.x_dtype), None, None, None
-
-
 def vif_loss(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0, sigma_n_sq: float = 2.0) -> torch.Tensor:
     """1 - mean over the images of VIF(x, y), the pixel-domain visual information fidelity of Sheikh & Bovik in the ``piq.vif_p``
     form (luminance of an RGB image on the 0 .. 255 scale, four scales with Gaussian windows of 17, 9, 5, 3 taps, a filtered and
     decimated pyramid, inputs NOT clamped to the data range), for device tensors [B,C,H,W] with C = 1 or 3 and H, W >= 41;
     differentiable with respect to ``x`` only.  VIF exceeds 1 for a contrast-enhanced ``x``: the value may be negative and is not
     clipped.  fp64 inside the kernels, fp32 in and out."""
-    _vif_check("vif_loss", x, y, data_range, sigma_n_sq)
-    if y.requires_grad:
-        raise M2TError("vif_loss gives the gradient with respect to x only: y must not require grad (detach it)")
-    return _VIFLossFn.apply(x, y, float(data_range), float(sigma_n_sq))
+    _vif_check("vif_loss", x, y, data_range, sigma_n_sq, y_no_grad=True)
+    return _EagerGradFn.apply(x, lambda want_grad: _vif_call(x, y, data_range, sigma_n_sq, want_grad, False)[:2])
 
 
 class VIFLoss(nn.Module):
@@ -682,31 +651,11 @@ class VIFLoss(nn.Module):
 # MIMO-UNet's F.l1_loss(view_as_real(rfft2(x)), view_as_real(rfft2(y)))).  Value and gradient are HIP (m2t_fft_loss_tensor of
 # include/m2t_spectral.h, k_fft_loss.hip); there is no torch fallback.
 # ---------------------------------------------------------------------------------------------------------------
-class _FFTLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, y, data_range, norm):
-        lib = _lib.load()
-        xc, yc = x.detach().contiguous().float(), y.detach().contiguous().float()
-        B, Cn, H, W = xc.shape
-        nbytes = lib.m2t_fft_loss_scratch_bytes(B, Cn, H, W)
-        if nbytes == 0:
-            raise M2TError(f"fft_loss: no scratch size for [{B},{Cn},{H},{W}] (B * C must be 1 .. 65535)")
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=xc.device)
-        out = torch.empty(1, dtype=torch.float32, device=xc.device)
-        # value and gradient come from one call; the gradient of the MEAN, scaled by the upstream gradient in backward
-        grad = torch.zeros_like(xc) if ctx.needs_input_grad[0] else None
-        n = 2 * B * Cn * H * (W // 2 + 1)
-        with torch.cuda.device(xc.device):
-            _lib.check(lib.m2t_fft_loss_tensor(_lib.ptr(xc), _lib.ptr(yc), B, Cn, H, W, Cn * H * W, W, float(data_range), 0,
-                                               _lib.FFT_NORMS[norm], 1.0 / n, _lib.ptr(grad), _lib.ptr(out), 0, _lib.ptr(scratch),
-                                               _lib.stream_ptr()), "m2t_fft_loss_tensor")
-        ctx.grad = grad
-        ctx.x_dtype = x.dtype
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        return (ctx.grad * g).to(ctx.x_dtype), None, None, None
+def _fft_call(x, y, data_range, norm, want_grad):
+    """(loss [1] float32, gradient of the mean or None) of device tensors [B,C,H,W]."""
+    return _tensor_loss("fft", "fft_loss: no scratch size for [{B},{C},{H},{W}] (B * C must be 1 .. 65535)", x, y, want_grad, None,
+                        lambda B, Cn, H, W, grad, out, per, scratch:
+                        (float(data_range), 0, _lib.FFT_NORMS[norm], 1.0 / (2 * B * Cn * H * (W // 2 + 1)), grad, out, 0, scratch))[:2]
 
 
 def fft_loss(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0, norm: str = "backward") -> torch.Tensor:
@@ -715,18 +664,14 @@ def fft_loss(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0, norm: st
     only.  H and W must be even, 8 .. 2048 and of the form 2^a * 3^b.  The imaginary part of the four self-conjugate bins is
     exactly 0 (torch leaves rounding noise there and takes its sign); sign(0) = 0.  fp32 butterflies, fp64 sums."""
     from .train_step import FFT_SIZE_RULE, fft_size_supported, resolve_fft_norm
-    if x.dim() != 4 or x.shape != y.shape:
-        raise M2TError(f"fft_loss: expected two [B,C,H,W] tensors of equal shape, got {tuple(x.shape)} and {tuple(y.shape)}")
-    if not (x.is_cuda and y.is_cuda):
-        raise M2TError("fft_loss needs HIP device tensors (there is no host implementation)")
-    if y.requires_grad:
-        raise M2TError("fft_loss gives the gradient with respect to x only: y must not require grad (detach it)")
+    _pair_check("fft_loss", x, y)
     if not (float(data_range) > 0.0):
         raise M2TError(f"fft_loss: data_range must be > 0, got {data_range!r}")
     H, W = int(x.shape[2]), int(x.shape[3])
     if not (fft_size_supported(H) and fft_size_supported(W)):
         raise M2TError(f"fft_loss: image size {H}x{W} is not supported by the HIP transform (height and width must be {FFT_SIZE_RULE})")
-    return _FFTLossFn.apply(x, y, float(data_range), resolve_fft_norm(norm))
+    norm = resolve_fft_norm(norm)
+    return _EagerGradFn.apply(x, lambda want_grad: _fft_call(x, y, data_range, norm, want_grad))
 
 
 class FFTLoss(nn.Module):
@@ -790,17 +735,6 @@ def vgg_fold_state_dict(state: Dict[str, torch.Tensor]) -> Dict[str, torch.Tenso
         out[f"features.{plain}.weight"], out[f"features.{plain}.bias"] = w.float(), b.float()
     return out
 
-
-class _PerceptualFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, y, mod):
-        out, ctx.grad = mod._call(x, y, ctx.needs_input_grad[0])
-        ctx.x_dtype = x.dtype
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        return (ctx.grad * g).to(ctx.x_dtype), None, None
 
 
 class PerceptualLoss(nn.Module):
@@ -876,8 +810,7 @@ class PerceptualLoss(nn.Module):
         return self._ws[key]
 
     def check(self, x, y):
-        if x.dim() != 4 or x.shape != y.shape:
-            raise M2TError(f"PerceptualLoss: expected two [B,C,H,W] tensors of equal shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+        _pair_check("PerceptualLoss", x, y, device=False)
         if int(x.shape[1]) not in (1, 3):
             raise M2TError(f"PerceptualLoss: 1 or 3 channels, got {int(x.shape[1])}")
         H, W = (224, 224) if self.resize else (int(x.shape[2]), int(x.shape[3]))
@@ -885,10 +818,7 @@ class PerceptualLoss(nn.Module):
             raise M2TError(f"PerceptualLoss: image {H}x{W} is too small (height and width must be at least {_lib.VGG_MIN_SIDE}: four pools before relu5_1)")
         if not self.loaded:
             raise M2TError("PerceptualLoss: no VGG19 weights loaded (none ship with the library): call load_vgg_state_dict first")
-        if not (x.is_cuda and y.is_cuda):
-            raise M2TError("PerceptualLoss needs HIP device tensors (there is no host implementation)")
-        if y.requires_grad:
-            raise M2TError("PerceptualLoss gives the gradient with respect to x only: y must not require grad (detach it)")
+        _pair_check("PerceptualLoss", x, y)
 
     def _call(self, x, y, want_grad):
         """(loss [1] float32, gradient or None) of device tensors [B,C,H,W]."""
@@ -916,7 +846,7 @@ class PerceptualLoss(nn.Module):
 
     def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         self.check(x, y)
-        return _PerceptualFn.apply(x, y, self)
+        return _EagerGradFn.apply(x, lambda want_grad: self._call(x, y, want_grad))
 
     def __del__(self):
         try:

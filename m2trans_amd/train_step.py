@@ -30,34 +30,31 @@ L1_Charbonnier_loss): the kind only selects the per-pixel function inside the ke
 m2t_pixel_loss_deferred), so every kind runs the schedule of the L1 step -- the seed fused into the x4 tail backward, accumulation,
 the overlapped exchange and the optimizer options included.
 
-Structural term (``lambda_ssim``; the reference imports SSIMLoss from piq next to the pixel criteria, losses.py:8, and scores every
-epoch by SSIM, utils.py:232-234): ``lambda_ssim * (1 - mean SSIM)`` per RGB channel in the pytorch_msssim.ssim /
-piq.ssim(downsample=False) form -- piq.SSIMLoss's default ``downsample=True`` pooling is NOT applied -- with its gradient in HIP
-(m2t_ssim_loss, fp64 inside).  A step with lambda_ssim > 0 takes the MATERIALISED seed (immediate pixel loss, then m2t_ssim_loss adds
-into it): the seed fused into the x4 tail backward does not apply.  With lambda_ssim = 0 (the default) the step is the one above.
+Optional loss terms (all off by default; LOSS_TERMS below is their table, and its order -- SSIM, MS-SSIM, FFT, VIF, then the
+perceptual term -- is the order of the calls).  Every term that is on takes the MATERIALISED seed: the immediate pixel loss, then one
+``m2t_<term>_loss`` call per term that adds its gradient into the seed, then the backward pass; the seed fused into the x4 tail
+backward does not apply.  An SR size a term does not take is refused on the host before anything is launched.  With a weight of 0
+nothing is allocated for the term and the step issues the calls it issued before.  Value and gradient are HIP, fp64 inside unless
+said otherwise.
 
-Frequency-domain term (``lambda_fft``, ``fft_norm``; the reference imports torch.fft in losses.py:5 and never calls it -- the term
-is MIMO-UNet's L1 on the Fourier coefficients): ``lambda_fft * mean(|Re D|, |Im D|)`` with ``D = rfft2(clamp(sr) / R - hr / R,
-norm=fft_norm)`` per RGB channel, value and gradient in HIP (m2t_fft_loss of include/m2t_spectral.h: a mixed-radix Stockham FFT in
-LDS; SR height and width even, 8 .. 2048, of the form 2^a 3^b).  Like lambda_ssim it takes the MATERIALISED seed, and the calls
-run in the order pixel -> SSIM (if on) -> FFT -> backward.  With lambda_fft = 0 (the default) nothing is allocated and the step
-issues the calls it issued before.
-
-Multi-scale structural term (``lambda_msssim``; the reference imports MultiScaleSSIMLoss from piq in the same line, losses.py:8; L1 +
-MS-SSIM is the recipe of Zhao et al.): ``lambda_msssim * (1 - mean MS-SSIM)`` per image and RGB channel in the
-pytorch_msssim.ms_ssim / piq.multi_scale_ssim form (five levels, the 2 x 2 average between them), value and gradient in HIP
-(m2t_msssim_loss of include/m2t_msssim.h, fp64 inside; SR height and width > 160).  An (image, channel) with a non-positive level
-mean has MS-SSIM 0 and adds no gradient.  It takes the MATERIALISED seed like the other two terms; the calls run in the order
-pixel -> SSIM (if on) -> MS-SSIM (if on) -> FFT (if on) -> backward.  With lambda_msssim = 0 (the default) nothing is allocated and
-the step issues the calls it issued before.
-
-Information-fidelity term (``lambda_vif``; the reference imports VIFLoss from piq in the same line, losses.py:8):
-``lambda_vif * (1 - mean VIF)`` per image, the pixel-domain VIF of Sheikh & Bovik in the piq.vif_p form on the luminance of
-``clamp(sr, 0, rgb_range)`` and ``hr`` (four scales, windows of 17 / 9 / 5 / 3 taps, sigma_n_sq = 2), value and gradient in HIP
-(m2t_vif_loss of include/m2t_vif.h, fp64 inside; SR height and width >= 41).  VIF exceeds 1 for a contrast-enhanced output, so the
-term may be negative; it is not clipped.  It takes the MATERIALISED seed like the other terms; the calls run in the order
-pixel -> SSIM -> MS-SSIM -> FFT -> VIF (each if on) -> backward.  With lambda_vif = 0 (the default) nothing is allocated and the
-step issues the calls it issued before.
+* ``lambda_ssim`` (the reference imports SSIMLoss from piq next to the pixel criteria, losses.py:8, and scores every epoch by SSIM,
+  utils.py:232-234): ``lambda_ssim * (1 - mean SSIM)`` per RGB channel in the pytorch_msssim.ssim / piq.ssim(downsample=False) form --
+  piq.SSIMLoss's default ``downsample=True`` pooling is NOT applied (m2t_ssim_loss; SR height and width >= 11).
+* ``lambda_msssim`` (MultiScaleSSIMLoss of the same import; L1 + MS-SSIM is the recipe of Zhao et al.): ``lambda_msssim * (1 - mean
+  MS-SSIM)`` per image and RGB channel in the pytorch_msssim.ms_ssim / piq.multi_scale_ssim form, five levels with the 2 x 2 average
+  between them (m2t_msssim_loss of include/m2t_msssim.h; SR height and width > 160).  An (image, channel) with a non-positive level
+  mean has MS-SSIM 0 and adds no gradient.
+* ``lambda_fft``, ``fft_norm`` (the reference imports torch.fft in losses.py:5 and never calls it -- the term is MIMO-UNet's L1 on the
+  Fourier coefficients): ``lambda_fft * mean(|Re D|, |Im D|)`` with ``D = rfft2(clamp(sr) / R - hr / R, norm=fft_norm)`` per RGB
+  channel (m2t_fft_loss of include/m2t_spectral.h: a mixed-radix Stockham FFT in LDS, fp32 butterflies; SR height and width even,
+  8 .. 2048, of the form 2^a 3^b).
+* ``lambda_vif`` (VIFLoss of the same import): ``lambda_vif * (1 - mean VIF)`` per image, the pixel-domain VIF of Sheikh & Bovik in
+  the piq.vif_p form on the luminance of ``clamp(sr, 0, rgb_range)`` and ``hr``, four scales, windows of 17 / 9 / 5 / 3 taps,
+  sigma_n_sq = 2 (m2t_vif_loss of include/m2t_vif.h; SR height and width >= 41).  VIF exceeds 1 for a contrast-enhanced output, so
+  the term may be negative; it is not clipped.
+* ``lambda_perceptual``, ``perceptual_loss=`` (PerceptualLoss of the reference's losses.py:222-270): ``lambda_perceptual * sum_k w_k
+  mean(crit(F_k(sr) - F_k(hr)))`` on VGG19 features; the tower, its weights, its workspace, the criterion and the tap weights are
+  those of the losses.PerceptualLoss object (m2t_vgg_loss of include/m2t_perceptual.h, bf16 compute; SR height and width >= 16).
 
 Parameter groups and frozen tensors (``param_groups=``; replaces ``torch.optim.Adam([{"params": ..., "lr": ...,
 "weight_decay": ...}, ...])`` over a model part of which has ``requires_grad = False``; param_groups.py resolves the spec by name):
@@ -71,8 +68,9 @@ of m2t_backward.  ``param_groups="requires_grad"`` freezes the trainable tensors
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
-from typing import Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -120,74 +118,22 @@ def resolve_pixel_loss(name, param=None):
     return kind, canon, value
 
 
-def resolve_lambda_ssim(value) -> float:
-    """TrainStep's ``lambda_ssim`` as a float; M2TError unless it is a finite number >= 0."""
+def resolve_lambda(name: str, value) -> float:
+    """TrainStep's ``lambda_<name>`` as a float; M2TError unless it is a finite number >= 0."""
     try:
         v = float(value)
     except (TypeError, ValueError):
-        raise _lib.M2TError(f"lambda_ssim must be a finite number >= 0, got {value!r}") from None
+        v = math.nan
     if not (math.isfinite(v) and v >= 0.0):
-        raise _lib.M2TError(f"lambda_ssim must be a finite number >= 0, got {value!r}")
+        raise _lib.M2TError(f"lambda_{name} must be a finite number >= 0, got {value!r}")
     return v
 
 
-def resolve_lambda_msssim(value) -> float:
-    """TrainStep's ``lambda_msssim`` as a float; M2TError unless it is a finite number >= 0."""
-    try:
-        v = float(value)
-    except (TypeError, ValueError):
-        raise _lib.M2TError(f"lambda_msssim must be a finite number >= 0, got {value!r}") from None
-    if not (math.isfinite(v) and v >= 0.0):
-        raise _lib.M2TError(f"lambda_msssim must be a finite number >= 0, got {value!r}")
-    return v
-
-
-def msssim_size_supported(h: int, w: int) -> bool:
-    """The sizes the multi-scale term takes (the rule of include/m2t_msssim.h, decided on the host): min(H, W) > 160."""
-    return min(int(h), int(w)) >= _lib.MSSSIM_MIN_SIDE
-
-
-def resolve_lambda_vif(value) -> float:
-    """TrainStep's ``lambda_vif`` as a float; M2TError unless it is a finite number >= 0."""
-    try:
-        v = float(value)
-    except (TypeError, ValueError):
-        raise _lib.M2TError(f"lambda_vif must be a finite number >= 0, got {value!r}") from None
-    if not (math.isfinite(v) and v >= 0.0):
-        raise _lib.M2TError(f"lambda_vif must be a finite number >= 0, got {value!r}")
-    return v
-
-
-def resolve_lambda_perceptual(value) -> float:
-    """TrainStep's ``lambda_perceptual`` as a float; M2TError unless it is a finite number >= 0."""
-    try:
-        v = float(value)
-    except (TypeError, ValueError):
-        raise _lib.M2TError(f"lambda_perceptual must be a finite number >= 0, got {value!r}") from None
-    if not (math.isfinite(v) and v >= 0.0):
-        raise _lib.M2TError(f"lambda_perceptual must be a finite number >= 0, got {value!r}")
-    return v
-
-
-def perceptual_size_supported(h: int, w: int) -> bool:
-    """The sizes the VGG19 feature term takes (the rule of include/m2t_perceptual.h, decided on the host): min(H, W) >= 16."""
-    return min(int(h), int(w)) >= _lib.VGG_MIN_SIDE
-
-
-def vif_size_supported(h: int, w: int) -> bool:
-    """The sizes the information-fidelity term takes (the rule of include/m2t_vif.h, decided on the host): min(H, W) >= 41."""
-    return min(int(h), int(w)) >= _lib.VIF_MIN_SIDE
-
-
-def resolve_lambda_fft(value) -> float:
-    """TrainStep's ``lambda_fft`` as a float; M2TError unless it is a finite number >= 0."""
-    try:
-        v = float(value)
-    except (TypeError, ValueError):
-        raise _lib.M2TError(f"lambda_fft must be a finite number >= 0, got {value!r}") from None
-    if not (math.isfinite(v) and v >= 0.0):
-        raise _lib.M2TError(f"lambda_fft must be a finite number >= 0, got {value!r}")
-    return v
+resolve_lambda_ssim = functools.partial(resolve_lambda, "ssim")
+resolve_lambda_msssim = functools.partial(resolve_lambda, "msssim")
+resolve_lambda_fft = functools.partial(resolve_lambda, "fft")
+resolve_lambda_vif = functools.partial(resolve_lambda, "vif")
+resolve_lambda_perceptual = functools.partial(resolve_lambda, "perceptual")
 
 
 def resolve_fft_norm(name) -> str:
@@ -196,6 +142,21 @@ def resolve_fft_norm(name) -> str:
     if not isinstance(key, str) or key not in _lib.FFT_NORMS:
         raise _lib.M2TError(f"fft_norm must be one of {sorted(_lib.FFT_NORMS)}, got {name!r}")
     return key
+
+
+def msssim_size_supported(h: int, w: int) -> bool:
+    """The sizes the multi-scale term takes (the rule of include/m2t_msssim.h, decided on the host): min(H, W) > 160."""
+    return min(int(h), int(w)) >= _lib.MSSSIM_MIN_SIDE
+
+
+def vif_size_supported(h: int, w: int) -> bool:
+    """The sizes the information-fidelity term takes (the rule of include/m2t_vif.h, decided on the host): min(H, W) >= 41."""
+    return min(int(h), int(w)) >= _lib.VIF_MIN_SIDE
+
+
+def perceptual_size_supported(h: int, w: int) -> bool:
+    """The sizes the VGG19 feature term takes (the rule of include/m2t_perceptual.h, decided on the host): min(H, W) >= 16."""
+    return min(int(h), int(w)) >= _lib.VGG_MIN_SIDE
 
 
 FFT_SIZE_RULE = "even, 8 .. 2048 and of the form 2^a * 3^b"
@@ -213,6 +174,46 @@ def fft_size_supported(n: int) -> bool:
     return n == 1
 
 
+class LossTerm(NamedTuple):
+    """One optional term whose scratch the step owns.  From the name follow the step's attributes ``lambda_<n>`` (weight, 0 = off),
+    ``<n>_loss`` (device float [1], already weighted: this rank's share of the global mean) and ``_<n>_scratch`` ((B, Hs, Ws) -> the
+    kernels' scratch, allocated once per plan shape), and the entries ``m2t_<n>_loss`` / ``m2t_<n>_loss_scratch_bytes``; the fields
+    are what differs between the terms.  The two refusals follow "lambda_<n> > 0: " and are formatted with B, Hs, Ws."""
+    name: str
+    size_ok: Callable       # (Hs, Ws) -> bool: the SR sizes the kernels take, decided on the host
+    too_small: str          # the refusal of a size outside that rule
+    no_scratch: str         # the refusal of a shape the library names no scratch size for
+    count: Callable         # (B, Hs, Ws) -> what the term's mean runs over on this rank (the global divisor is built from it)
+    extra: Callable         # (step) -> the term's own arguments of m2t_<n>_loss, between rgb_range and the value
+
+
+# in call order: pixel -> these (each if on) -> the perceptual term (if on) -> backward
+LOSS_TERMS = (
+    LossTerm("ssim", lambda hs, ws: min(hs, ws) >= 11,
+             "the SR image {Hs}x{Ws} is smaller than the 11 x 11 SSIM window",
+             "the SR image {Hs}x{Ws} is smaller than the 11 x 11 SSIM window",
+             lambda b, hs, ws: b * 3 * (hs - 10) * (ws - 10),         # entries of the valid map
+             lambda step: ()),
+    LossTerm("msssim", msssim_size_supported,
+             "the SR image {Hs}x{Ws} is too small for five levels under the 11-tap window (height and width must be larger than 160)",
+             "no scratch size for a batch of {B} SR images {Hs}x{Ws} (B * 3 <= 65535)",
+             lambda b, hs, ws: b * 3,                                 # (image, channel) pairs
+             lambda step: ()),
+    LossTerm("fft", lambda hs, ws: fft_size_supported(hs) and fft_size_supported(ws),
+             "the SR image {Hs}x{Ws} is not supported by the HIP transform (height and width must be " + FFT_SIZE_RULE + ")",
+             "no scratch size for a batch of {B} SR images {Hs}x{Ws} (B * 3 <= 65535; height and width " + FFT_SIZE_RULE + ")",
+             lambda b, hs, ws: b * 3 * hs * (ws // 2 + 1) * 2,        # reals of the half spectrum
+             lambda step: (_lib.FFT_NORMS[step.fft_norm],)),
+    LossTerm("vif", vif_size_supported,
+             "the SR image {Hs}x{Ws} is too small for four scales under the 17 / 9 / 5 / 3-tap windows (height and width must be at "
+             "least 41)",
+             "no scratch size for a batch of {B} SR images {Hs}x{Ws} (B <= 65535)",
+             lambda b, hs, ws: b,                                     # images (luminance: not times 3)
+             lambda step: (_lib.VIF_SIGMA_N_SQ,)),
+)
+_TERM = {t.name: t for t in LOSS_TERMS}
+
+
 _STREAMS: dict = {}
 
 
@@ -226,13 +227,22 @@ def _shared_stream(device, role: str):
     return _STREAMS[key]
 
 
+def _refuse_mid_cycle(step, what: str):
+    """A setting that changes what a micro-batch computes may not change between the micro-batches of one optimizer step."""
+    if getattr(step, "micro_count", 0) != 0:
+        raise _lib.M2TError(f"{what} in the middle of an accumulation cycle ({step.micro_count} of {step.accum_steps} "
+                            "micro-batches since the last optimizer step)")
+
+
 class TrainStep:
-    # (defaults of the newest term for step objects assembled without __init__)
-    lambda_vif = 0.0
-    vif_loss = None
-    lambda_perceptual = 0.0
+    # The state of the optional terms, off: what __init__ starts from and what a step object assembled without __init__ has.  A term
+    # of LOSS_TERMS has its weight, its device [1] value and its per-shape scratch cache (None: the dict is made per object, on first
+    # use or by the setter); the perceptual term keeps its value next to the PerceptualLoss object, whose workspace is its own.
+    lambda_ssim = lambda_msssim = lambda_fft = lambda_vif = lambda_perceptual = 0.0
+    ssim_loss = msssim_loss = fft_loss = vif_loss = perceptual_loss_value = None
+    _ssim_scratch = _msssim_scratch = _fft_scratch = _vif_scratch = None
+    fft_norm = "backward"
     perceptual_loss = None
-    perceptual_loss_value = None
     groups = None
     _need_stage = None
 
@@ -252,27 +262,12 @@ class TrainStep:
         self.groups = resolve_param_groups(model, param_groups)
         # the pixel term: lambda_l1 (the reference's config key) stays its weight and l1_loss the tensor that holds it, whatever the kind
         self.set_pixel_loss(pixel_loss, pixel_loss_param)
-        # the structural term lambda_ssim * (1 - mean SSIM): 0 = off (nothing allocated, the step issues the calls it always issued)
-        self.ssim_loss = None                   # device float [1], already weighted (this rank's share of the global mean)
-        self._ssim_scratch = {}                 # (B, Hs, Ws) -> the kernel's partial-sum scratch, allocated once per plan shape
+        # the optional terms, each lambda * (its measure): 0 = off (nothing allocated, the step issues the calls it always issued)
         self.set_lambda_ssim(lambda_ssim)
-        # the multi-scale structural term lambda_msssim * (1 - mean MS-SSIM): 0 = off (nothing allocated, no call more)
-        self.msssim_loss = None                 # device float [1], already weighted
-        self._msssim_scratch = {}               # (B, Hs, Ws) -> pyramids, gradient levels, partial sums, record: once per plan shape
         self.set_lambda_msssim(lambda_msssim)
-        # the frequency-domain term lambda_fft * mean |rfft2(sr - hr)|: 0 = off (nothing allocated, no call more)
-        self.fft_loss = None                    # device float [1], already weighted
-        self._fft_scratch = {}                  # (B, Hs, Ws) -> the half spectrum + partial sums, allocated once per plan shape
-        self.fft_norm = "backward"
         self.set_lambda_fft(lambda_fft, fft_norm)
-        # the information-fidelity term lambda_vif * (1 - mean VIF): 0 = off (nothing allocated, no call more)
-        self.vif_loss = None                    # device float [1], already weighted (may be negative: VIF can exceed 1)
-        self._vif_scratch = {}                  # (B, Hs, Ws) -> pyramids, gradient levels, partial sums, record: once per plan shape
         self.set_lambda_vif(lambda_vif)
-        # the VGG19 feature term lambda_perceptual * sum_k w_k mean(crit(F_k(sr) - F_k(hr))): 0 = off (nothing allocated, no call more);
-        # the tower, its weights, the criterion and the tap weights are those of the losses.PerceptualLoss object
         self.perceptual_loss = perceptual_loss
-        self.perceptual_loss_value = None       # device float [1], already weighted
         self.set_lambda_perceptual(lambda_perceptual)
         # gradient accumulation: one optimizer step consumes accum_steps equal micro-batches (forward_backward calls); the
         # gradients and the loss of calls 2..k of a cycle are added to the first call's by m2t_grad_accumulate
@@ -386,162 +381,99 @@ class TrainStep:
     def set_pixel_loss(self, name, param=None):
         """Choose the pixel loss: 'l1', 'mse' (alias 'l2'), 'charbonnier' (param = eps, default 1e-6), 'smooth_l1' (alias 'sl1';
         param = beta, default 1.0).  Takes effect with the next forward_backward (checkpoint.import_checkpoint calls this)."""
-        if getattr(self, "micro_count", 0) != 0:
-            raise _lib.M2TError(f"set_pixel_loss in the middle of an accumulation cycle ({self.micro_count} of {self.accum_steps} "
-                                "micro-batches since the last optimizer step)")
+        _refuse_mid_cycle(self, "set_pixel_loss")
         self._pixel_kind, self.pixel_loss, self.pixel_loss_param = resolve_pixel_loss(name, param)
+
+    # -- the optional terms of LOSS_TERMS: one setter, one scratch cache and one call for all of them -----------------------
+    def _set_lambda(self, term: LossTerm, value):
+        """Weight of one term (0 = off): the [1] value exists while the term is on; turning it off drops value and scratch."""
+        n = term.name
+        _refuse_mid_cycle(self, f"set_lambda_{n}")
+        lam = resolve_lambda(n, value)
+        setattr(self, f"lambda_{n}", lam)
+        if lam > 0.0:
+            if getattr(self, f"{n}_loss") is None:
+                setattr(self, f"{n}_loss", torch.zeros(1, dtype=torch.float32, device=self.model.flat_params.device))
+        else:
+            setattr(self, f"{n}_loss", None)
+            setattr(self, f"_{n}_scratch", {})
 
     def set_lambda_ssim(self, value):
         """Weight of the structural term (0 = off).  Takes effect with the next forward_backward (checkpoint.import_checkpoint
         calls this); refused in the middle of an accumulation cycle."""
-        if getattr(self, "micro_count", 0) != 0:
-            raise _lib.M2TError(f"set_lambda_ssim in the middle of an accumulation cycle ({self.micro_count} of {self.accum_steps} "
-                                "micro-batches since the last optimizer step)")
-        self.lambda_ssim = resolve_lambda_ssim(value)
-        if self.lambda_ssim > 0.0:
-            if self.ssim_loss is None:
-                self.ssim_loss = torch.zeros(1, dtype=torch.float32, device=self.model.flat_params.device)
-        else:
-            self.ssim_loss, self._ssim_scratch = None, {}
-
-    def _ssim_loss_call(self, lib, plan, hr_img, first: bool, ws, st):
-        """m2t_ssim_loss of one (micro-)batch, behind the immediate pixel loss: adds into the materialised seed; the value is stored
-        by the first micro-batch of a cycle and added to by the others."""
-        B, _, Hs, Ws = hr_img.shape
-        key = (B, Hs, Ws)
-        if key not in self._ssim_scratch:
-            nbytes = int(lib.m2t_ssim_loss_scratch_bytes(B, 3, Hs, Ws))
-            if nbytes == 0:
-                raise _lib.M2TError(f"lambda_ssim > 0: the SR image {Hs}x{Ws} is smaller than the 11 x 11 SSIM window")
-            self._ssim_scratch[key] = torch.empty(nbytes, dtype=torch.uint8, device=hr_img.device)
-        divisor = global_divisor(B * 3 * (Hs - 10) * (Ws - 10), self.world_size, self.accum_steps)     # global number of map entries
-        _lib.check(lib.m2t_ssim_loss(plan.handle, _lib.ptr(hr_img), self.lambda_ssim, divisor, float(self.model.rgb_range),
-                                     _lib.ptr(self.ssim_loss), 0 if first else 1, _lib.ptr(self._ssim_scratch[key]), ws, st),
-                   "m2t_ssim_loss")
+        self._set_lambda(_TERM["ssim"], value)
 
     def set_lambda_msssim(self, value):
         """Weight of the multi-scale structural term (0 = off).  Takes effect with the next forward_backward
         (checkpoint.import_checkpoint calls this); refused in the middle of an accumulation cycle."""
-        if getattr(self, "micro_count", 0) != 0:
-            raise _lib.M2TError(f"set_lambda_msssim in the middle of an accumulation cycle ({self.micro_count} of {self.accum_steps} "
-                                "micro-batches since the last optimizer step)")
-        self.lambda_msssim = resolve_lambda_msssim(value)
-        if self.lambda_msssim > 0.0:
-            if self.msssim_loss is None:
-                self.msssim_loss = torch.zeros(1, dtype=torch.float32, device=self.model.flat_params.device)
-        else:
-            self.msssim_loss, self._msssim_scratch = None, {}
-
-    def _msssim_scratch_for(self, lib, hr_img):
-        """The scratch of the multi-scale term for this (micro-)batch shape, allocated once; an SR size below the five-level rule
-        is refused here, on the host, before anything is launched."""
-        B, _, Hs, Ws = hr_img.shape
-        key = (B, Hs, Ws)
-        if key not in self._msssim_scratch:
-            if not msssim_size_supported(Hs, Ws):
-                raise _lib.M2TError(f"lambda_msssim > 0: the SR image {Hs}x{Ws} is too small for five levels under the 11-tap window "
-                                    "(height and width must be larger than 160)")
-            nbytes = int(lib.m2t_msssim_loss_scratch_bytes(B, 3, Hs, Ws))
-            if nbytes == 0:
-                raise _lib.M2TError(f"lambda_msssim > 0: no scratch size for a batch of {B} SR images {Hs}x{Ws} (B * 3 <= 65535)")
-            self._msssim_scratch[key] = torch.empty(nbytes, dtype=torch.uint8, device=hr_img.device)
-        return self._msssim_scratch[key]
-
-    def _msssim_loss_call(self, lib, plan, hr_img, first: bool, ws, st):
-        """m2t_msssim_loss of one (micro-)batch, behind the immediate pixel loss (and the SSIM term): adds into the materialised
-        seed; the value is stored by the first micro-batch of a cycle and added to by the others."""
-        B = hr_img.shape[0]
-        divisor = global_divisor(B * 3, self.world_size, self.accum_steps)       # global number of (image, channel) pairs
-        _lib.check(lib.m2t_msssim_loss(plan.handle, _lib.ptr(hr_img), self.lambda_msssim, divisor, float(self.model.rgb_range),
-                                       _lib.ptr(self.msssim_loss), 0 if first else 1, _lib.ptr(self._msssim_scratch_for(lib, hr_img)),
-                                       ws, st), "m2t_msssim_loss")
+        self._set_lambda(_TERM["msssim"], value)
 
     def set_lambda_fft(self, value, norm=None):
         """Weight of the frequency-domain term (0 = off) and, when given, its normalisation ('backward' / 'ortho').  Takes effect
         with the next forward_backward (checkpoint.import_checkpoint calls this); refused in the middle of an accumulation cycle."""
-        if getattr(self, "micro_count", 0) != 0:
-            raise _lib.M2TError(f"set_lambda_fft in the middle of an accumulation cycle ({self.micro_count} of {self.accum_steps} "
-                                "micro-batches since the last optimizer step)")
-        lam = resolve_lambda_fft(value)
+        _refuse_mid_cycle(self, "set_lambda_fft")
+        lam = resolve_lambda("fft", value)      # (a refused weight leaves the normalisation as it was)
         if norm is not None:
             self.fft_norm = resolve_fft_norm(norm)
-        self.lambda_fft = lam
-        if self.lambda_fft > 0.0:
-            if self.fft_loss is None:
-                self.fft_loss = torch.zeros(1, dtype=torch.float32, device=self.model.flat_params.device)
-        else:
-            self.fft_loss, self._fft_scratch = None, {}
-
-    def _fft_scratch_for(self, lib, hr_img):
-        """The scratch of the frequency-domain term for this (micro-)batch shape, allocated once; an SR size the HIP transform does
-        not take is refused here, on the host, before anything is launched."""
-        B, _, Hs, Ws = hr_img.shape
-        key = (B, Hs, Ws)
-        if key not in self._fft_scratch:
-            if not (fft_size_supported(Hs) and fft_size_supported(Ws)):
-                raise _lib.M2TError(f"lambda_fft > 0: the SR image {Hs}x{Ws} is not supported by the HIP transform (height and width "
-                                    f"must be {FFT_SIZE_RULE})")
-            nbytes = int(lib.m2t_fft_loss_scratch_bytes(B, 3, Hs, Ws))
-            if nbytes == 0:
-                raise _lib.M2TError(f"lambda_fft > 0: no scratch size for a batch of {B} SR images {Hs}x{Ws} (B * 3 <= 65535; height "
-                                    f"and width {FFT_SIZE_RULE})")
-            self._fft_scratch[key] = torch.empty(nbytes, dtype=torch.uint8, device=hr_img.device)
-        return self._fft_scratch[key]
-
-    def _fft_loss_call(self, lib, plan, hr_img, first: bool, ws, st):
-        """m2t_fft_loss of one (micro-)batch, behind the immediate pixel loss (and the structural term): adds into the materialised
-        seed; the value is stored by the first micro-batch of a cycle and added to by the others."""
-        B, _, Hs, Ws = hr_img.shape
-        divisor = global_divisor(B * 3 * Hs * (Ws // 2 + 1) * 2, self.world_size, self.accum_steps)     # global number of reals
-        _lib.check(lib.m2t_fft_loss(plan.handle, _lib.ptr(hr_img), self.lambda_fft, divisor, float(self.model.rgb_range),
-                                    _lib.FFT_NORMS[self.fft_norm], _lib.ptr(self.fft_loss), 0 if first else 1,
-                                    _lib.ptr(self._fft_scratch_for(lib, hr_img)), ws, st), "m2t_fft_loss")
+        self._set_lambda(_TERM["fft"], lam)
 
     def set_lambda_vif(self, value):
         """Weight of the information-fidelity term (0 = off).  Takes effect with the next forward_backward
         (checkpoint.import_checkpoint calls this); refused in the middle of an accumulation cycle."""
-        if getattr(self, "micro_count", 0) != 0:
-            raise _lib.M2TError(f"set_lambda_vif in the middle of an accumulation cycle ({self.micro_count} of {self.accum_steps} "
-                                "micro-batches since the last optimizer step)")
-        self.lambda_vif = resolve_lambda_vif(value)
-        if self.lambda_vif > 0.0:
-            if self.vif_loss is None:
-                self.vif_loss = torch.zeros(1, dtype=torch.float32, device=self.model.flat_params.device)
-        else:
-            self.vif_loss, self._vif_scratch = None, {}
+        self._set_lambda(_TERM["vif"], value)
+
+    def _scratch_for(self, term: LossTerm, lib, hr_img):
+        """The scratch of one term for this (micro-)batch shape, allocated once; an SR size the term does not take is refused here,
+        on the host, before anything is launched."""
+        n = term.name
+        B, _, Hs, Ws = hr_img.shape
+        cache = getattr(self, f"_{n}_scratch")
+        if cache is None:
+            cache = {}
+            setattr(self, f"_{n}_scratch", cache)
+        key = (B, Hs, Ws)
+        if key not in cache:
+            if not term.size_ok(Hs, Ws):
+                raise _lib.M2TError(f"lambda_{n} > 0: " + term.too_small.format(B=B, Hs=Hs, Ws=Ws))
+            nbytes = int(getattr(lib, f"m2t_{n}_loss_scratch_bytes")(B, 3, Hs, Ws))
+            if nbytes == 0:
+                raise _lib.M2TError(f"lambda_{n} > 0: " + term.no_scratch.format(B=B, Hs=Hs, Ws=Ws))
+            cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=hr_img.device)
+        return cache[key]
+
+    def _msssim_scratch_for(self, lib, hr_img):
+        return self._scratch_for(_TERM["msssim"], lib, hr_img)
+
+    def _fft_scratch_for(self, lib, hr_img):
+        return self._scratch_for(_TERM["fft"], lib, hr_img)
 
     def _vif_scratch_for(self, lib, hr_img):
-        """The scratch of the information-fidelity term for this (micro-)batch shape, allocated once; an SR size below the
-        four-scale rule is refused here, on the host, before anything is launched."""
+        return self._scratch_for(_TERM["vif"], lib, hr_img)
+
+    @staticmethod
+    def _store_or_add(first: bool) -> int:
+        """The accumulate flag of every m2t_*_loss call: a term's value is stored by the first micro-batch of a cycle and added to
+        by the others."""
+        return 0 if first else 1
+
+    def _term_call(self, term: LossTerm, lib, plan, hr_img, first: bool, ws, st):
+        """m2t_<n>_loss of one (micro-)batch, behind the immediate pixel loss and the terms in front of it: adds into the
+        materialised seed.  The divisor is the GLOBAL count of what the term's mean runs over."""
+        n = term.name
         B, _, Hs, Ws = hr_img.shape
-        key = (B, Hs, Ws)
-        if key not in self._vif_scratch:
-            if not vif_size_supported(Hs, Ws):
-                raise _lib.M2TError(f"lambda_vif > 0: the SR image {Hs}x{Ws} is too small for four scales under the 17 / 9 / 5 / 3-tap "
-                                    "windows (height and width must be at least 41)")
-            nbytes = int(lib.m2t_vif_loss_scratch_bytes(B, 3, Hs, Ws))
-            if nbytes == 0:
-                raise _lib.M2TError(f"lambda_vif > 0: no scratch size for a batch of {B} SR images {Hs}x{Ws} (B <= 65535)")
-            self._vif_scratch[key] = torch.empty(nbytes, dtype=torch.uint8, device=hr_img.device)
-        return self._vif_scratch[key]
+        divisor = global_divisor(term.count(B, Hs, Ws), self.world_size, self.accum_steps)
+        entry = f"m2t_{n}_loss"
+        _lib.check(getattr(lib, entry)(plan.handle, _lib.ptr(hr_img), getattr(self, f"lambda_{n}"), divisor, float(self.model.rgb_range),
+                                       *term.extra(self), _lib.ptr(getattr(self, f"{n}_loss")), self._store_or_add(first),
+                                       _lib.ptr(self._scratch_for(term, lib, hr_img)), ws, st), entry)
 
-    def _vif_loss_call(self, lib, plan, hr_img, first: bool, ws, st):
-        """m2t_vif_loss of one (micro-)batch, behind the immediate pixel loss and the other terms: adds into the materialised seed;
-        the value is stored by the first micro-batch of a cycle and added to by the others."""
-        B = hr_img.shape[0]
-        divisor = global_divisor(B, self.world_size, self.accum_steps)           # global number of images (luminance: not times 3)
-        _lib.check(lib.m2t_vif_loss(plan.handle, _lib.ptr(hr_img), self.lambda_vif, divisor, float(self.model.rgb_range),
-                                    _lib.VIF_SIGMA_N_SQ, _lib.ptr(self.vif_loss), 0 if first else 1,
-                                    _lib.ptr(self._vif_scratch_for(lib, hr_img)), ws, st), "m2t_vif_loss")
-
+    # -- the perceptual term: the same slot in the order and in the total, its own preconditions, workspace and call ---------------
     def set_lambda_perceptual(self, value):
         """Weight of the VGG19 feature term (0 = off); needs ``perceptual_loss=`` (a losses.PerceptualLoss with weights loaded, resize
         off, data_range = the model's rgb_range).  Takes effect with the next forward_backward; refused in the middle of an
         accumulation cycle."""
-        if getattr(self, "micro_count", 0) != 0:
-            raise _lib.M2TError(f"set_lambda_perceptual in the middle of an accumulation cycle ({self.micro_count} of {self.accum_steps} "
-                                "micro-batches since the last optimizer step)")
-        self.lambda_perceptual = resolve_lambda_perceptual(value)
+        _refuse_mid_cycle(self, "set_lambda_perceptual")
+        self.lambda_perceptual = resolve_lambda("perceptual", value)
         if self.lambda_perceptual > 0.0:
             p = self.perceptual_loss
             if p is None:
@@ -568,24 +500,28 @@ class TrainStep:
         return self.perceptual_loss.workspace(B, Hs, Ws, True)
 
     def _perceptual_loss_call(self, lib, plan, hr_img, first: bool, ws, st):
-        """m2t_vgg_loss of one (micro-)batch, behind the immediate pixel loss and the other terms: adds into the materialised seed;
-        the value is stored by the first micro-batch of a cycle and added to by the others."""
+        """m2t_vgg_loss of one (micro-)batch, behind the immediate pixel loss and the other terms: adds into the materialised seed."""
         p = self.perceptual_loss
         divisor = global_divisor(hr_img.shape[0], self.world_size, self.accum_steps)     # global number of images
         _lib.check(lib.m2t_vgg_loss(plan.handle, p.handle, _lib.ptr(hr_img), self.lambda_perceptual, divisor, float(self.model.rgb_range),
-                                    p.kind, p.param, p.tap_weights(), _lib.ptr(self.perceptual_loss_value), 0 if first else 1,
+                                    p.kind, p.param, p.tap_weights(), _lib.ptr(self.perceptual_loss_value), self._store_or_add(first),
                                     _lib.ptr(self._perceptual_workspace_for(hr_img)), ws, st), "m2t_vgg_loss")
 
-    def _total_loss(self, with_clip: bool):
-        loss = self.l1_loss if self.ssim_loss is None else self.l1_loss + self.ssim_loss
-        if self.msssim_loss is not None:
-            loss = loss + self.msssim_loss
-        if self.fft_loss is not None:
-            loss = loss + self.fft_loss
-        if self.vif_loss is not None:
-            loss = loss + self.vif_loss
-        if self.perceptual_loss_value is not None:
-            loss = loss + self.perceptual_loss_value
+    # -- what forward_backward iterates ------------------------------------------------------------------------------------
+    def _terms_on(self, lib) -> list:
+        """The optional terms that are on, in call order -- the rows of LOSS_TERMS, then the perceptual term -- each as (value,
+        prepare, call): the term's device [1] tensor; prepare(hr_img), which refuses an SR size the term does not take and makes
+        sure of its scratch before anything is launched; call(plan, hr_img, first, ws, st), its m2t_*_loss call."""
+        on = [(getattr(self, f"{t.name}_loss"), functools.partial(self._scratch_for, t, lib), functools.partial(self._term_call, t, lib))
+              for t in LOSS_TERMS if getattr(self, f"lambda_{t.name}") > 0.0]
+        if self.lambda_perceptual > 0.0:
+            on.append((self.perceptual_loss_value, self._perceptual_workspace_for, functools.partial(self._perceptual_loss_call, lib)))
+        return on
+
+    def _total_loss(self, on: list, with_clip: bool):
+        loss = self.l1_loss
+        for value, _, _ in on:
+            loss = loss + value
         return loss + self.clip_loss if with_clip else loss
 
     def _pixel_loss_call(self, lib, deferred: bool, plan, hr_img, divisor, l1_loss, ws, st):
@@ -618,9 +554,7 @@ class TrainStep:
         """Exchange the contents of model.flat_params and ema_params in place (a validation sweep between epochs runs the model on
         the EMA weights, a second call puts every bit back).  Plain torch copies: this is off the timed path."""
         self._need_ema("swap_ema")
-        if self.micro_count != 0:
-            raise _lib.M2TError(f"swap_ema in the middle of an accumulation cycle ({self.micro_count} of {self.accum_steps} "
-                                "micro-batches since the last optimizer step)")
+        _refuse_mid_cycle(self, "swap_ema")
         flat = self.model.flat_params
         with torch.no_grad():
             tmp = flat.detach().clone()
@@ -648,21 +582,16 @@ class TrainStep:
         B = lr_img.shape[0]
         if tuple(hr_img.shape) != (B, 3, lr_img.shape[2] * m.scale, lr_img.shape[3] * m.scale):
             raise _lib.M2TError("hr shape must be [B,3,H*scale,W*scale]")
-        if self.lambda_msssim > 0.0:
-            self._msssim_scratch_for(lib, hr_img)   # (refuses an SR size below the five-level rule before any launch)
-        if self.lambda_fft > 0.0:
-            self._fft_scratch_for(lib, hr_img)      # (refuses an SR size outside the transform's rule before any launch)
-        if self.lambda_vif > 0.0:
-            self._vif_scratch_for(lib, hr_img)      # (refuses an SR size below the four-scale rule before any launch)
-        if self.lambda_perceptual > 0.0:
-            self._perceptual_workspace_for(hr_img)  # (refuses an SR size below 16 before any launch)
+        on = self._terms_on(lib)
+        for _, prepare, _ in on:
+            prepare(hr_img)                         # (refuses an SR size the term does not take before any launch)
         divisor = global_divisor(hr_img.numel(), self.world_size, self.accum_steps)      # global mean (equal shards, equal micro-batches)
         use_clip = self.semantic_loss is not None and self.lambda_clip > 0 and captions is not None
         # (micro-batches 2..k of a cycle: a second gradient buffer and a second loss slot, added to the first ones below)
         grads = self.grads if first else self.micro_grads
         l1_loss = self.l1_loss if first else self.micro_loss
         if use_clip and getattr(self.semantic_loss, "differentiable", False):
-            return self._forward_backward_semantic_grad(m, lib, plan, lr_img, hr_img, captions, divisor, grads, l1_loss)
+            return self._forward_backward_semantic_grad(m, lib, plan, lr_img, hr_img, captions, divisor, grads, l1_loss, on)
         sr = torch.empty_like(hr_img) if use_clip else None
         plan.gen += 1
         plan.trained = True              # (the plan LRU of the model keeps training plans while forward-only ones remain)
@@ -674,22 +603,11 @@ class TrainStep:
                                        float(m.rgb_range), 1, ws, st), "m2t_forward")
             # (deferred: the loss and the backward seed are produced inside m2t_backward, which follows at once -- on the bf16 x4
             #  path by the fused tail backward itself; hr_img stays alive until then)
-            # (lambda_ssim > 0: the materialised seed -- the immediate pixel loss, then the structural term added into it)
-            # (lambda_msssim / lambda_fft / lambda_vif > 0: the same route; the order is pixel -> SSIM -> MS-SSIM -> FFT -> VIF -> backward)
-            # (lambda_perceptual > 0: the same route again, after VIF)
-            ssim, msssim, fft, vif = self.lambda_ssim > 0.0, self.lambda_msssim > 0.0, self.lambda_fft > 0.0, self.lambda_vif > 0.0
-            perc = self.lambda_perceptual > 0.0
-            self._pixel_loss_call(lib, not (ssim or msssim or fft or vif or perc), plan, hr_img, divisor, l1_loss, ws, st)
-            if ssim:
-                self._ssim_loss_call(lib, plan, hr_img, first, ws, st)
-            if msssim:
-                self._msssim_loss_call(lib, plan, hr_img, first, ws, st)
-            if fft:
-                self._fft_loss_call(lib, plan, hr_img, first, ws, st)
-            if vif:
-                self._vif_loss_call(lib, plan, hr_img, first, ws, st)
-            if perc:
-                self._perceptual_loss_call(lib, plan, hr_img, first, ws, st)
+            # (any optional term on: the materialised seed -- the immediate pixel loss, then each term added into it, in the order
+            #  of _terms_on)
+            self._pixel_loss_call(lib, not on, plan, hr_img, divisor, l1_loss, ws, st)
+            for _, _, call in on:
+                call(plan, hr_img, first, ws, st)
             fwd_done = torch.cuda.current_stream(lr_img.device).record_event() if (use_clip and self.overlap_semantic) else None
             self._backward_call(lib, plan, lr_img, grads, ws, st)
             self._accumulate_micro(lib, first, st)
@@ -708,9 +626,7 @@ class TrainStep:
                 main.wait_stream(self.sem_stream)
             else:
                 self._add_clip(self.semantic_loss.batch(sr, hr_img, captions) * self.lambda_clip, first)
-            self.loss = self._total_loss(True)
-        else:
-            self.loss = self._total_loss(False)
+        self.loss = self._total_loss(on, use_clip)
         return self.loss
 
     def _accumulate_micro(self, lib, first: bool, st):
@@ -730,13 +646,14 @@ class TrainStep:
         """The SemanticLoss term of one micro-batch (a per-sample SUM: no divisor) into the cycle's clip_loss."""
         self.clip_loss = clip if first else self.clip_loss + clip
 
-    def _forward_backward_semantic_grad(self, m, lib, plan, lr_img, hr_img, captions, divisor, grads, l1_loss):
+    def _forward_backward_semantic_grad(self, m, lib, plan, lr_img, hr_img, captions, divisor, grads, l1_loss, on):
         """The route of a differentiable SemanticLoss: forward -> semantic encode (the SR crops stash what the encoder's backward
         needs, the HR crops do not) -> its vector-Jacobian product -> m2t_l1_loss (a MATERIALISED seed: the fused-L1 seed of the
         default route, m2t_l1_loss_deferred, does not apply here) -> m2t_add_output_grad(lambda_clip) -> m2t_backward.  HIP kernels
         only, one stream.  The semantic term is a per-sample SUM on every rank, so a SUM all-reduce of the gradients equals the
         gradient of the global-batch sum without rescaling (as the reference's DataParallel gather)."""
         sl = self.semantic_loss
+        first = grads is self.grads
         sr = torch.empty_like(hr_img)
         plan.gen += 1
         plan.trained = True
@@ -748,16 +665,8 @@ class TrainStep:
                                        float(m.rgb_range), 1, ws, st), "m2t_forward")
             tot, g, origins = sl._value_and_grad(sr, hr_img, captions)
             self._pixel_loss_call(lib, False, plan, hr_img, divisor, l1_loss, ws, st)
-            if self.lambda_ssim > 0.0:
-                self._ssim_loss_call(lib, plan, hr_img, grads is self.grads, ws, st)
-            if self.lambda_msssim > 0.0:
-                self._msssim_loss_call(lib, plan, hr_img, grads is self.grads, ws, st)
-            if self.lambda_fft > 0.0:
-                self._fft_loss_call(lib, plan, hr_img, grads is self.grads, ws, st)
-            if self.lambda_vif > 0.0:
-                self._vif_loss_call(lib, plan, hr_img, grads is self.grads, ws, st)
-            if self.lambda_perceptual > 0.0:
-                self._perceptual_loss_call(lib, plan, hr_img, grads is self.grads, ws, st)
+            for _, _, call in on:
+                call(plan, hr_img, first, ws, st)
             g = g.contiguous()
             arr = None
             if origins is not None:
@@ -765,10 +674,9 @@ class TrainStep:
             _lib.check(lib.m2t_add_output_grad(plan.handle, _lib.ptr(g), g.shape[2], g.shape[3], arr, self.lambda_clip,
                                                float(m.rgb_range), ws, st), "m2t_add_output_grad")
             self._backward_call(lib, plan, lr_img, grads, ws, st)
-            first = grads is self.grads
             self._accumulate_micro(lib, first, st)
         self._add_clip(tot * self.lambda_clip, first)
-        self.loss = self._total_loss(True)
+        self.loss = self._total_loss(on, True)
         return self.loss
 
     def all_reduce_grads(self):
@@ -903,3 +811,4 @@ class TrainStep:
         self.all_reduce_grads()
         self.optimizer_step()
         return loss
+

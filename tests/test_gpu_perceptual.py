@@ -486,3 +486,58 @@ def test_train_step_total_default_step_accumulation_and_checkpoint(lib, ts_tower
     # a small SR image is refused by the step itself, on the host
     with pytest.raises(M2TError, match="at least 16"):
         TrainStep(_model(scale, "bf16", 1), world_size=1, perceptual_loss=ts_tower, lambda_perceptual=LAM)._perceptual_workspace_for(torch.zeros(1, 3, 12, 48))
+
+
+def test_all_five_terms_accumulated_are_the_sequence_by_hand_bit_for_bit(lib, ts_tower):
+    """Every optional term on at once, bf16 x4, accum_steps = 2, micro-batches (1, 3, 48, 48): 192 x 192 SR pixels, the smallest size
+    that suits both the five MS-SSIM levels and the transform's 2^a 3^b rule.  The step issues pixel -> SSIM -> MS-SSIM -> FFT -> VIF ->
+    perceptual -> backward per micro-batch; the six values and the accumulated gradients are those of that sequence issued by hand on a
+    twin model with the cycle's divisors, summed in call order, and the total is the six values added in that order.  No tolerance."""
+    from m2trans_amd import _lib
+    from m2trans_amd.train_step import TrainStep
+    from tests.gpu_util import assert_flat_equal
+    from tests.test_gpu_msssim_loss import _model, _pair, _pixel
+    from tests.test_gpu_pixel_loss import _backward, _forward
+    scale, Hs, Ws = 4, 192, 192
+    lam = {"ssim": 0.1, "msssim": 0.16, "fft": 0.05, "vif": 0.1}
+    names = ["l1", "ssim", "msssim", "fft", "vif", "perceptual"]
+    x, hr = _pair(scale, "bf16", 2, 48, 48)
+    m_a, m_b = _model(scale, "bf16", 1), _model(scale, "bf16", 1)
+    ts = TrainStep(m_a, world_size=1, accum_steps=2, lambda_ssim=lam["ssim"], lambda_msssim=lam["msssim"], lambda_fft=lam["fft"],
+                   lambda_vif=lam["vif"], perceptual_loss=ts_tower, lambda_perceptual=LAM)
+    ts.forward_backward(x[0:1], hr[0:1])
+    loss = ts.forward_backward(x[1:2], hr[1:2])
+    torch.cuda.synchronize()
+    scratch = {n: torch.empty(getattr(lib, f"m2t_{n}_loss_scratch_bytes")(1, 3, Hs, Ws), dtype=torch.uint8, device="cuda") for n in lam}
+    # the global counts of a cycle of two micro-batches of one image: map entries, (image, channel) pairs, reals of the half spectrum, images
+    div = {"ssim": float(2 * 3 * (Hs - 10) * (Ws - 10)), "msssim": 6.0, "fft": float(2 * 3 * Hs * (Ws // 2 + 1) * 2), "vif": 2.0}
+    parts = []
+    for i in range(2):
+        cx, ch = x[i:i + 1].contiguous(), hr[i:i + 1].contiguous()
+        plan = m_b._plan_for(cx)
+        ws, st, h = _lib.ptr(plan.workspace), _lib.stream_ptr(), _lib.ptr(ch)
+        v = {n: torch.full((1,), float("nan"), device="cuda") for n in names}
+        grads = torch.full_like(m_b.flat_params, float("nan"))
+        _forward(lib, m_b, plan, cx)
+        assert _pixel(lib, plan, ch, v["l1"], divisor=hr.numel()) == 0
+        _lib.check(lib.m2t_ssim_loss(plan.handle, h, lam["ssim"], div["ssim"], 1.0, _lib.ptr(v["ssim"]), 0, _lib.ptr(scratch["ssim"]), ws, st),
+                   "m2t_ssim_loss")
+        _lib.check(lib.m2t_msssim_loss(plan.handle, h, lam["msssim"], div["msssim"], 1.0, _lib.ptr(v["msssim"]), 0, _lib.ptr(scratch["msssim"]),
+                                       ws, st), "m2t_msssim_loss")
+        _lib.check(lib.m2t_fft_loss(plan.handle, h, lam["fft"], div["fft"], 1.0, 0, _lib.ptr(v["fft"]), 0, _lib.ptr(scratch["fft"]), ws, st),
+                   "m2t_fft_loss")
+        _lib.check(lib.m2t_vif_loss(plan.handle, h, lam["vif"], div["vif"], 1.0, _lib.VIF_SIGMA_N_SQ, _lib.ptr(v["vif"]), 0,
+                                    _lib.ptr(scratch["vif"]), ws, st), "m2t_vif_loss")
+        assert _vgg(lib, plan, ts_tower, ch, v["perceptual"], divisor=2) == 0
+        _backward(lib, m_b, plan, cx, grads)
+        torch.cuda.synchronize()
+        parts.append((v, grads))
+    got = dict(zip(names, (ts.l1_loss, ts.ssim_loss, ts.msssim_loss, ts.fft_loss, ts.vif_loss, ts.perceptual_loss_value)))
+    for n in names:
+        want = parts[0][0][n] + parts[1][0][n]
+        assert bool(torch.isfinite(want).all()) and float(want) != 0.0, n
+        assert torch.equal(got[n], want), (n, float(got[n]), float(want))
+    assert torch.equal(loss, got["l1"] + got["ssim"] + got["msssim"] + got["fft"] + got["vif"] + got["perceptual"])
+    assert_flat_equal(m_a, ts.grads, parts[0][1] + parts[1][1], "accumulated pixel + SSIM + MS-SSIM + FFT + VIF + perceptual")
+    ts.optimizer_step()
+    assert ts.micro_count == 0
