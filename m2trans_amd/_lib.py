@@ -1,5 +1,5 @@
 """ctypes binding of libm2t.so (include/m2t.h, include/m2t_spectral.h, include/m2t_resize.h, include/m2t_msssim.h,
-include/m2t_vif.h, include/m2t_groups.h, include/m2t_perceptual.h).
+include/m2t_vif.h, include/m2t_groups.h, include/m2t_perceptual.h, include/m2t_rlutrans.h).
 
 The product path has NO fallback: if the HIP library is missing, or a call fails, this
 module raises.  Build it with ``python -m m2trans_amd.build`` (hipcc, gfx950).
@@ -162,6 +162,17 @@ VGG_CHANNELS = (64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 512, 512, 512)
 VGG_LEVEL = (0, 0, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4)            # 2 x 2 pools before the layer
 VGG_TAP_LAYERS = (0, 2, 4, 8, 12)                              # relu1_1, relu2_1, relu3_1, relu4_1, relu5_1
 
+# the eighth header, include/m2t_rlutrans.h (the training route of the TransBlock), bound on the same library; must list every symbol
+# that header declares.  The seven tables above stay as they are.
+RLUTRANS_SIGNATURES = {
+    "m2t_transblock_train_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
+    "m2t_transblock_train_workspace_offset": (C.c_size_t, [_i, _i, _i, _i]),
+    "m2t_transblock_forward_train": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "m2t_transblock_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+}
+TRANSBLOCK_NPARAMS = 22928                                     # TransBlock(n_feat=64, dim=64), state_dict order
+TRANSBLOCK_REGIONS = {"H1": 0, "AO": 1, "weights": 2, "X": 3, "LN1": 4, "R": 5, "QKV": 6, "X1": 7, "LN2": 8}
+
 _lib = None
 
 
@@ -185,7 +196,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) \
             + list(MSSSIM_SIGNATURES.items()) + list(VIF_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()) \
-            + list(PERCEPTUAL_SIGNATURES.items()):
+            + list(PERCEPTUAL_SIGNATURES.items()) + list(RLUTRANS_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -326,6 +326,17 @@ int launch_transpose_convert(int dt, const float* src, void* dst, int N, int K, 
 int launch_bicubic_resize_bwd(const float* gdst, float* gsrc, int NC, int Hin, int Win, int Hout, int Wout, hipStream_t st);
 int launch_add_output_grad(const float* pre, const float* g, float* gpre, int B, int Hp, int Wp, int gh, int gw, const M2TCropOrigins& org,
                            float scale, float R, hipStream_t st);
+// ---- k_rlutrans_bwd.hip (the TransBlock backward: include/m2t_rlutrans.h, host layer m2t_rlutrans.hip) ----------
+// gh1 [M][16] = [h1 > 0] * (gy [M][64] . w2 [64][16]), all in the storage type
+int launch_tb_fc2_dgrad_relu(int dt, const void* gy, const void* w2, const void* h1, void* gh1, long long M, hipStream_t st);
+// backward of the chunked attention (chunks of N / 16 tokens): qkv [M][192], ao / gao [M][64] -> gqkv [M][192]; stats: M * 8 * 3 floats of scratch
+int launch_tb_attn_bwd(int dt, const void* qkv, const void* ao, const void* gao, void* gqkv, float* stats, long long M, int N, hipStream_t st);
+// LayerNorm (C = 64, eps 1e-5) affine gradients, first stage: part [*nblk_out][128] = (sum g xhat | sum g) per block of rows
+int launch_tb_ln_affine(int dt, const void* x, const void* g, float* part, long long M, int* nblk_out, hipStream_t st);
+// second stage of all parameter gradients in one launch; the descriptors ride in the kernel arguments (no device table to upload)
+struct tb_reduce_desc { long long src, dst; int n, ns; };     // out[dst + e] = sum_{s < ns} arena[src + s n + e], e < n
+struct tb_reduce_table { tb_reduce_desc d[12]; };
+int launch_tb_param_reduce(const float* arena, float* out, const tb_reduce_table& tab, int ndesc, hipStream_t st);
 // ---- k_ssim_loss.hip (the 1 - SSIM loss term and its gradient: m2t_ssim_loss_tensor / m2t_ssim_loss) ----------
 // x [B][C][H][W] with image stride xs_img, channel stride xs_img / C, row stride xs_row; y contiguous; gx_add (or nullptr) has x's strides:
 // gx_add[q] += -scale * d sum(S) / dx[q] (through the clamp mask when clamp); loss_out = (accumulate ? loss_out : 0) + scale * sum(1 - S).

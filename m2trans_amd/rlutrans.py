@@ -1,8 +1,10 @@
 """Host mirror of the reference's ``util/rlutrans.py``: ``Mlp``, ``EffAttention``, ``TransBlock``
 with the reference's constructor arguments, parameter names, shapes and default initialisation, so a ``state_dict``
 moves between the two unchanged.  The reference never imports that file (dead code); the block is provided for
-completeness, forward only: ``TransBlock.forward`` runs as HIP kernels behind ``m2t_transblock_forward``
-(csrc/m2t_rlutrans.hip) and raises without the library or for a CPU tensor -- there is no eager fallback.
+completeness: ``TransBlock.forward`` runs as HIP kernels behind ``m2t_transblock_forward`` (csrc/m2t_rlutrans.hip) and raises
+without the library or for a CPU tensor -- there is no eager fallback.  With autograd on and anything requiring a gradient it
+takes the training route instead (``m2t_transblock_forward_train`` / ``m2t_transblock_backward``, include/m2t_rlutrans.h): the
+same ``y`` bit for bit, with gradients for ``x`` and the 12 parameter tensors.
 """
 from __future__ import annotations
 
@@ -40,6 +42,55 @@ class EffAttention(nn.Module):
         self.proj = nn.Linear(dim, dim)
 
 
+def _require_device(x: torch.Tensor) -> None:
+    if x.device.type != "cuda":
+        raise M2TError("TransBlock (MI355X build): needs a HIP device tensor; there is no CPU fallback")
+
+
+class _TransBlockFunction(torch.autograd.Function):
+    """The training route of ``TransBlock.forward``: ``m2t_transblock_forward_train`` on a workspace of this call's own, and
+    ``m2t_transblock_backward`` on it (include/m2t_rlutrans.h).  The node owns the workspace and the flat parameter vector, so a
+    second forward before the backward cannot overwrite either; the backward writes scratch only and may run twice."""
+
+    @staticmethod
+    def forward(ctx, x, flat, code, *params):
+        lib = _lib.load()
+        B, N, _ = x.shape
+        xc = x.detach().contiguous().float()
+        need = int(lib.m2t_transblock_train_workspace_bytes(B, N, code))
+        if need <= 0:
+            raise M2TError("TransBlock: no training workspace for this shape")
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        y = torch.empty_like(xc)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.m2t_transblock_forward_train(_lib.ptr(flat), _lib.ptr(xc), _lib.ptr(y), B, N, code, _lib.ptr(ws),
+                                                        _lib.stream_ptr()), "m2t_transblock_forward_train")
+        ctx.flat, ctx.ws, ctx.code, ctx.shape = flat, ws, code, (B, N)
+        ctx.param_shapes = [tuple(p.shape) for p in params]
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        lib = _lib.load()
+        B, N = ctx.shape
+        need_x, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[3:]
+        gyc = gy.detach().contiguous().float()
+        gx = torch.empty_like(gyc) if need_x else None
+        gparams = torch.empty(_lib.TRANSBLOCK_NPARAMS, dtype=torch.float32, device=gyc.device) if any(need_p) else None
+        with torch.cuda.device(gyc.device):
+            _lib.check(lib.m2t_transblock_backward(_lib.ptr(ctx.flat), _lib.ptr(gyc), _lib.ptr(gx), _lib.ptr(gparams), B, N, ctx.code,
+                                                   _lib.ptr(ctx.ws), _lib.stream_ptr()), "m2t_transblock_backward")
+        grads, off = [], 0
+        for shape, need in zip(ctx.param_shapes, need_p):
+            n = 1
+            for d in shape:
+                n *= d
+            grads.append(gparams[off:off + n].view(shape) if need else None)       # views of the one buffer
+            off += n
+        return (gx, None, None, *grads)
+
+
 class TransBlock(nn.Module):
     """util/rlutrans.py:70-87.  ``compute_dtype``: "fp32" (parity) or "bf16"."""
 
@@ -74,8 +125,7 @@ class TransBlock(nn.Module):
         return super().train(mode)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if x.device.type != "cuda":
-            raise M2TError("TransBlock (MI355X build): needs a HIP device tensor; there is no CPU fallback")
+        _require_device(x)
         if x.dim() != 3 or x.shape[2] != self.dim:
             raise M2TError("TransBlock: input must be [B, N, 64]")
         B, N, _ = x.shape
@@ -99,6 +149,13 @@ class TransBlock(nn.Module):
         flat = self._flat
         if flat.numel() != 22928:
             raise M2TError("TransBlock: unexpected parameter count")
+        if torch.is_grad_enabled():
+            params = [p for _, p in self.named_parameters()]
+            if x.requires_grad or any(p.requires_grad for p in params):
+                if [n for n, _ in self.named_parameters()] != list(self.state_dict().keys()):
+                    raise M2TError("TransBlock: parameters and state_dict disagree (the flat vector is in state_dict order)")
+                # the node owns this call's flat vector and workspace: `flat` is rebuilt on every call while autograd is on (above)
+                return _TransBlockFunction.apply(x, flat, code, *params)
         need = int(lib.m2t_transblock_workspace_bytes(B, N, code))
         if self._ws is None or self._ws.numel() < need or self._ws.device != x.device:
             self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
