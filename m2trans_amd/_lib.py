@@ -1,5 +1,5 @@
 """ctypes binding of libm2t.so (include/m2t.h, include/m2t_spectral.h, include/m2t_resize.h, include/m2t_msssim.h,
-include/m2t_vif.h, include/m2t_groups.h, include/m2t_perceptual.h, include/m2t_rlutrans.h).
+include/m2t_vif.h, include/m2t_groups.h, include/m2t_perceptual.h, include/m2t_rlutrans.h, include/m2t_infer.h).
 
 The product path has NO fallback: if the HIP library is missing, or a call fails, this
 module raises.  Build it with ``python -m m2trans_amd.build`` (hipcc, gfx950).
@@ -173,6 +173,14 @@ RLUTRANS_SIGNATURES = {
 TRANSBLOCK_NPARAMS = 22928                                     # TransBlock(n_feat=64, dim=64), state_dict order
 TRANSBLOCK_REGIONS = {"H1": 0, "AO": 1, "weights": 2, "X": 3, "LN1": 4, "R": 5, "QKV": 6, "X1": 7, "LN2": 8}
 
+# the ninth header, include/m2t_infer.h (the inference end: the eight dihedral views, their merge, the 8-bit export), bound on the
+# same library; must list every symbol that header declares.  The eight tables above stay as they are.
+INFER_SIGNATURES = {
+    "m2t_dihedral_pack": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "m2t_dihedral_merge": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "m2t_tensor_to_image_u8": (_i, [_vp, _i, _i, _i, _f, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -196,7 +204,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) \
             + list(MSSSIM_SIGNATURES.items()) + list(VIF_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()) \
-            + list(PERCEPTUAL_SIGNATURES.items()) + list(RLUTRANS_SIGNATURES.items()):
+            + list(PERCEPTUAL_SIGNATURES.items()) + list(RLUTRANS_SIGNATURES.items()) + list(INFER_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

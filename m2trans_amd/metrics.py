@@ -130,12 +130,16 @@ def vif_device(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0) -> tor
 
 
 def evaluate(model, pairs, scale: int, rgb_range: float = 1.0, with_gmsd: bool = False, with_fsim: bool = False,
-             with_vif: bool = False):
+             with_vif: bool = False, self_ensemble: bool = False):
     """The reference's test loop (test.py:77-122): `pairs` yields (lr, hr) device tensors [1,3,h,w] / [1,3,h*scale,w*scale];
     returns (avg_psnr, avg_ssim) -- with_gmsd: + avg_gmsd; with_fsim: + avg_fsim, in the order the reference prints them
     (PSNR, SSIM, FSIM, GMSD; test.py:118-122) -- rounded as the reference rounds them; with_vif: + the average
     pixel-domain VIF of (sr, hr) at data range `rgb_range`, after everything else, rounded like FSIM / GMSD (SR sides of at least
-    41).  One host synchronisation at the end (the reference synchronises per image)."""
+    41).  One host synchronisation at the end (the reference synchronises per image).  self_ensemble: `model` runs on the eight flips
+    and transposes of each lr and the outputs are averaged (infer.SelfEnsemble, the "+" row of a results table)."""
+    if self_ensemble:
+        from .infer import SelfEnsemble
+        model = SelfEnsemble(model)
     rows, grows, frows, vrows = [], [], [], []
     with torch.no_grad():
         for lr, hr in pairs:
