@@ -20,6 +20,7 @@
 #include "m2t_common.h"
 #include "m2t_kernels.h"
 #include "m2t_fft.h"
+#include "m2t_moment_tile.h"      // block_sum
 #include "../../include/m2t_spectral.h"
 #include <math.h>
 #include <map>
@@ -31,18 +32,7 @@ namespace {
 using namespace m2t_fft;
 constexpr int NT = 256;
 
-template <int N>
-__device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < N / 64; ++w) t += red[w];
-  return t;
-}
+using moment_tile::block_sum;
 
 // all stages of one transform on the sequences in a (b = the other ping-pong buffer); the caller has synchronised after filling a;
 // returns the buffer that holds the result, synchronised
@@ -103,19 +93,6 @@ __global__ __launch_bounds__(NT) void fft_rows_adj_kernel(Image im, int nseq, co
   __syncthreads();
   const float2* const z = fft_run(a, b, im.W, im.W, nseq, tw, 1);
   rowsadj_add(im, z, gcoef, nseq, blockIdx.x, threadIdx.x, NT);
-}
-
-// loss = (accumulate ? loss : 0) + (float)(scale * sum(partial[0 .. n))): one workgroup, fixed order
-__global__ __launch_bounds__(NT) void fft_loss_finish_kernel(const double* __restrict__ partial, long long n, double scale, int accumulate,
-                                                             float* __restrict__ loss) {
-  __shared__ double red[NT / 64];
-  double a = 0.0;
-  for (long long i = threadIdx.x; i < n; i += NT) a += partial[i];
-  const double t = block_sum<NT>(a, red);
-  if (threadIdx.x == 0) {
-    const float v = (float)(scale * t);
-    loss[0] = accumulate ? loss[0] + v : v;
-  }
 }
 
 // The N-th roots of unity e^{-2 pi i j / N}, j < N: fp64 on the host, rounded once to fp32, uploaded ONCE per (calling thread,
@@ -200,9 +177,7 @@ int launch_fft_loss(const float* x, const float* y, int B, int C, int H, int W, 
     fft_rows_adj_kernel<<<(unsigned)((im.npairs + nseq - 1) / nseq), NT, lds, st>>>(im, nseq, twW, spec, scale * s / (double)R);
     M2T_LAUNCH_CHECK();
   }
-  fft_loss_finish_kernel<<<1, NT, 0, st>>>(partial, planes * strips, scale * s, accumulate, loss_out);
-  M2T_LAUNCH_CHECK();
-  return 0;
+  return launch_loss_finish(partial, planes * strips, 1, 0, scale * s, accumulate, loss_out, st);
 }
 
 extern "C" size_t m2t_fft_loss_scratch_bytes(int B, int C, int H, int W) { return fft_loss_scratch_bytes(B, C, H, W); }

@@ -9,7 +9,7 @@
 //   pyramid   4 launches: level l+1 from level l, x and y together.  The levels are fp64 and UN-normalised (pooled clamp(pre), pooled
 //             hr): sums of at most 4^l fp32 numbers times 4^-l, exact, and summed in the order of the restatement -- bit for bit.
 //   phase 1   one launch per level: the tile of m2t_ssim_tile.h (level 0: the fp32 tile of the SSIM term, 32 x 32; levels 1 .. 4:
-//             fp64 inputs staged in LDS, 16 x 16 tile, 74 432 B, two workgroups per CU) reduces the map to one partial sum per tile.
+//             fp64 inputs staged in LDS, 16 x 16 tile, 74 464 B, two workgroups per CU) reduces the map to one partial sum per tile.
 //   finalize  one workgroup per (b,c) folds the partial sums of the five levels in a fixed order and writes the record: the
 //             coefficients c_l = w_l M / (v_l n_l), M, the alive flag, v_l; then one workgroup folds 1 - M_bc into the loss.
 //   phase 2   one launch per level, coarsest first: the tile recomputes the coefficient maps, filters them back, scales by c_l read
@@ -42,29 +42,19 @@ constexpr int MIN_SIDE = (WIN - 1) * 16 + 1;        // 161: level 4 still holds 
 // the record of one (b,c), in doubles
 constexpr int REC_COEF = 0, REC_M = 5, REC_ALIVE = 6, REC_V = 7, REC = 12;
 
-struct MsLayout {           // offsets in doubles
-  int h[LEVELS], w[LEVELS], ty[LEVELS], tx[LEVELS];
-  size_t rec, part[LEVELS], xp[LEVELS], yp[LEVELS], g[LEVELS], total;      // (index 0 of xp / yp / g is unused)
-};
+using MsLayout = LevelledLayout;        // a = the x pyramid, b = the y pyramid, g = the gradient of a level
 
 bool ms_layout(int B, int C, int H, int W, MsLayout& L) {
   if (B < 1 || C < 1 || (long long)B * C > 65535 || H < MIN_SIDE || W < MIN_SIDE) return false;
-  const size_t planes = (size_t)B * C;
-  size_t off = 0;
-  L.rec = off; off += planes * REC;
+  L.levels = LEVELS;
   for (int l = 0; l < LEVELS; ++l) {
     L.h[l] = l ? L.h[l - 1] / 2 + L.h[l - 1] % 2 : H;
     L.w[l] = l ? L.w[l - 1] / 2 + L.w[l - 1] % 2 : W;
     const int ts = l ? TileP::TS : Tile0::TS;
     L.ty[l] = (L.h[l] + ts - 1) / ts;
     L.tx[l] = (L.w[l] + ts - 1) / ts;
-    L.part[l] = off; off += planes * L.ty[l] * L.tx[l];
   }
-  L.xp[0] = L.yp[0] = L.g[0] = 0;
-  for (int l = 1; l < LEVELS; ++l) { L.xp[l] = off; off += planes * L.h[l] * L.w[l]; }
-  for (int l = 1; l < LEVELS; ++l) { L.yp[l] = off; off += planes * L.h[l] * L.w[l]; }
-  for (int l = 1; l < LEVELS; ++l) { L.g[l] = off; off += planes * L.h[l] * L.w[l]; }
-  L.total = off;
+  levelled_layout_fill(L, (size_t)B * C, REC, 1);
   return true;
 }
 
@@ -149,19 +139,6 @@ __global__ __launch_bounds__(256) void msssim_record_kernel(double* __restrict__
   if (per_channel_out) per_channel_out[bc] = M;
 }
 
-// loss = (accumulate ? loss : 0) + (float)(scale * sum_bc (1 - M_bc)): one workgroup, fixed order
-__global__ __launch_bounds__(256) void msssim_finish_kernel(const double* __restrict__ rec, int planes, double scale, int accumulate,
-                                                            float* __restrict__ loss) {
-  __shared__ double red[4];
-  double a = 0.0;
-  for (int i = threadIdx.x; i < planes; i += 256) a += 1.0 - rec[(long long)i * REC + REC_M];
-  const double t = block_sum<256>(a, red);
-  if (threadIdx.x == 0) {
-    const float v = (float)(scale * t);
-    loss[0] = accumulate ? loss[0] + v : v;
-  }
-}
-
 // Phase 2, one level: G_l(q) = c_l * d sum(map_l) / dx_l(q) + G_{l+1}(parent of q) / 4  (gpar = NULL on the coarsest level).
 // TOP = false: gout [B*C][H][W] = G_l.  TOP = true (level 0): gx[q] += (float)(gcoef * G_0(q)) where the clamp passes, x's strides.
 template <typename T, int KIND, bool TOP>
@@ -195,9 +172,6 @@ __global__ __launch_bounds__(T::NT) void msssim_grad_kernel(const typename T::In
   });
 }
 
-template <typename K>
-int ensure_lds(K kernel, size_t bytes) { return m2t_ensure_dynamic_lds((const void*)kernel, (int)bytes); }
-
 }  // namespace
 
 size_t msssim_loss_scratch_bytes(int B, int C, int H, int W) {
@@ -229,12 +203,12 @@ int launch_msssim_loss(const float* x, const float* y, int B, int C, int H, int 
   for (int l = 1; l < LEVELS; ++l) {
     const dim3 grid((L.w[l] + 31) / 32, (L.h[l] + 7) / 8, planes);
     if (l == 1)
-      msssim_pool_kernel<float><<<grid, dim3(32, 8), 0, st>>>(x, y, C, H, W, xs_img, xs_img / C, xs_row, R, clamp, s + L.xp[1], s + L.yp[1],
+      msssim_pool_kernel<float><<<grid, dim3(32, 8), 0, st>>>(x, y, C, H, W, xs_img, xs_img / C, xs_row, R, clamp, s + L.a[1], s + L.b[1],
                                                               L.h[1], L.w[1]);
     else
-      msssim_pool_kernel<double><<<grid, dim3(32, 8), 0, st>>>(s + L.xp[l - 1], s + L.yp[l - 1], C, L.h[l - 1], L.w[l - 1],
+      msssim_pool_kernel<double><<<grid, dim3(32, 8), 0, st>>>(s + L.a[l - 1], s + L.b[l - 1], C, L.h[l - 1], L.w[l - 1],
                                                                (long long)C * L.h[l - 1] * L.w[l - 1], (long long)L.h[l - 1] * L.w[l - 1],
-                                                               L.w[l - 1], Rd, 0, s + L.xp[l], s + L.yp[l], L.h[l], L.w[l]);
+                                                               L.w[l - 1], Rd, 0, s + L.a[l], s + L.b[l], L.h[l], L.w[l]);
     M2T_LAUNCH_CHECK();
   }
 
@@ -246,7 +220,7 @@ int launch_msssim_loss(const float* x, const float* y, int B, int C, int H, int 
     if (l == 0)
       v0<<<grid, Tile0::NT, Tile0::SMEM, st>>>(x, y, C, H, W, xs_img, xs_img / C, xs_row, R, clamp, win, s + L.part[0]);
     else
-      (*(l < LEVELS - 1 ? vp : v4))<<<grid, TileP::NT, TileP::SMEM, st>>>(s + L.xp[l], s + L.yp[l], C, L.h[l], L.w[l], C * hw, hw, L.w[l],
+      (*(l < LEVELS - 1 ? vp : v4))<<<grid, TileP::NT, TileP::SMEM, st>>>(s + L.a[l], s + L.b[l], C, L.h[l], L.w[l], C * hw, hw, L.w[l],
                                                                          Rd, 0, win, s + L.part[l]);
     M2T_LAUNCH_CHECK();
     f.part[l] = (long long)L.part[l];
@@ -255,8 +229,7 @@ int launch_msssim_loss(const float* x, const float* y, int B, int C, int H, int 
   }
   msssim_record_kernel<<<planes, 256, 0, st>>>(s, f, (long long)L.rec, per_channel_out);
   M2T_LAUNCH_CHECK();
-  msssim_finish_kernel<<<1, 256, 0, st>>>(s + L.rec, planes, scale, accumulate, loss_out);
-  M2T_LAUNCH_CHECK();
+  if (int rc = launch_loss_finish(s + L.rec + REC_M, planes, REC, 1, scale, accumulate, loss_out, st)) return rc;      // sum_bc (1 - M_bc)
   if (!gx_add) return 0;
 
   // phase 2: the gradient, coarsest level first
@@ -270,7 +243,7 @@ int launch_msssim_loss(const float* x, const float* y, int B, int C, int H, int 
     const dim3 grid(L.tx[l], L.ty[l], planes);
     const long long hw = (long long)L.h[l] * L.w[l];
     const bool top = l == LEVELS - 1;
-    (*(top ? g4 : gp))<<<grid, TileP::NT, TileP::SMEM, st>>>(s + L.xp[l], s + L.yp[l], C, L.h[l], L.w[l], C * hw, hw, L.w[l], Rd, 0, win,
+    (*(top ? g4 : gp))<<<grid, TileP::NT, TileP::SMEM, st>>>(s + L.a[l], s + L.b[l], C, L.h[l], L.w[l], C * hw, hw, L.w[l], Rd, 0, win,
                                                          s + L.rec, l, top ? nullptr : s + L.g[l + 1], top ? 0 : L.h[l + 1],
                                                          top ? 0 : L.w[l + 1], 0.0, nullptr, s + L.g[l]);
     M2T_LAUNCH_CHECK();
@@ -285,14 +258,7 @@ extern "C" size_t m2t_msssim_loss_scratch_bytes(int B, int C, int H, int W) { re
 
 extern "C" size_t m2t_msssim_loss_scratch_offset(int B, int C, int H, int W, int region, int level) {
   MsLayout L;
-  if (!ms_layout(B, C, H, W, L) || level < 0 || level >= LEVELS) return (size_t)-1;
-  if (region == 0) return sizeof(double) * L.rec;
-  if (region == 1) return sizeof(double) * L.part[level];
-  if (level < 1) return (size_t)-1;
-  if (region == 2) return sizeof(double) * L.xp[level];
-  if (region == 3) return sizeof(double) * L.yp[level];
-  if (region == 4) return sizeof(double) * L.g[level];
-  return (size_t)-1;
+  return ms_layout(B, C, H, W, L) ? levelled_layout_offset(L, region, level) : (size_t)-1;
 }
 
 extern "C" int m2t_msssim_loss_tensor(const float* x, const float* y, int B, int C, int H, int W, long long x_image_stride,

@@ -31,7 +31,7 @@ namespace {
 using ssim_tile::block_sum;
 using ssim_tile::WIN;
 using SsimTaps = ssim_tile::Taps;
-using SsimTile = ssim_tile::Tile<float, 32, 512>;      // (the tile machinery itself: m2t_ssim_tile.h, shared with k_msssim_loss.hip)
+using SsimTile = ssim_tile::Tile<float, 32, 512>;      // (m2t_ssim_tile.h, shared with k_msssim_loss.hip, on m2t_moment_tile.h)
 constexpr int TS = SsimTile::TS;       // output tile edge (pixels)
 constexpr int NT = SsimTile::NT;       // threads per workgroup
 // LDS: 151 392 B of the CU's 160 KB: one workgroup of 8 waves per CU.
@@ -61,12 +61,12 @@ __global__ __launch_bounds__(NT) void ssim_loss_tile_kernel(const float* __restr
   });
 }
 
-// loss = (accumulate ? loss : 0) + (float)(scale * sum(partial[0 .. n))): one workgroup, fixed order
-__global__ __launch_bounds__(256) void ssim_loss_finish_kernel(const double* __restrict__ partial, long long n, double scale, int accumulate,
-                                                               float* __restrict__ loss) {
+// loss = (accumulate ? loss : 0) + (float)(scale * sum_i v_i), v_i = p[i * stride] or 1 - p[i * stride]: one workgroup, fixed order
+__global__ __launch_bounds__(256) void loss_term_finish_kernel(const double* __restrict__ p, long long n, long long stride, int one_minus,
+                                                          double scale, int accumulate, float* __restrict__ loss) {
   __shared__ double red[4];
   double a = 0.0;
-  for (long long i = threadIdx.x; i < n; i += 256) a += partial[i];
+  for (long long i = threadIdx.x; i < n; i += 256) a += one_minus ? 1.0 - p[i * stride] : p[i * stride];
   const double t = block_sum<256>(a, red);
   if (threadIdx.x == 0) {
     const float v = (float)(scale * t);
@@ -99,9 +99,36 @@ int launch_ssim_loss(const float* x, const float* y, int B, int C, int H, int W,
   ssim_loss_tile_kernel<<<dim3(tx, ty, B * C), NT, SSIM_SMEM, st>>>(x, y, C, H, W, xs_img, xs_img / C, xs_row, R, clamp,
                                                                      -scale / (double)R, win, gx_add, (double*)scratch);
   M2T_LAUNCH_CHECK();
-  ssim_loss_finish_kernel<<<1, 256, 0, st>>>((const double*)scratch, (long long)B * C * tx * ty, scale, accumulate, loss_out);
+  return launch_loss_finish((const double*)scratch, (long long)B * C * tx * ty, 1, 0, scale, accumulate, loss_out, st);
+}
+
+int launch_loss_finish(const double* p, long long n, long long stride, int one_minus, double scale, int accumulate, float* loss_out,
+                       hipStream_t st) {
+  loss_term_finish_kernel<<<1, 256, 0, st>>>(p, n, stride, one_minus, scale, accumulate, loss_out);
   M2T_LAUNCH_CHECK();
   return 0;
+}
+
+void levelled_layout_fill(LevelledLayout& L, size_t items, int rec, int sums) {
+  size_t off = 0;
+  L.rec = off; off += items * rec;
+  for (int l = 0; l < L.levels; ++l) { L.part[l] = off; off += items * L.ty[l] * L.tx[l] * sums; }
+  for (size_t* plane : {L.a, L.b, L.g}) {
+    plane[0] = 0;
+    for (int l = 1; l < L.levels; ++l) { plane[l] = off; off += items * L.h[l] * L.w[l]; }
+  }
+  L.total = off;
+}
+
+size_t levelled_layout_offset(const LevelledLayout& L, int region, int level) {
+  if (level < 0 || level >= L.levels) return (size_t)-1;
+  if (region == 0) return sizeof(double) * L.rec;
+  if (region == 1) return sizeof(double) * L.part[level];
+  if (level < 1) return (size_t)-1;
+  if (region == 2) return sizeof(double) * L.a[level];
+  if (region == 3) return sizeof(double) * L.b[level];
+  if (region == 4) return sizeof(double) * L.g[level];
+  return (size_t)-1;
 }
 
 int loss_tensor_check(const char* who, const float* x, const float* y, const float* loss_out, const void* scratch, int C, int H, int W,

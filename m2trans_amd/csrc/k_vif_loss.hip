@@ -31,27 +31,18 @@ static_assert(TileN<17>::SMEM <= 160 * 1024 && 2 * TileN<9>::SMEM <= 160 * 1024 
 
 constexpr int REC_T = 0, REC_D = 1, REC_VIF = 2, REC_COEF = 3, REC = 4;      // the record of one image, in doubles
 
-struct VifLayout {          // offsets in doubles
-  int h[SCALES], w[SCALES], ty[SCALES], tx[SCALES];
-  size_t rec, part[SCALES], up[SCALES], vp[SCALES], g[SCALES], total;      // (index 0 of up / vp / g is unused)
-};
+using VifLayout = LevelledLayout;       // a = the u pyramid, b = the v pyramid, g = the gradient of a level
 
 bool vif_layout(int B, int C, int H, int W, VifLayout& L) {
   if (B < 1 || B > 65535 || (C != 1 && C != 3) || H < MIN_SIDE || W < MIN_SIDE) return false;
-  size_t off = 0;
-  L.rec = off; off += (size_t)B * REC;
+  L.levels = SCALES;
   for (int s = 0; s < SCALES; ++s) {
     L.h[s] = s ? decimated_side(L.h[s - 1], win_len(s)) : H;
     L.w[s] = s ? decimated_side(L.w[s - 1], win_len(s)) : W;
     L.ty[s] = (L.h[s] + TS - 1) / TS;
     L.tx[s] = (L.w[s] + TS - 1) / TS;
-    L.part[s] = off; off += (size_t)B * L.ty[s] * L.tx[s] * 2;
   }
-  L.up[0] = L.vp[0] = L.g[0] = 0;
-  for (int s = 1; s < SCALES; ++s) { L.up[s] = off; off += (size_t)B * L.h[s] * L.w[s]; }
-  for (int s = 1; s < SCALES; ++s) { L.vp[s] = off; off += (size_t)B * L.h[s] * L.w[s]; }
-  for (int s = 1; s < SCALES; ++s) { L.g[s] = off; off += (size_t)B * L.h[s] * L.w[s]; }
-  L.total = off;
+  levelled_layout_fill(L, (size_t)B, REC, 2);
   return true;
 }
 
@@ -113,19 +104,6 @@ __global__ __launch_bounds__(256) void vif_record_kernel(double* __restrict__ sc
   if (per_image_out) per_image_out[b] = vif;
 }
 
-// loss = (accumulate ? loss : 0) + (float)(scale * sum_b (1 - VIF_b)): one workgroup, fixed order
-__global__ __launch_bounds__(256) void vif_finish_kernel(const double* __restrict__ rec, int B, double scale, int accumulate,
-                                                         float* __restrict__ loss) {
-  __shared__ double red[4];
-  double a = 0.0;
-  for (int i = threadIdx.x; i < B; i += 256) a += 1.0 - rec[(long long)i * REC + REC_VIF];
-  const double t = block_sum<256>(a, red);
-  if (threadIdx.x == 0) {
-    const float v = (float)(scale * t);
-    loss[0] = accumulate ? loss[0] + v : v;
-  }
-}
-
 // Phase 2, one scale: G_s(p) = d sum(t_s) / du_s(p) + sum over parents of g g G_{s+1} (gpar = NULL on the coarsest scale; NP = N_{s+1}).
 // L0 = false: gout [B][H][W] = G_s.  L0 = true (scale 0): per channel, gx[p] += (float)(-coef_b * w_ch * k255 * G_0(p)) where the
 // clamp passes, x's strides.
@@ -165,16 +143,13 @@ __global__ __launch_bounds__(256) void vif_grad_kernel(Src src, long long img_x,
   });
 }
 
-template <typename K>
-int ensure_lds(K kernel, size_t bytes) { return m2t_ensure_dynamic_lds((const void*)kernel, (int)bytes); }
-
 struct Run {                // what every launch of one call shares
   Src src0; long long img_x, img_y; int B; double nn; double* s; const VifLayout* L; hipStream_t st; Taps win[SCALES];
 };
 
 Src plane_src(const Run& r, int s) {
   Src p = r.src0;
-  p.u = r.s + r.L->up[s]; p.v = r.s + r.L->vp[s]; p.row = r.L->w[s];
+  p.u = r.s + r.L->a[s]; p.v = r.s + r.L->b[s]; p.row = r.L->w[s];
   return p;
 }
 
@@ -186,7 +161,7 @@ int launch_pyramid(const Run& r) {          // level S from level S - 1
   if (int rc = ensure_lds(k, Pyr<N>::SMEM)) return rc;
   const dim3 grid((L.w[S] + PT - 1) / PT, (L.h[S] + PT - 1) / PT, r.B);
   k<<<grid, 256, Pyr<N>::SMEM, r.st>>>(S == 1 ? r.src0 : plane_src(r, S - 1), r.img_x, r.img_y, (long long)L.h[S - 1] * L.w[S - 1],
-                                      L.h[S - 1], L.w[S - 1], L.h[S], L.w[S], r.win[S], r.s + L.up[S], r.s + L.vp[S]);
+                                      L.h[S - 1], L.w[S - 1], L.h[S], L.w[S], r.win[S], r.s + L.a[S], r.s + L.b[S]);
   M2T_LAUNCH_CHECK();
   return 0;
 }
@@ -253,8 +228,7 @@ int launch_vif_loss(const float* x, const float* y, int B, int C, int H, int W, 
   for (int s = 0; s < SCALES; ++s) { f.part[s] = (long long)L.part[s]; f.nt[s] = L.ty[s] * L.tx[s]; }
   vif_record_kernel<<<B, 256, 0, st>>>(r.s, f, (long long)L.rec, scale, per_image_out);
   M2T_LAUNCH_CHECK();
-  vif_finish_kernel<<<1, 256, 0, st>>>(r.s + L.rec, B, scale, accumulate, loss_out);
-  M2T_LAUNCH_CHECK();
+  if (int rc = launch_loss_finish(r.s + L.rec + REC_VIF, B, REC, 1, scale, accumulate, loss_out, st)) return rc;      // sum_b (1 - VIF_b)
   if (!gx_add) return 0;
   if (int rc = launch_grad<3>(r, gx_add)) return rc;
   if (int rc = launch_grad<2>(r, gx_add)) return rc;
@@ -266,14 +240,7 @@ extern "C" size_t m2t_vif_loss_scratch_bytes(int B, int C, int H, int W) { retur
 
 extern "C" size_t m2t_vif_loss_scratch_offset(int B, int C, int H, int W, int region, int level) {
   VifLayout L;
-  if (!vif_layout(B, C, H, W, L) || level < 0 || level >= SCALES) return (size_t)-1;
-  if (region == 0) return sizeof(double) * L.rec;
-  if (region == 1) return sizeof(double) * L.part[level];
-  if (level < 1) return (size_t)-1;
-  if (region == 2) return sizeof(double) * L.up[level];
-  if (region == 3) return sizeof(double) * L.vp[level];
-  if (region == 4) return sizeof(double) * L.g[level];
-  return (size_t)-1;
+  return vif_layout(B, C, H, W, L) ? levelled_layout_offset(L, region, level) : (size_t)-1;
 }
 
 extern "C" int m2t_vif_loss_tensor(const float* x, const float* y, int B, int C, int H, int W, long long x_image_stride, int x_row_stride,

@@ -348,6 +348,23 @@ size_t ssim_loss_scratch_bytes(int B, int C, int H, int W);
 int loss_tensor_check(const char* who, const float* x, const float* y, const float* loss_out, const void* scratch, int C, int H, int W,
                       long long x_image_stride, int x_row_stride, float data_range, const char* shape_refusal,
                       const char* more_refusal = nullptr);
+// The last launch of every loss term, one workgroup, fixed order: loss_out = (accumulate ? loss_out : 0) + (float)(scale * sum_i v_i),
+// v_i = p[i * stride] for i < n, or 1 - p[i * stride] with one_minus.
+int launch_loss_finish(const double* p, long long n, long long stride, int one_minus, double scale, int accumulate, float* loss_out,
+                       hipStream_t st);
+template <typename K>
+int ensure_lds(K kernel, size_t bytes) { return m2t_ensure_dynamic_lds((const void*)kernel, (int)bytes); }
+// The scratch of a levelled term (MS-SSIM, VIF), offsets in doubles: the records | the tiles' partial sums per level | the planes
+// a, b (both pyramids) and g (the gradient) of levels 1 .. (index 0 of a / b / g is unused).  The term sets levels and h / w / ty / tx
+// by its own size rule; levelled_layout_fill(items, rec, sums) places `rec` doubles per item, `sums` per tile and item, and the planes.
+struct LevelledLayout {
+  static constexpr int MAX_LEVELS = 5;
+  int levels, h[MAX_LEVELS], w[MAX_LEVELS], ty[MAX_LEVELS], tx[MAX_LEVELS];
+  size_t rec, part[MAX_LEVELS], a[MAX_LEVELS], b[MAX_LEVELS], g[MAX_LEVELS], total;
+};
+void levelled_layout_fill(LevelledLayout& L, size_t items, int rec, int sums);
+// bytes into the scratch of region 0 (records), 1 (partial sums of `level`), 2 / 3 / 4 (planes a / b / g of `level` >= 1); (size_t)-1: none
+size_t levelled_layout_offset(const LevelledLayout& L, int region, int level);
 void ssim_loss_taps(double* g11);      // the 11 taps of the window (the fp32 taps torch builds, widened), also those of k_msssim_loss.hip
 int launch_ssim_loss(const float* x, const float* y, int B, int C, int H, int W, long long xs_img, int xs_row, float R, int clamp,
                      double scale, float* gx_add, float* loss_out, int accumulate, void* scratch, hipStream_t st);

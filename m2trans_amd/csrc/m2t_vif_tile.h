@@ -6,9 +6,9 @@
 //
 //   pyr_tile<N, L0>   one 16 x 16 tile of level s from level s - 1: the raw (2 * 15 + N)^2 input tile in LDS, the vertical pass on the
 //                     16 rows that survive the decimation only, the horizontal pass on the 16 surviving columns only.
-//   Tile<N, TS, NT>   one workgroup owns a TS x TS tile of a level.  maps() loads the TI x TI input tile (TI = TS + 2 (N - 1)), filters
-//                     u, v, uu, vv, uv vertically then horizontally on the TM x TM map entries whose windows touch the tile
-//                     (TM = TS + N - 1), leaves the three coefficient maps in LDS -- dA = dt/da (on u^2), dC = dt/dc (on u v),
+//   Tile<N, TS, NT>   the moment tile (m2t_moment_tile.h) of a level under its N-tap window: TI = TS + 2 (N - 1) input samples and
+//                     TM = TS + N - 1 map entries per edge.  maps() forms u and v in the load (level 0: clamp, luminance, 255 / R)
+//                     and leaves the three coefficient maps in LDS -- dA = dt/da (on u^2), dC = dt/dc (on u v),
 //                     dU = -2 mx dt/da - my dt/dc (on u); 0 outside the map and where the entry is not live -- and returns the tile's
 //                     sums of t and d over the map entries it owns.  grad() filters the three maps back and hands
 //                     d sum(t) / du_s(p) = 2 u(p) G^T[dA] + v(p) G^T[dC] + G^T[dU] of each of the tile's pixels to the epilogue.
@@ -23,11 +23,11 @@
 #define M2T_VIF_TILE_H
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include "m2t_ssim_tile.h"
+#include "m2t_ssim_tile.h"      // clamp_to; the moment tile comes with it
 
 namespace vif_tile {
 
-using ssim_tile::block_sum;
+using moment_tile::block_sum;
 
 constexpr int SCALES = 4;
 constexpr int MAXWIN = 17;
@@ -150,144 +150,57 @@ __device__ __forceinline__ double parent_gather(const double* __restrict__ gp, i
   return acc;
 }
 
-// ---- the moments, the map and its coefficient maps on one tile of one level ---------------------------------------------------------
+// ---- the moments, the map and its coefficient maps on one tile of one level: the moment tile with the luminance load, the
+// five-branch map (sums of t and d) and 2 u G^T[dA] + v G^T[dC] + G^T[dU] ----------------------------------------------------------
 template <int N_, int TS_, int NT_>
-struct Tile {
+struct Tile : moment_tile::Tile<N_, TS_, NT_, double> {
+  using Base = moment_tile::Tile<N_, TS_, NT_, double>;
   static constexpr int N = N_;
-  static constexpr int TS = TS_;
-  static constexpr int NT = NT_;
-  static constexpr int TM = TS + N - 1;
-  static constexpr int TI = TM + N - 1;
-  static constexpr size_t OFF_V = 0;                                             // 5 vertical passes; later (aliased) 3 transposed ones
-  static constexpr size_t OFF_D = OFF_V + sizeof(double) * 5 * TM * TI;          // dA | dC | dU
-  static constexpr size_t OFF_RED = OFF_D + sizeof(double) * 3 * TM * TM;
-  static constexpr size_t OFF_U = OFF_RED + sizeof(double) * (NT / 64 > 8 ? NT / 64 : 8);
-  static constexpr size_t OFF_W = OFF_U + sizeof(double) * TI * TI;
-  static constexpr size_t SMEM = OFF_W + sizeof(double) * TI * TI;
-  static_assert(SMEM <= 160 * 1024, "the tile does not fit the LDS of a CU");
-  static_assert(3 * TS * TM <= 5 * TM * TI, "the transposed vertical pass is aliased on V");
 
   // (y0, x0): the tile's first pixel; nn = sigma_n_sq.  SUM: sum_t / sum_d of the owned map entries are returned to every thread.
   template <bool L0, bool SUM>
   static __device__ __forceinline__ void maps(unsigned char* smem, const Src& src, int H, int W, int y0, int x0, double nn,
                                               const Taps& win, double& sum_t, double& sum_d) {
-    double* const V = (double*)(smem + OFF_V);
-    double* const D = (double*)(smem + OFF_D);
-    double* const red = (double*)(smem + OFF_RED);
-    double* const UR = (double*)(smem + OFF_U);
-    double* const WR = (double*)(smem + OFF_W);
-    const int tid = threadIdx.x;
-    const int Hm = H - N + 1, Wm = W - N + 1;
-    const int my0 = y0 - (N - 1), mx0 = x0 - (N - 1);
-
-    // 1. the input tile of u and v; 0 outside the level
-    for (int i = tid; i < TI * TI; i += NT) {
-      const int r = i / TI, cc = i - r * TI;
-      const int gy = my0 + r, gxx = mx0 + cc;
-      double u = 0.0, v = 0.0;
-      if (gy >= 0 && gy < H && gxx >= 0 && gxx < W) load_uv<L0>(src, gy, gxx, u, v);
-      UR[i] = u; WR[i] = v;
-    }
-    __syncthreads();
-
-    // 2. vertical pass of u, v, uu, vv, uv
-    for (int i = tid; i < TM * TI; i += NT) {
-      const int r = i / TI, cc = i - r * TI;
-      double a0 = 0, a1 = 0, a2 = 0, a3 = 0, a4 = 0;
-#pragma unroll
-      for (int t = 0; t < N; ++t) {
-        const double g = win.g[t], u = UR[(r + t) * TI + cc], v = WR[(r + t) * TI + cc];
-        a0 = fma(g, u, a0); a1 = fma(g, v, a1); a2 = fma(g, u * u, a2); a3 = fma(g, v * v, a3); a4 = fma(g, u * v, a4);
-      }
-      V[0 * TM * TI + i] = a0; V[1 * TM * TI + i] = a1; V[2 * TM * TI + i] = a2; V[3 * TM * TI + i] = a3; V[4 * TM * TI + i] = a4;
-    }
-    __syncthreads();
-
-    // 3. horizontal pass, the five-branch map and its coefficient maps
     const double iln10 = 0.43429448190325182765;        // 1 / ln 10
-    double acc_t = 0.0, acc_d = 0.0;
-    for (int i = tid; i < TM * TM; i += NT) {
-      const int r = i / TM, cc = i - r * TM;
-      double m[5];
-#pragma unroll
-      for (int q = 0; q < 5; ++q) {
-        double a = 0;
-#pragma unroll
-        for (int t = 0; t < N; ++t) a = fma(win.g[t], V[q * TM * TI + r * TI + cc + t], a);
-        m[q] = a;
-      }
-      const int py = my0 + r, px = mx0 + cc;
-      const bool valid = py >= 0 && py < Hm && px >= 0 && px < Wm;
-      const double mx = m[0], my = m[1];
-      const double a = fmax(m[2] - mx * mx, 0.0), b = fmax(m[3] - my * my, 0.0), c = m[4] - mx * my;
-      const bool live = valid && b >= EPS && a >= EPS && c >= 0.0;
-      double t = 0.0, dA = 0.0, dC = 0.0;
-      if (live) {
-        const double be = b + EPS;
-        const double g = c / be;
-        const double sv_raw = a - g * c;
-        const bool open = sv_raw > EPS;
-        const double z = (open ? sv_raw : EPS) + nn;
-        const double q = g * g * b;
-        t = log10(1.0 + q / z);
-        const double k = iln10 / (1.0 + q / z);
-        const double qz2 = q / (z * z);
-        dA = open ? -k * qz2 : 0.0;
-        dC = k * (2.0 * c * b / (be * be * z) + qz2 * (open ? 2.0 * c / be : 0.0));
-      }
-      D[0 * TM * TM + i] = dA;
-      D[1 * TM * TM + i] = dC;
-      D[2 * TM * TM + i] = -2.0 * mx * dA - my * dC;
-      if (valid && r >= N - 1 && cc >= N - 1) {          // the map entries this tile owns
-        acc_t += t;
-        if (b >= EPS) acc_d += log10(1.0 + b / nn);
-      }
-    }
-    if (SUM) {
-      sum_t = block_sum<NT>(acc_t, red);
-      sum_d = block_sum<NT>(acc_d, red);
-    }
-    __syncthreads();
+    double sum[2];
+    Base::template maps<SUM>(
+        smem, H, W, y0, x0, win, [&](int gy, int gxx, double& u, double& v) { load_uv<L0>(src, gy, gxx, u, v); },
+        [](double u) { return u; },
+        [=](const double(&m)[5], bool valid, bool owned, double(&d)[3], double(&acc)[2]) {
+          const double mx = m[0], my = m[1];
+          const double a = fmax(m[2] - mx * mx, 0.0), b = fmax(m[3] - my * my, 0.0), c = m[4] - mx * my;
+          const bool live = valid && b >= EPS && a >= EPS && c >= 0.0;
+          double t = 0.0, dA = 0.0, dC = 0.0;
+          if (live) {
+            const double be = b + EPS;
+            const double g = c / be;
+            const double sv_raw = a - g * c;
+            const bool open = sv_raw > EPS;
+            const double z = (open ? sv_raw : EPS) + nn;
+            const double q = g * g * b;
+            t = log10(1.0 + q / z);
+            const double k = iln10 / (1.0 + q / z);
+            const double qz2 = q / (z * z);
+            dA = open ? -k * qz2 : 0.0;
+            dC = k * (2.0 * c * b / (be * be * z) + qz2 * (open ? 2.0 * c / be : 0.0));
+          }
+          d[0] = dA;
+          d[1] = dC;
+          d[2] = -2.0 * mx * dA - my * dC;
+          if (owned) {
+            acc[0] += t;
+            if (b >= EPS) acc[1] += log10(1.0 + b / nn);
+          }
+        },
+        sum);
+    if (SUM) { sum_t = sum[0]; sum_d = sum[1]; }
   }
 
   // After maps(): epi(gy, gxx, d) for every pixel of the tile inside the level, d = d sum(t) / du_s(gy, gxx), this scale's own part.
   template <typename Epi>
   static __device__ __forceinline__ void grad(unsigned char* smem, int H, int W, int y0, int x0, const Taps& win, Epi epi) {
-    double* const T = (double*)(smem + OFF_V);
-    const double* const D = (const double*)(smem + OFF_D);
-    const double* const UR = (const double*)(smem + OFF_U);
-    const double* const WR = (const double*)(smem + OFF_W);
-    const int tid = threadIdx.x;
-
-    // 4. transposed filter, vertical: pixel row y0 + r collects the map rows y0 + r - t (local r + N - 1 - t)
-    for (int i = tid; i < TS * TM; i += NT) {
-      const int r = i / TM, cc = i - r * TM;
-      double a0 = 0, a1 = 0, a2 = 0;
-#pragma unroll
-      for (int t = 0; t < N; ++t) {
-        const double g = win.g[t];
-        const int j = (r + N - 1 - t) * TM + cc;
-        a0 = fma(g, D[j], a0); a1 = fma(g, D[TM * TM + j], a1); a2 = fma(g, D[2 * TM * TM + j], a2);
-      }
-      T[i] = a0; T[TS * TM + i] = a1; T[2 * TS * TM + i] = a2;
-    }
-    __syncthreads();
-
-    // 5. transposed filter, horizontal; the gradient of this tile's pixels
-    for (int i = tid; i < TS * TS; i += NT) {
-      const int r = i / TS, cc = i - r * TS;
-      const int gy = y0 + r, gxx = x0 + cc;
-      if (gy >= H || gxx >= W) continue;
-      double a0 = 0, a1 = 0, a2 = 0;
-#pragma unroll
-      for (int t = 0; t < N; ++t) {
-        const double g = win.g[t];
-        const int j = r * TM + cc + N - 1 - t;
-        a0 = fma(g, T[j], a0); a1 = fma(g, T[TS * TM + j], a1); a2 = fma(g, T[2 * TS * TM + j], a2);
-      }
-      const int p = (r + N - 1) * TI + cc + N - 1;
-      epi(gy, gxx, 2.0 * UR[p] * a0 + WR[p] * a1 + a2);
-    }
+    Base::grad(smem, H, W, y0, x0, win, [](double) { return true; },
+               [=](int gy, int gxx, double a0, double a1, double a2, double u, double v) { epi(gy, gxx, 2.0 * u * a0 + v * a1 + a2); });
   }
 };
 

@@ -1,4 +1,5 @@
-// A stand-in for <hip/hip_runtime.h> that lets tests/msssim_emulate.cpp run the device text of csrc/m2t_ssim_tile.h on the host:
+// A stand-in for <hip/hip_runtime.h> that lets tests/*_emulate.cpp run the device text of csrc/m2t_moment_tile.h and the tile headers
+// on it on the host (tests/emulate_hip/launch.h is the launch):
 // a workgroup is a set of real threads, __syncthreads a barrier, a wave shuffle an exchange through memory.  Test scaffolding only.
 #pragma once
 #include <barrier>

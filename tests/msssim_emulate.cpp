@@ -6,32 +6,13 @@
 // in:  int32 H, W, row stride, clamp; float R; double scale; float x[H][rs], y[H][W], gx[H][rs]
 // out: float loss; double M; float gx[H][rs] (after the add); double x pyramid levels 1 .. 4
 #include "m2t_ssim_tile.h"
+#include "launch.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 using namespace ssim_tile;
 using Tile0 = Tile<float, 32, 512>;
 using TileP = Tile<double, 16, 256>;
-static unsigned char* g_smem;
-// one set of nt threads per launch; the workgroups run one after the other on it
-template <class F> void launch(int gx, int gy, int nt, size_t smem, F body) {
-  gridDim.x = gx; gridDim.y = gy; gridDim.z = 1;
-  unsigned char* buf = (unsigned char*)aligned_alloc(64, (smem + 63) / 64 * 64);
-  g_smem = buf;
-  std::barrier<> bar(nt); g_bar = &bar;
-  std::vector<std::thread> th;
-  for (int t = 0; t < nt; ++t) th.emplace_back([&, t] {
-    threadIdx.x = t;
-    for (int b = 0; b < gx * gy; ++b) {
-      if (t == 0) { blockIdx.x = b % gx; blockIdx.y = b / gx; blockIdx.z = 0; }
-      bar.arrive_and_wait();
-      body();
-      bar.arrive_and_wait();
-    }
-  });
-  for (auto& t : th) t.join();
-  free(buf);
-}
 int main(int argc, char** argv) {
   FILE* f = fopen(argv[1], "rb");
   int hdr[4]; float R; double scale;

@@ -1,6 +1,7 @@
 """CPU tests (no GPU) of the SSIM loss term (TrainStep(lambda_ssim=...), m2t_ssim_loss / m2t_ssim_loss_tensor): the fp64
 restatement the GPU tests compare the kernels with (tests/ssim_loss_ref.py) -- its analytic gradient against torch autograd, its
-value against anchors and an independent scipy evaluation -- the C ABI table, TrainStep's argument validation and the checkpoint entry."""
+value against anchors and an independent scipy evaluation -- the C ABI table, TrainStep's argument validation, the checkpoint entry,
+and the kernel text run on host threads (tests/ssim_emulate.cpp) under the gate of the GPU test."""
 import ctypes as C
 import inspect
 import types
@@ -236,3 +237,62 @@ def test_checkpoint_entry_carries_lambda_ssim_and_round_trips(name, param, entry
                                   scheduler_last_epoch=0, set_lr=lambda lr: None)
     import_checkpoint(ck, _model(), plain)
     assert plain.lambda_ssim == 0.1
+
+
+# ------------------------------------------------------------------------------------------------------------- host emulation
+@pytest.fixture(scope="module")
+def emulator(tmp_path_factory):
+    import os
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cxx = next((c for c in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc", shutil.which("hipcc"), shutil.which("clang++"), shutil.which("g++"))
+                if c and os.path.exists(c)), None)
+    assert cxx, "no C++ compiler found"
+    exe = str(tmp_path_factory.mktemp("ssim") / "ssim_emulate")
+    subprocess.run([cxx, "-x", "c++", "-std=c++20", "-O2", "-ffp-contract=off", "-I", os.path.join(root, "tests", "emulate_hip"),
+                    "-I", os.path.join(root, "m2trans_amd", "csrc"), os.path.join(root, "tests", "ssim_emulate.cpp"), "-o", exe, "-lpthread"],
+                   check=True, capture_output=True)
+    return exe
+
+
+@pytest.mark.parametrize("H,W,rs,clamp,phases", [(11, 11, 11, 0, (0.3, 0.7)), (12, 43, 43, 0, (0.3, 1.9)), (40, 56, 64, 1, (0.3, 1.9))],
+                         ids=["one-entry", "two-row-map", "strided-clamp"])
+def test_kernel_text_emulated_on_the_host_meets_the_gpu_gate(emulator, tmp_path, H, W, rs, clamp, phases):
+    """csrc/m2t_ssim_tile.h on csrc/m2t_moment_tile.h -- the text the kernel runs, Tile<float, 32, 512> with the 1 - SSIM map, value then
+    gradient -- on host threads (tests/ssim_emulate.cpp), the inputs of the GPU test's cases: one map entry; a two-row map, ragged; two
+    tiles, clamp on, x in a NaN-filled buffer with a longer row.  The gradient within the gate of the GPU test's plan-free entry
+    (1e-6 |ref| + 1e-7 scale + 6e-8 |prefill + ref|), the value within fp32 rounding (1e-6), nothing written outside [H, W]."""
+    import struct
+    import subprocess
+    import numpy as np
+    x = (O.closed_form_image(1, 1, H, W, phase=phases[0]) * 1.6 - 0.3).contiguous()
+    y = O.closed_form_image(1, 1, H, W, phase=phases[1]).contiguous()
+    if clamp:
+        assert bool((x < 0).any()) and bool((x > 1).any())
+    scale = 0.37 / ((H - 10) * (W - 10))
+    want_loss, want = R.value_and_grad(x, y, 1.0, bool(clamp), scale)
+    assert float(want.abs().max()) > 0
+    g = torch.Generator().manual_seed(7)
+    prefill = (torch.randn(H, rs, generator=g) * float(want.abs().max())).float()
+    xb = torch.full((H, rs), float("nan"))
+    xb[:, :W] = x[0, 0]
+    with open(tmp_path / "in.bin", "wb") as f:
+        f.write(struct.pack("4i", H, W, rs, clamp) + struct.pack("f", 1.0) + struct.pack("d", scale))
+        f.write(xb.numpy().tobytes() + y[0, 0].numpy().tobytes() + prefill.numpy().tobytes())
+    subprocess.run([emulator, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], check=True, capture_output=True)
+    b = open(tmp_path / "out.bin", "rb").read()
+    assert len(b) == 4 + 4 * H * rs
+    loss = struct.unpack("f", b[:4])[0]
+    gx = torch.from_numpy(np.frombuffer(b[4:], dtype=np.float32).copy()).view(H, rs)
+    total = prefill[:, :W].double() + want[0, 0]
+    bound = 1e-6 * want[0, 0].abs() + 1e-7 * scale + 6e-8 * total.abs()
+    excess = float(((gx[:, :W].double() - total).abs() - bound).max())
+    print(f"emulated tile {H}x{W}: largest excess over the gate {excess:.3e} (max |ref| {float(want.abs().max()):.3e}, scale {scale:.3e}); "
+          f"value {loss:.9e} against {float(want_loss):.9e}")
+    assert excess <= 0.0, excess
+    if clamp:
+        outside = (x[0, 0] < 0) | (x[0, 0] > 1)
+        assert torch.equal(gx[:, :W][outside], prefill[:, :W][outside])                      # the clamp passes no gradient
+    assert torch.equal(gx[:, W:].view(torch.int32), prefill[:, W:].view(torch.int32))
+    assert abs(loss - float(want_loss)) <= 1e-6 * abs(float(want_loss))

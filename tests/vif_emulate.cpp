@@ -6,31 +6,12 @@
 // in:  int32 H, W, row stride, C, clamp; float R; double scale, sigma_n_sq; float x[C][H][rs], y[C][H][W], gx[C][H][rs]
 // out: float loss; double VIF; float gx[C][H][rs] (after the add); double u pyramid levels 1 .. 3
 #include "m2t_vif_tile.h"
+#include "launch.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 using namespace vif_tile;
 template <int N> using TileN = Tile<N, 16, 256>;
-static unsigned char* g_smem;
-// one set of nt threads per launch; the workgroups run one after the other on it
-template <class F> void launch(int gx, int gy, int nt, size_t smem, F body) {
-  gridDim.x = gx; gridDim.y = gy; gridDim.z = 1;
-  unsigned char* buf = (unsigned char*)aligned_alloc(64, (smem + 63) / 64 * 64);
-  g_smem = buf;
-  std::barrier<> bar(nt); g_bar = &bar;
-  std::vector<std::thread> th;
-  for (int t = 0; t < nt; ++t) th.emplace_back([&, t] {
-    threadIdx.x = t;
-    for (int b = 0; b < gx * gy; ++b) {
-      if (t == 0) { blockIdx.x = b % gx; blockIdx.y = b / gx; blockIdx.z = 0; }
-      bar.arrive_and_wait();
-      body();
-      bar.arrive_and_wait();
-    }
-  });
-  for (auto& t : th) t.join();
-  free(buf);
-}
 struct Ctx {
   int h[SCALES], w[SCALES]; Src src0; Taps win[SCALES]; double nn;
   std::vector<double> up[SCALES], vp[SCALES], g[SCALES], part[SCALES];
