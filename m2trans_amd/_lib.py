@@ -1,5 +1,5 @@
 """ctypes binding of libm2t.so (include/m2t.h, include/m2t_spectral.h, include/m2t_resize.h, include/m2t_msssim.h,
-include/m2t_vif.h, include/m2t_groups.h, include/m2t_perceptual.h, include/m2t_rlutrans.h, include/m2t_infer.h).
+include/m2t_vif.h, include/m2t_groups.h, include/m2t_perceptual.h, include/m2t_rlutrans.h, include/m2t_infer.h, include/m2t_train.h).
 
 The product path has NO fallback: if the HIP library is missing, or a call fails, this
 module raises.  Build it with ``python -m m2trans_amd.build`` (hipcc, gfx950).
@@ -181,6 +181,16 @@ INFER_SIGNATURES = {
     "m2t_tensor_to_image_u8": (_i, [_vp, _i, _i, _i, _f, _vp, _vp]),
 }
 
+# the tenth header, include/m2t_train.h (the training-loop end: the step meter and the preview strip), bound on the same library;
+# must list every symbol that header declares.  The nine tables above stay as they are.
+TRAIN_SIGNATURES = {
+    "m2t_meter_reset": (_i, [_vp, _vp, _i, _i, _vp]),
+    "m2t_meter_update": (_i, [C.POINTER(_vp), C.POINTER(_i), _i, _vp, _vp, _i, _ll, _vp]),
+    "m2t_preview_strip": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
+}
+METER_MAX_COLS = 16                                            # M2T_METER_MAX_COLS
+METER_RECORD = ("sum", "count", "nonfinite", "min", "max", "last")     # the first six of the 8 doubles of a column
+
 _lib = None
 
 
@@ -204,7 +214,8 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) \
             + list(MSSSIM_SIGNATURES.items()) + list(VIF_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()) \
-            + list(PERCEPTUAL_SIGNATURES.items()) + list(RLUTRANS_SIGNATURES.items()) + list(INFER_SIGNATURES.items()):
+            + list(PERCEPTUAL_SIGNATURES.items()) + list(RLUTRANS_SIGNATURES.items()) + list(INFER_SIGNATURES.items()) \
+            + list(TRAIN_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args
