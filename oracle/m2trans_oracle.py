@@ -321,7 +321,10 @@ def cftm(x: Tensor, p: Params, prefix: str, cap=None, ck: str = "", emu: "_Emu |
     the packed 3x3 weight and the block output.  ``extra_residual``: the `res + x` of M2Trans.forward:70, which the
     HIP path folds into the LAST block's conv epilogue (one rounding instead of two)."""
     e = emu
-    x1, x2, x3, x4 = torch.chunk(instance_norm(x), 4, dim=1)
+    xn = instance_norm(x)
+    if cap is not None:
+        cap[ck + "xn"] = xn                                # the normalised block input (a graph tensor: tests/bwd_stage_ref.py)
+    x1, x2, x3, x4 = torch.chunk(xn, 4, dim=1)
     d1 = _r(x1, e, ck + "d1")
     x1 = _r(tblock(d1, p, prefix + "attn1.", cap, ck + "qkv1", e) + d1, e, ck + "xc", slice(0, 16))
     x2 = _r((x2 + x1) / 2.0, e)
@@ -369,6 +372,8 @@ def tail(x: Tensor, p: Params, scale: int, cap=None, emu: "_Emu | None" = None) 
     if scale == 4:
         t1 = F.pixel_shuffle(F.conv2d(x, _rw(p["tail.0.weight"], e), p["tail.0.bias"]), 2)
         a1, d1 = _gelu_stored(t1, e, "t1act", "t1der")
+        if cap is not None:
+            cap["t1pre"] = t1                              # the first expansion's pre-activation (a graph tensor)
         t2 = F.pixel_shuffle(F.conv2d(a1, _rw(p["tail.3.weight"], e), p["tail.3.bias"]), 2)
         a2, d2 = _gelu_stored(t2, e, "t2act", "t2der")
         if cap is not None:

@@ -213,9 +213,13 @@ def explicit(inp: dict, points=frozenset(), dtype=torch.float64) -> dict:
         d4 = dkh.view(N, KWIN, KWIN, C)
         drel_h = d4[..., :half].sum((0, 2))
         drel_w = d4[..., half:].sum((0, 1))
-    dk = r(overlap_add(r(dkh, "win"), B, h, w), "halo")
-    dv = r(overlap_add(r(dvw, "win"), B, h, w), "halo")
-    return {"out": from_windows(out, B, h, w), "dq": from_windows(dq, B, h, w), "dk": dk, "dv": dv, "drel_h": drel_h, "drel_w": drel_w}
+    dkh, dvw = r(dkh, "win"), r(dvw, "win")
+    dk = r(overlap_add(dkh, B, h, w), "halo")
+    dv = r(overlap_add(dvw, B, h, w), "halo")
+    # dk_win | dv_win: the windows' dK^ | dV rows [N, 100, C] as the kernel holds them BEFORE the overlap-add (tests/bwd_stage_ref.py:
+    # the fused projection data gradient multiplies these rows by Wqkv per window); not in TENSORS, so errors() leaves them alone
+    return {"out": from_windows(out, B, h, w), "dq": from_windows(dq, B, h, w), "dk": dk, "dv": dv, "drel_h": drel_h, "drel_w": drel_w,
+            "dk_win": dkh, "dv_win": dvw}
 
 
 # ------------------------------------------------------------------------------------------------ comparator

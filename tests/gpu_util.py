@@ -160,6 +160,35 @@ def hip_forward_trace(plan, scale, n_blocks, B, H, W):
     return t
 
 
+def _ws_p64(plan, name, B, H, W):
+    """A chunk-planar 64-channel workspace tensor ([4][B*H*W][16], csrc/m2t_common.h) -> float32 NCHW on the CPU."""
+    t = plan.ws_tensor(name).view(4, B, H, W, 16).permute(1, 2, 3, 0, 4).reshape(B, H, W, 64)
+    return nhwc_to_nchw(t.float()).cpu()
+
+
+def hip_backward_trace(plan, scale, n_blocks, B, H, W):
+    """The gradient tensors that the last (synchronised) m2t_backward / m2t_backward_ex left intact in the workspace, as float32 NCHW
+    on the CPU under the tap names of tests/bwd_stage_ref.py (H, W = padded LR size).  Only taps that no later launch of the same pass
+    overwrites are returned -- which ones those are, and which line overwrites the others, is listed in that module's docstring; they
+    hold for n_blocks <= 2 (a third block would reuse buffer set 0 and gA / gB).  The input gradient is the caller's (lr.grad)."""
+    if n_blocks not in (1, 2):
+        raise ValueError("hip_backward_trace: the taps are intact for n_blocks <= 2 only")
+    t = {"gpre": plan.ws_tensor("gpre", dtype=torch.float32).view(B, 3, H * scale, W * scale).cpu().clone()}
+    if scale == 4:
+        t["g_t1pre"] = nhwc_to_nchw(plan.ws_tensor("g_t1pre").view(B, 2 * H, 2 * W, 64).float()).cpu()
+    t["gT"] = _ws_p64(plan, "gT", B, H, W)
+    if n_blocks == 2:
+        t["gB"] = _ws_p64(plan, "gB", B, H, W)
+    for b in range(n_blocks):
+        sfx = "b" if b & 1 else ""                         # buffer set b & 1 (csrc/m2t_api.hip: hd.gqkv[b & 1])
+        for i in range(4):
+            h, w = H >> BR_L[i], W >> BR_L[i]
+            t[f"b{b}.gqkv{i+1}"] = nhwc_to_nchw(plan.ws_tensor(f"gqkv{i}{sfx}").view(B, h, w, 3 * BR_C[i]).float()).cpu()
+    t["gn"] = _ws_p64(plan, "gn", B, H, W)                  # block 0's (the last one written)
+    t["gres"] = _ws_p64(plan, "gxc", B, H, W)               # after block 0's InstanceNorm backward: g(res), the head's cotangent
+    return t
+
+
 def smooth_hr(B, size, seed, device="cpu", noise=0.026):
     """Band-limited synthetic 'tissue' in [0,1] (the bf16 quality tests): a low-frequency Fourier field, a few soft-edged
     blobs and mild speckle that the x4 box down-sampling removes only partly -- an image family on which the network
