@@ -1,5 +1,6 @@
 """ctypes binding of libm2t.so (include/m2t.h, include/m2t_spectral.h, include/m2t_resize.h, include/m2t_msssim.h,
-include/m2t_vif.h, include/m2t_groups.h, include/m2t_perceptual.h, include/m2t_rlutrans.h, include/m2t_infer.h, include/m2t_train.h).
+include/m2t_vif.h, include/m2t_groups.h, include/m2t_perceptual.h, include/m2t_rlutrans.h, include/m2t_infer.h, include/m2t_train.h,
+include/m2t_tiles.h).
 
 The product path has NO fallback: if the HIP library is missing, or a call fails, this
 module raises.  Build it with ``python -m m2trans_amd.build`` (hipcc, gfx950).
@@ -191,6 +192,14 @@ TRAIN_SIGNATURES = {
 METER_MAX_COLS = 16                                            # M2T_METER_MAX_COLS
 METER_RECORD = ("sum", "count", "nonfinite", "min", "max", "last")     # the first six of the 8 doubles of a column
 
+# the eleventh header, include/m2t_tiles.h (tiled inference: the tile grid, the gather of a chunk of tiles, the feather blend), bound on
+# the same library; must list every symbol that header declares.  The ten tables above stay as they are.
+TILES_SIGNATURES = {
+    "m2t_tile_grid": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "m2t_tile_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "m2t_tile_blend": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -215,7 +224,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) \
             + list(MSSSIM_SIGNATURES.items()) + list(VIF_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()) \
             + list(PERCEPTUAL_SIGNATURES.items()) + list(RLUTRANS_SIGNATURES.items()) + list(INFER_SIGNATURES.items()) \
-            + list(TRAIN_SIGNATURES.items()):
+            + list(TRAIN_SIGNATURES.items()) + list(TILES_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -4,7 +4,11 @@ results table: the model runs on the eight flips and transposes of the input as 
 averaged) and the per-pixel spread of the eight outputs (test-time-augmentation uncertainty).
 
     python -m m2trans_amd.infer --config configs/M2Trans_x4_test.yml --model_path model.pt --input LR_DIR --output SR_DIR \\
-        [--self_ensemble] [--spread SPREAD_DIR] [--compute_dtype bf16|fp32]
+        [--self_ensemble] [--spread SPREAD_DIR] [--compute_dtype bf16|fp32] [--tile T [--tile_overlap V] [--tile_batch N] [--seam SEAM_DIR]]
+
+Tiled inference (include/m2t_tiles.h, k_tiles.hip; restated by tests/tiles_ref.py): the model runs on overlapping tiles of the
+training size, in batches, and the outputs are feather-blended; its InstanceNorms then see the statistics they were trained with, and
+every image of every size runs on one plan.
 
 View k = 4 t + 2 v + h of a plane x[H,W]: y[i,j] = x[v ? H-1-i : i, h ? W-1-j : j], transposed when t = 1; the inverse un-transposes
 first and applies the same flips; mean, spread and the 8-bit rounding are defined in include/m2t_infer.h and restated in torch by
@@ -70,13 +74,13 @@ def dihedral_merge(a: torch.Tensor, b: torch.Tensor, with_spread: bool = False):
     return (mean, spread) if with_spread else mean
 
 
-def _model_output(out, n: int, h: int, w: int, scale=None):
+def _model_output(out, n: int, h: int, w: int, scale=None, who: str = "self_ensemble"):
     """The scale of a model output [n,3,s h,s w] (contiguous float32 on the device), checked against `scale` when given."""
     if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.dim() != 4 or not out.is_cuda or not out.is_contiguous():
-        raise M2TError("self_ensemble: the model must return a contiguous float32 [n,3,s*h,s*w] device tensor")
+        raise M2TError(f"{who}: the model must return a contiguous float32 [n,3,s*h,s*w] device tensor")
     s = out.shape[2] // h if scale is None else scale
     if s < 1 or tuple(out.shape) != (n, 3, s * h, s * w):
-        raise M2TError(f"self_ensemble: model output {tuple(out.shape)} for an input [{n},3,{h},{w}]"
+        raise M2TError(f"{who}: model output {tuple(out.shape)} for an input [{n},3,{h},{w}]"
                        + (" is not that input times an integer scale" if scale is None else f" does not match the scale {scale} of the first call"))
     return s
 
@@ -117,6 +121,119 @@ class SelfEnsemble(nn.Module):
 
     def forward(self, lr):
         return self_ensemble(self.model, lr, self.with_spread)
+
+
+# ------------------------------------------------------------------------------------------------------------------------- tiles
+def tile_grid(L: int, T: int, overlap: int):
+    """The tile grid of one axis (m2t_tile_grid, the one definition the kernels use too): LR length L, tile size T, overlap with
+    0 <= 2 overlap <= T -> (tile_len, origins).  L <= T: one tile of length L; otherwise tiles of length T every T - overlap, the last
+    one shifted back to end at L.  Host only."""
+    import ctypes as C
+    lib = _lib.load()
+    n, t = C.c_int(0), C.c_int(0)
+    _lib.check(lib.m2t_tile_grid(int(L), int(T), int(overlap), C.byref(n), C.byref(t), None), "m2t_tile_grid")
+    origins = (C.c_int * n.value)()
+    _lib.check(lib.m2t_tile_grid(int(L), int(T), int(overlap), C.byref(n), C.byref(t), origins), "m2t_tile_grid")
+    return t.value, list(origins)
+
+
+def tile_gather(x: torch.Tensor, tile: int, overlap: int, first: int = 0, count=None) -> torch.Tensor:
+    """float32 [B,C,H,W] on the device -> the tiles first .. first + count - 1 of the global order (tile (b, ky, kx) has the index
+    (b ny + ky) nx + kx) as one batch [count,C,th,tw]; count = None: all from `first` on.  One launch."""
+    _check_planes("tile_gather", x, "x")
+    if x.requires_grad:
+        raise M2TError("tile_gather: inference only, x must not require a gradient")
+    B, C, H, W = x.shape
+    (th, oy), (tw, ox) = tile_grid(H, tile, overlap), tile_grid(W, tile, overlap)
+    total = B * len(oy) * len(ox)
+    count = total - int(first) if count is None else int(count)
+    if first < 0 or count < 1 or first + count > total:
+        raise M2TError(f"tile_gather: tiles {first} .. {first + count - 1} asked for, the batch has {total}")
+    dst = torch.empty(count, C, th, tw, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().m2t_tile_gather(_lib.ptr(x), B, C, H, W, int(tile), int(overlap), int(first), count, _lib.ptr(dst),
+                                               _lib.stream_ptr()), "m2t_tile_gather")
+    return dst
+
+
+def tile_blend(tiles: torch.Tensor, B: int, H: int, W: int, tile: int, overlap: int, scale: int, with_seam: bool = False):
+    """The outputs of all tiles of a batch [B,C,H,W], tiles [B ny nx,C,s th,s tw] in the global order -> the feather-blended image
+    [B,C,s H,s W], or (image, seam) with the weighted standard deviation of the covering tiles per element (0 where one tile covers).
+    The weights, the order of the sums and the single-cover copy are defined in include/m2t_tiles.h.  One launch."""
+    _check_planes("tile_blend", tiles, "tiles")
+    if tiles.requires_grad:
+        raise M2TError("tile_blend: inference only, the tiles must not require a gradient")
+    (th, oy), (tw, ox) = tile_grid(H, tile, overlap), tile_grid(W, tile, overlap)
+    s, C = int(scale), tiles.shape[1]
+    want = (int(B) * len(oy) * len(ox), C, s * th, s * tw)
+    if B < 1 or tuple(tiles.shape) != want:
+        raise M2TError(f"tile_blend: tiles {tuple(tiles.shape)}, expected {want} for B = {B}, an image {H} x {W}, tile {tile}, overlap "
+                       f"{overlap} and scale {scale}")
+    out = torch.empty(B, C, s * H, s * W, dtype=torch.float32, device=tiles.device)
+    seam = torch.empty_like(out) if with_seam else None
+    with torch.cuda.device(tiles.device):
+        _lib.check(_lib.load().m2t_tile_blend(_lib.ptr(tiles), int(B), C, int(H), int(W), int(tile), int(overlap), s, _lib.ptr(out),
+                                              _lib.ptr(seam), _lib.stream_ptr()), "m2t_tile_blend")
+    return (out, seam) if with_seam else out
+
+
+def tiled(model, lr: torch.Tensor, tile: int = 128, overlap: int = 16, tile_batch: int = 16, with_seam: bool = False):
+    """`model` (any callable under the contract of `self_ensemble`) on overlapping tiles of lr [B,3,H,W], the outputs feather-blended
+    -> sr [B,3,s H,s W], or (sr, seam).  The tiles are gathered and run in chunks of `tile_batch` (every chunk on the one
+    (tile_batch, tile, tile) plan, the last chunk on a smaller one), each chunk's output is copied into one SR-tile buffer, one blend
+    follows.  When both axes have a single tile the result is `model(lr)` itself and nothing else is launched (a seam is then all 0).
+    A model that returns several tensors of the SR shape, as `SelfEnsemble(model, with_spread=True)` does, has each of them blended
+    with the same weights: (sr, spread) or (sr, spread, seam), the seam being that of the first.  A tile that is not a multiple of 32
+    makes the model reflect-pad every tile."""
+    _check_planes("tiled", lr, "lr")
+    if lr.shape[1] != 3:
+        raise M2TError(f"tiled: lr must be [B,3,H,W], got {tuple(lr.shape)}")
+    if lr.requires_grad:
+        raise M2TError("tiled: inference only, lr must not require a gradient")
+    tile_batch = int(tile_batch)
+    if tile_batch < 1:
+        raise M2TError(f"tiled: tile_batch must be positive, got {tile_batch}")
+    B, _, H, W = lr.shape
+    (th, oy), (tw, ox) = tile_grid(H, tile, overlap), tile_grid(W, tile, overlap)
+    total = B * len(oy) * len(ox)
+    with torch.no_grad():
+        if len(oy) == 1 and len(ox) == 1:
+            out = model(lr)
+            if not with_seam:
+                return out
+            outs = tuple(out) if isinstance(out, (tuple, list)) else (out,)
+            _model_output(outs[0], B, H, W, who="tiled")
+            return outs + (torch.zeros_like(outs[0]),)
+        s, bufs = None, None
+        for first in range(0, total, tile_batch):
+            count = min(tile_batch, total - first)
+            out = model(tile_gather(lr, tile, overlap, first, count))
+            outs = tuple(out) if isinstance(out, (tuple, list)) else (out,)
+            for o in outs:
+                s = _model_output(o, count, th, tw, scale=s, who="tiled")
+            if bufs is None:
+                bufs = [torch.empty(total, 3, s * th, s * tw, dtype=torch.float32, device=lr.device) for _ in outs]
+            elif len(bufs) != len(outs):
+                raise M2TError(f"tiled: the model returned {len(outs)} tensors for one chunk and {len(bufs)} for the first")
+            for buf, o in zip(bufs, outs):
+                buf[first:first + count].copy_(o)
+        res = [tile_blend(buf, B, H, W, tile, overlap, s) for buf in bufs[1:]]
+        head = tile_blend(bufs[0], B, H, W, tile, overlap, s, with_seam)
+        if with_seam:
+            return (head[0], *res, head[1])
+        return (head, *res) if res else head
+
+
+class Tiled(nn.Module):
+    """`tiled` as a module around `model`: drops into `metrics.evaluate`, and composes with `SelfEnsemble`:
+    `Tiled(SelfEnsemble(model))` ensembles per tile (square tiles: ONE model call on 8 * tile_batch views per chunk)."""
+
+    def __init__(self, model, tile: int = 128, overlap: int = 16, tile_batch: int = 16, with_seam: bool = False):
+        super().__init__()
+        self.model, self.tile, self.overlap, self.tile_batch, self.with_seam = model, int(tile), int(overlap), int(tile_batch), bool(with_seam)
+
+    def forward(self, lr):
+        return tiled(self.model, lr, self.tile, self.overlap, self.tile_batch, self.with_seam)
 
 
 def to_uint8(sr: torch.Tensor, rgb_range: float = 1.0) -> torch.Tensor:
@@ -173,14 +290,26 @@ def load_image(path, device, rgb_range: float = 1.0) -> torch.Tensor:
     return lr if rgb_range == 1.0 else lr * float(rgb_range)
 
 
+def _save_map(grey_of: torch.Tensor, path) -> float:
+    """A per-element map [1,3,H,W] as an 8-bit grey PNG: its maximum over RGB, scaled by the image's own maximum; returns that maximum."""
+    grey = grey_of[0].amax(dim=0, keepdim=True)
+    top = float(grey.max())
+    save_image(grey, path, top if top > 0.0 else 1.0)
+    return top
+
+
 def upscale_folder(model, in_dir, out_dir, self_ensemble: bool = False, spread_dir=None, rgb_range: float = 1.0,
-                   device="cuda") -> list:
+                   device="cuda", tile=None, overlap: int = 16, tile_batch=None, seam_dir=None) -> list:
     """Every image of `in_dir` through `model` into `out_dir` as `<name>.png`; returns the written names.  self_ensemble: through
     the eight views.  spread_dir (needs self_ensemble): the per-pixel maximum over RGB of the spread as an 8-bit grey PNG of the same
     name, scaled by the image's own maximum (grey 255 = that maximum); `spread.json` beside the files maps each name to that maximum,
-    in units of `rgb_range`."""
+    in units of `rgb_range`.  tile: through `tiled` with that tile size, `overlap` and `tile_batch` (None: 16, or 2 with
+    self_ensemble, which makes 16 views per call); the ensemble is then taken per tile.  seam_dir (needs tile): the seam map, written
+    like the spread, with `seam.json`."""
     if spread_dir is not None and not self_ensemble:
         raise M2TError("upscale_folder: spread_dir needs self_ensemble=True (the spread is that of the eight views)")
+    if seam_dir is not None and tile is None:
+        raise M2TError("upscale_folder: seam_dir needs a tile size (the seam is the disagreement of overlapping tiles)")
     names = image_names(in_dir)
     if not names:
         raise M2TError(f"upscale_folder: no image file in {in_dir}")
@@ -188,25 +317,37 @@ def upscale_folder(model, in_dir, out_dir, self_ensemble: bool = False, spread_d
     os.makedirs(str(out_dir), exist_ok=True)
     if spread_dir is not None:
         os.makedirs(str(spread_dir), exist_ok=True)
+    if seam_dir is not None:
+        os.makedirs(str(seam_dir), exist_ok=True)
     run = _self_ensemble                                        # (the keyword of this function shadows the module's function)
-    factors = {}
+    factors, seams = {}, {}
     with torch.no_grad():
         for name, out in zip(names, outs):
             lr = load_image(os.path.join(str(in_dir), name), device, rgb_range)
-            if not self_ensemble:
+            if tile is not None:
+                inner = SelfEnsemble(model, with_spread=spread_dir is not None) if self_ensemble else model
+                got = tiled(inner, lr, tile, overlap, (2 if self_ensemble else 16) if tile_batch is None else tile_batch,
+                            with_seam=seam_dir is not None)
+                got = list(got) if isinstance(got, (tuple, list)) else [got]
+                sr = got.pop(0)
+                if spread_dir is not None:
+                    factors[out] = _save_map(got.pop(0), os.path.join(str(spread_dir), out))
+                if seam_dir is not None:
+                    seams[out] = _save_map(got.pop(0), os.path.join(str(seam_dir), out))
+            elif not self_ensemble:
                 sr = model(lr)
             elif spread_dir is None:
                 sr = run(model, lr)
             else:
                 sr, spread = run(model, lr, with_spread=True)
-                grey = spread[0].amax(dim=0, keepdim=True)
-                top = float(grey.max())
-                save_image(grey, os.path.join(str(spread_dir), out), top if top > 0.0 else 1.0)
-                factors[out] = top
+                factors[out] = _save_map(spread, os.path.join(str(spread_dir), out))
             save_image(sr, os.path.join(str(out_dir), out), rgb_range)
     if spread_dir is not None:
         with open(os.path.join(str(spread_dir), "spread.json"), "w") as f:
             json.dump({"rgb_range": float(rgb_range), "max_spread": factors}, f, indent=1, sort_keys=True)
+    if seam_dir is not None:
+        with open(os.path.join(str(seam_dir), "seam.json"), "w") as f:
+            json.dump({"rgb_range": float(rgb_range), "max_seam": seams}, f, indent=1, sort_keys=True)
     return outs
 
 
@@ -221,9 +362,24 @@ def parse_args(argv=None):
     ap.add_argument("--self_ensemble", action="store_true", help="average over the eight flips and transposes of the input")
     ap.add_argument("--spread", default=None, metavar="DIR", help="with --self_ensemble: write the per-pixel spread of the eight outputs there")
     ap.add_argument("--compute_dtype", choices=("bf16", "fp32"), default=None, help="overrides the yaml's compute_dtype")
+    ap.add_argument("--tile", type=int, default=None, metavar="T", help="run the model on overlapping T x T tiles (the training LR patch "
+                    "size, a multiple of 32) and feather-blend the outputs")
+    ap.add_argument("--tile_overlap", type=int, default=16, metavar="V", help="with --tile: LR pixels two neighbouring tiles share, 0 <= 2 V <= T")
+    ap.add_argument("--tile_batch", type=int, default=None, metavar="N", help="with --tile: tiles per model call (default 16, or 2 with "
+                    "--self_ensemble: 16 views per call)")
+    ap.add_argument("--seam", default=None, metavar="DIR", help="with --tile: write the per-pixel disagreement of overlapping tiles there")
     args = ap.parse_args(argv)
     if args.spread is not None and not args.self_ensemble:
         ap.error("--spread needs --self_ensemble")
+    if args.seam is not None and args.tile is None:
+        ap.error("--seam needs --tile")
+    if args.tile is not None:
+        if args.tile < 1 or args.tile_overlap < 0 or 2 * args.tile_overlap > args.tile:
+            ap.error("--tile must be positive and --tile_overlap must satisfy 0 <= 2 V <= T")
+        if args.tile_batch is None:
+            args.tile_batch = 2 if args.self_ensemble else 16
+        elif args.tile_batch < 1:
+            ap.error("--tile_batch must be positive")
     return args
 
 
@@ -259,8 +415,10 @@ def main(argv=None) -> int:
     load_weights(model, torch.load(args.model_path, map_location="cpu", weights_only=False))
     model.eval()
     outs = upscale_folder(model, args.input, args.output, self_ensemble=args.self_ensemble, spread_dir=args.spread,
-                          rgb_range=float(getattr(ns, "rgb_range", 1.0)))
-    print(json.dumps({"images": len(outs), "output": args.output, "self_ensemble": bool(args.self_ensemble), "spread": args.spread}))
+                          rgb_range=float(getattr(ns, "rgb_range", 1.0)), tile=args.tile, overlap=args.tile_overlap,
+                          tile_batch=args.tile_batch, seam_dir=args.seam)
+    print(json.dumps({"images": len(outs), "output": args.output, "self_ensemble": bool(args.self_ensemble), "spread": args.spread,
+                      "tile": args.tile, "tile_overlap": args.tile_overlap if args.tile is not None else None, "seam": args.seam}))
     return 0
 
 
