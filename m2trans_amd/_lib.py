@@ -1,6 +1,6 @@
 """ctypes binding of libm2t.so (include/m2t.h, include/m2t_spectral.h, include/m2t_resize.h, include/m2t_msssim.h,
 include/m2t_vif.h, include/m2t_groups.h, include/m2t_perceptual.h, include/m2t_rlutrans.h, include/m2t_infer.h, include/m2t_train.h,
-include/m2t_tiles.h).
+include/m2t_tiles.h, include/m2t_gmsd.h).
 
 The product path has NO fallback: if the HIP library is missing, or a call fails, this
 module raises.  Build it with ``python -m m2trans_amd.build`` (hipcc, gfx950).
@@ -200,6 +200,15 @@ TILES_SIGNATURES = {
     "m2t_tile_blend": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 
+# the twelfth header, include/m2t_gmsd.h (the GMSD loss term), bound on the same library; must list every symbol that header
+# declares.  The eleven tables above stay as they are.
+GMSD_SIGNATURES = {
+    "m2t_gmsd_loss_scratch_bytes": (C.c_size_t, [_i, _i, _i, _i]),
+    "m2t_gmsd_loss_tensor": (_i, [_vp, _vp, _i, _i, _i, _i, _ll, _i, _f, _i, _d, _vp, _vp, _vp, _i, _vp, _vp]),
+    "m2t_gmsd_loss": (_i, [_vp, _vp, _f, _d, _f, _vp, _i, _vp, _vp, _vp]),
+}
+GMSD_MIN_SIDE = 2                                              # min(H, W) >= 2: one 2 x 2 cell
+
 _lib = None
 
 
@@ -224,7 +233,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) \
             + list(MSSSIM_SIGNATURES.items()) + list(VIF_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()) \
             + list(PERCEPTUAL_SIGNATURES.items()) + list(RLUTRANS_SIGNATURES.items()) + list(INFER_SIGNATURES.items()) \
-            + list(TRAIN_SIGNATURES.items()) + list(TILES_SIGNATURES.items()):
+            + list(TRAIN_SIGNATURES.items()) + list(TILES_SIGNATURES.items()) + list(GMSD_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -26,8 +26,8 @@ above, key for key.
 With a pixel loss other than L1 (TrainStep(pixel_loss=...)) the dict carries ``m2t_loss`` = {"pixel_loss": name, "param": eps /
 beta / None}; ``import_checkpoint`` sets the TrainStep's loss from it and leaves the loss alone when the file has no such entry.
 An L1 run writes no entry: its dict is the one above.  Every optional loss term of the step that is on (train_step.LOSS_TERMS, in
-that order, then the perceptual term) adds its weight to the entry as ``"lambda_<term>"`` (and the entry then exists for an L1 pixel
-term too); ``import_checkpoint`` calls the step's ``set_lambda_<term>`` with it.  ``"lambda_fft"`` is followed by ``"fft_norm"``;
+that order, then the perceptual term, then train_step.MORE_LOSS_TERMS: ``"lambda_gmsd"`` comes last) adds its weight to the entry
+as ``"lambda_<term>"`` (and the entry then exists for an L1 pixel term too); ``import_checkpoint`` calls the step's ``set_lambda_<term>`` with it.  ``"lambda_fft"`` is followed by ``"fft_norm"``;
 ``"lambda_perceptual"`` by ``"perceptual_criterion"``, ``"perceptual_weights"`` and ``"perceptual_resize"`` (never the VGG19 weights;
 ``import_checkpoint`` sets them on the step's ``perceptual_loss`` object first).  The keys of a term whose weight is 0 are absent, so
 with every weight 0 the dict is the one described above, byte for byte.
@@ -106,9 +106,10 @@ def _optim_options(train_step) -> dict:
 def _pixel_loss(train_step):
     """The ``m2t_loss`` entry of a step object, or None for L1 with every optional term off (and for an object that knows no pixel
     losses)."""
-    from .train_step import LOSS_TERMS, resolve_pixel_loss
+    from .train_step import LOSS_TERMS, MORE_LOSS_TERMS, resolve_pixel_loss
     _, canon, value = resolve_pixel_loss(getattr(train_step, "pixel_loss", "l1"), getattr(train_step, "pixel_loss_param", None))
-    names = [t.name for t in LOSS_TERMS] + ["perceptual"]
+    # (the entry keeps the order it always had -- LOSS_TERMS, then the perceptual term -- and the later rows follow it)
+    names = [t.name for t in LOSS_TERMS] + ["perceptual"] + [t.name for t in MORE_LOSS_TERMS]
     lam = {n: float(getattr(train_step, f"lambda_{n}", 0.0) or 0.0) for n in names}
     if canon == "l1" and not any(lam.values()):
         return None
@@ -242,8 +243,8 @@ def import_checkpoint(ckpt: dict, model, train_step=None) -> int:
         else:
             from .train_step import resolve_pixel_loss
             _, train_step.pixel_loss, train_step.pixel_loss_param = resolve_pixel_loss(ml["pixel_loss"], ml.get("param"))
-        from .train_step import LOSS_TERMS, resolve_fft_norm, resolve_lambda
-        for t in LOSS_TERMS:
+        from .train_step import LOSS_TERMS, MORE_LOSS_TERMS, resolve_fft_norm, resolve_lambda
+        for t in LOSS_TERMS + MORE_LOSS_TERMS:       # (a file without a term's key leaves that weight alone: 0 on a fresh step)
             key = f"lambda_{t.name}"
             if key not in ml:
                 continue

@@ -10,6 +10,7 @@
 #include "../../include/m2t_spectral.h"
 #include "../../include/m2t_msssim.h"
 #include "../../include/m2t_vif.h"
+#include "../../include/m2t_gmsd.h"
 #include "../../include/m2t_perceptual.h"
 
 static thread_local std::string g_err;
@@ -771,6 +772,18 @@ extern "C" int m2t_vif_loss(m2t_plan* p, const float* hr, float weight, double d
   CK(loss_entry_seed(__func__, p, p->B <= 65535, "batch too large (B <= 65535)", workspace, &s));
   return launch_vif_loss(s.x, hr, p->B, 3, p->Hs, p->Ws, s.xs_img, s.xs_row, rgb_range, sigma_n_sq, 1, (double)weight / divisor, s.gx,
                          loss_out, nullptr, accumulate ? 1 : 0, scratch, (hipStream_t)stream);
+}
+
+// weight * mean GMSD (k_gmsd_loss.hip; include/m2t_gmsd.h)
+extern "C" int m2t_gmsd_loss(m2t_plan* p, const float* hr, float weight, double divisor, float rgb_range, float* loss_out, int accumulate,
+                             void* scratch, void* workspace, void* stream) {
+  CK(loss_entry_args(__func__, !p || !hr || !loss_out || !scratch || !workspace, rgb_range, divisor, weight));
+  if (!gmsd_loss_size_supported(p->Hs, p->Ws))
+    return m2t_set_error_at(M2T_ERR_ARG, __func__, "the SR height and width must be at least 2 (one 2 x 2 cell)");
+  LossSeed s;
+  CK(loss_entry_seed(__func__, p, p->B <= 65535, "batch too large (B <= 65535)", workspace, &s));
+  return launch_gmsd_loss(s.x, hr, p->B, 3, p->Hs, p->Ws, s.xs_img, s.xs_row, rgb_range, 1, (double)weight / divisor, s.gx, loss_out,
+                          nullptr, accumulate ? 1 : 0, scratch, (hipStream_t)stream);
 }
 
 // weight * sum_k w_k mean(rho(F_k(sr) - F_k(hr))) on VGG19 features (k_vgg.hip, m2t_vgg.hip; include/m2t_perceptual.h).  The tower's

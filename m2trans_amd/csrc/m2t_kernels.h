@@ -386,6 +386,14 @@ size_t vif_loss_scratch_bytes(int B, int C, int H, int W);
 int launch_vif_loss(const float* x, const float* y, int B, int C, int H, int W, long long xs_img, int xs_row, float R, double sigma_n_sq,
                     int clamp, double scale, float* gx_add, float* loss_out, double* per_image_out, int accumulate, void* scratch,
                     hipStream_t st);
+// ---- k_gmsd_loss.hip (the GMSD loss term and its gradient: m2t_gmsd_loss_tensor / m2t_gmsd_loss) ----------
+// The strides, gx_add, loss_out and accumulate of launch_ssim_loss; C is 1 or 3 (one pooled luminance plane per image);
+// loss_out = (accumulate ? loss_out : 0) + scale * sum_b GMSD_b; per_image_out (or nullptr): double [B] = GMSD_b.
+// scratch: gmsd_loss_scratch_bytes(B, C, H, W) bytes (0 when H or W < 2, C is not 1 or 3, or B is outside 1 .. 65535).
+bool gmsd_loss_size_supported(int H, int W);
+size_t gmsd_loss_scratch_bytes(int B, int C, int H, int W);
+int launch_gmsd_loss(const float* x, const float* y, int B, int C, int H, int W, long long xs_img, int xs_row, float R, int clamp,
+                     double scale, float* gx_add, float* loss_out, double* per_image_out, int accumulate, void* scratch, hipStream_t st);
 // ---- k_fft_loss.hip (the L1 loss on the coefficients of a 2-D real FFT and its gradient: m2t_fft_loss_tensor / m2t_fft_loss) ----------
 // x [B][C][H][W] with image stride xs_img, channel stride xs_img / C, row stride xs_row; y contiguous; gx_add (or nullptr) has x's strides:
 // gx_add[q] += scale * d sum(|Re D| + |Im D|) / dx[q] (through the clamp mask when clamp); loss_out = (accumulate ? loss_out : 0) + scale * sum.

@@ -30,8 +30,8 @@ L1_Charbonnier_loss): the kind only selects the per-pixel function inside the ke
 m2t_pixel_loss_deferred), so every kind runs the schedule of the L1 step -- the seed fused into the x4 tail backward, accumulation,
 the overlapped exchange and the optimizer options included.
 
-Optional loss terms (all off by default; LOSS_TERMS below is their table, and its order -- SSIM, MS-SSIM, FFT, VIF, then the
-perceptual term -- is the order of the calls).  Every term that is on takes the MATERIALISED seed: the immediate pixel loss, then one
+Optional loss terms (all off by default; LOSS_TERMS and MORE_LOSS_TERMS below are their table, and its order -- SSIM, MS-SSIM, FFT,
+VIF, GMSD, then the perceptual term -- is the order of the calls).  Every term that is on takes the MATERIALISED seed: the immediate pixel loss, then one
 ``m2t_<term>_loss`` call per term that adds its gradient into the seed, then the backward pass; the seed fused into the x4 tail
 backward does not apply.  An SR size a term does not take is refused on the host before anything is launched.  With a weight of 0
 nothing is allocated for the term and the step issues the calls it issued before.  Value and gradient are HIP, fp64 inside unless
@@ -52,6 +52,10 @@ said otherwise.
   the piq.vif_p form on the luminance of ``clamp(sr, 0, rgb_range)`` and ``hr``, four scales, windows of 17 / 9 / 5 / 3 taps,
   sigma_n_sq = 2 (m2t_vif_loss of include/m2t_vif.h; SR height and width >= 41).  VIF exceeds 1 for a contrast-enhanced output, so
   the term may be negative; it is not clipped.
+* ``lambda_gmsd`` (piq ships GMSDLoss next to those classes; the reference reports GMSD for every model, test.py:95-122):
+  ``lambda_gmsd * mean GMSD`` per image, the deviation of the gradient-magnitude similarity map of the pooled luminance of
+  ``clamp(sr, 0, rgb_range)`` and ``hr`` (m2t_gmsd_loss of include/m2t_gmsd.h; SR height and width >= 2).  A distortion: there is no
+  "1 -".  Exactly 0 gradient where the pooled output is locally flat (torch's autograd gives NaN there).
 * ``lambda_perceptual``, ``perceptual_loss=`` (PerceptualLoss of the reference's losses.py:222-270): ``lambda_perceptual * sum_k w_k
   mean(crit(F_k(sr) - F_k(hr)))`` on VGG19 features; the tower, its weights, its workspace, the criterion and the tap weights are
   those of the losses.PerceptualLoss object (m2t_vgg_loss of include/m2t_perceptual.h, bf16 compute; SR height and width >= 16).
@@ -133,6 +137,7 @@ resolve_lambda_ssim = functools.partial(resolve_lambda, "ssim")
 resolve_lambda_msssim = functools.partial(resolve_lambda, "msssim")
 resolve_lambda_fft = functools.partial(resolve_lambda, "fft")
 resolve_lambda_vif = functools.partial(resolve_lambda, "vif")
+resolve_lambda_gmsd = functools.partial(resolve_lambda, "gmsd")
 resolve_lambda_perceptual = functools.partial(resolve_lambda, "perceptual")
 
 
@@ -152,6 +157,11 @@ def msssim_size_supported(h: int, w: int) -> bool:
 def vif_size_supported(h: int, w: int) -> bool:
     """The sizes the information-fidelity term takes (the rule of include/m2t_vif.h, decided on the host): min(H, W) >= 41."""
     return min(int(h), int(w)) >= _lib.VIF_MIN_SIDE
+
+
+def gmsd_size_supported(h: int, w: int) -> bool:
+    """The sizes the GMSD term takes (the rule of include/m2t_gmsd.h, decided on the host): min(H, W) >= 2."""
+    return min(int(h), int(w)) >= _lib.GMSD_MIN_SIDE
 
 
 def perceptual_size_supported(h: int, w: int) -> bool:
@@ -187,7 +197,7 @@ class LossTerm(NamedTuple):
     extra: Callable         # (step) -> the term's own arguments of m2t_<n>_loss, between rgb_range and the value
 
 
-# in call order: pixel -> these (each if on) -> the perceptual term (if on) -> backward
+# in call order: pixel -> these (each if on) -> MORE_LOSS_TERMS (each if on) -> the perceptual term (if on) -> backward
 LOSS_TERMS = (
     LossTerm("ssim", lambda hs, ws: min(hs, ws) >= 11,
              "the SR image {Hs}x{Ws} is smaller than the 11 x 11 SSIM window",
@@ -211,7 +221,16 @@ LOSS_TERMS = (
              lambda b, hs, ws: b,                                     # images (luminance: not times 3)
              lambda step: (_lib.VIF_SIGMA_N_SQ,)),
 )
-_TERM = {t.name: t for t in LOSS_TERMS}
+# the rows that came after LOSS_TERMS was pinned to its four names: the same type, iterated directly behind it everywhere
+MORE_LOSS_TERMS = (
+    LossTerm("gmsd", gmsd_size_supported,
+             "the SR image {Hs}x{Ws} is smaller than one 2 x 2 cell (height and width must be at least 2)",
+             "no scratch size for a batch of {B} SR images {Hs}x{Ws} (B <= 65535)",
+             lambda b, hs, ws: b,                                     # images (luminance: not times 3)
+             lambda step: ()),
+)
+ALL_LOSS_TERMS = LOSS_TERMS + MORE_LOSS_TERMS
+_TERM = {t.name: t for t in ALL_LOSS_TERMS}
 
 
 _STREAMS: dict = {}
@@ -238,9 +257,9 @@ class TrainStep:
     # The state of the optional terms, off: what __init__ starts from and what a step object assembled without __init__ has.  A term
     # of LOSS_TERMS has its weight, its device [1] value and its per-shape scratch cache (None: the dict is made per object, on first
     # use or by the setter); the perceptual term keeps its value next to the PerceptualLoss object, whose workspace is its own.
-    lambda_ssim = lambda_msssim = lambda_fft = lambda_vif = lambda_perceptual = 0.0
-    ssim_loss = msssim_loss = fft_loss = vif_loss = perceptual_loss_value = None
-    _ssim_scratch = _msssim_scratch = _fft_scratch = _vif_scratch = None
+    lambda_ssim = lambda_msssim = lambda_fft = lambda_vif = lambda_gmsd = lambda_perceptual = 0.0
+    ssim_loss = msssim_loss = fft_loss = vif_loss = gmsd_loss = perceptual_loss_value = None
+    _ssim_scratch = _msssim_scratch = _fft_scratch = _vif_scratch = _gmsd_scratch = None
     fft_norm = "backward"
     perceptual_loss = None
     groups = None
@@ -255,7 +274,7 @@ class TrainStep:
                  track_grad_norm: bool = False, pixel_loss: str = "l1", pixel_loss_param: Optional[float] = None,
                  lambda_ssim: float = 0.0, lambda_fft: float = 0.0, fft_norm: str = "backward",
                  lambda_msssim: float = 0.0, lambda_vif: float = 0.0, param_groups=None, perceptual_loss=None,
-                 lambda_perceptual: float = 0.0):
+                 lambda_perceptual: float = 0.0, lambda_gmsd: float = 0.0):
         self.model = model
         # parameter groups / frozen tensors (param_groups.py): resolved against the model's names here, on the host, fixed for the
         # life of this object.  None (the default): nothing is allocated and the step issues the calls it always issued
@@ -267,6 +286,7 @@ class TrainStep:
         self.set_lambda_msssim(lambda_msssim)
         self.set_lambda_fft(lambda_fft, fft_norm)
         self.set_lambda_vif(lambda_vif)
+        self.set_lambda_gmsd(lambda_gmsd)
         self.perceptual_loss = perceptual_loss
         self.set_lambda_perceptual(lambda_perceptual)
         # gradient accumulation: one optimizer step consumes accum_steps equal micro-batches (forward_backward calls); the
@@ -422,6 +442,11 @@ class TrainStep:
         (checkpoint.import_checkpoint calls this); refused in the middle of an accumulation cycle."""
         self._set_lambda(_TERM["vif"], value)
 
+    def set_lambda_gmsd(self, value):
+        """Weight of the GMSD term (0 = off).  Takes effect with the next forward_backward (checkpoint.import_checkpoint calls
+        this); refused in the middle of an accumulation cycle."""
+        self._set_lambda(_TERM["gmsd"], value)
+
     def _scratch_for(self, term: LossTerm, lib, hr_img):
         """The scratch of one term for this (micro-)batch shape, allocated once; an SR size the term does not take is refused here,
         on the host, before anything is launched."""
@@ -509,11 +534,11 @@ class TrainStep:
 
     # -- what forward_backward iterates ------------------------------------------------------------------------------------
     def _terms_on(self, lib) -> list:
-        """The optional terms that are on, in call order -- the rows of LOSS_TERMS, then the perceptual term -- each as (value,
+        """The optional terms that are on, in call order -- the rows of LOSS_TERMS, of MORE_LOSS_TERMS, then the perceptual term -- each as (value,
         prepare, call): the term's device [1] tensor; prepare(hr_img), which refuses an SR size the term does not take and makes
         sure of its scratch before anything is launched; call(plan, hr_img, first, ws, st), its m2t_*_loss call."""
         on = [(getattr(self, f"{t.name}_loss"), functools.partial(self._scratch_for, t, lib), functools.partial(self._term_call, t, lib))
-              for t in LOSS_TERMS if getattr(self, f"lambda_{t.name}") > 0.0]
+              for t in ALL_LOSS_TERMS if getattr(self, f"lambda_{t.name}") > 0.0]
         if self.lambda_perceptual > 0.0:
             on.append((self.perceptual_loss_value, self._perceptual_workspace_for, functools.partial(self._perceptual_loss_call, lib)))
         return on
