@@ -209,6 +209,16 @@ GMSD_SIGNATURES = {
 }
 GMSD_MIN_SIDE = 2                                              # min(H, W) >= 2: one 2 x 2 cell
 
+# the thirteenth header, include/m2t_degrade.h (LR synthesis beyond bicubic: blur-kernel bank, decimation, speckle and noise), bound on
+# the same library; must list every symbol that header declares.  The twelve tables above stay as they are.
+_ull = C.c_ulonglong
+DEGRADE_SIGNATURES = {
+    "m2t_degrade_patches": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _ull, _vp, _vp, _vp]),
+    "m2t_degrade_image_u8": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _ull, _ull, _d, _d, _i, _vp, _vp]),
+}
+DEGRADE_DESC_COLS = 11                                         # M2T_DEGRADE_DESC_COLS
+DEGRADE_KMAX = {2: 20, 3: 21, 4: 20}                           # the largest K per scale; K has the parity of the scale
+
 _lib = None
 
 
@@ -233,7 +243,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) \
             + list(MSSSIM_SIGNATURES.items()) + list(VIF_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()) \
             + list(PERCEPTUAL_SIGNATURES.items()) + list(RLUTRANS_SIGNATURES.items()) + list(INFER_SIGNATURES.items()) \
-            + list(TRAIN_SIGNATURES.items()) + list(TILES_SIGNATURES.items()) + list(GMSD_SIGNATURES.items()):
+            + list(TRAIN_SIGNATURES.items()) + list(TILES_SIGNATURES.items()) + list(GMSD_SIGNATURES.items()) + list(DEGRADE_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -49,12 +49,16 @@ class US1K:
 
     From HR alone: with `LR_folder=None`, or an `images` entry `(hr, None)`, HR is mod-cropped to a multiple of `scale` on the host
     and uploaded, and the LR image is computed on the device straight into its slot of `lr_pool` (one m2t_imresize_u8 launch per
-    image: MATLAB-style bicubic, resize.py); no LR cache is read or written.  Everything downstream is the same."""
+    image: MATLAB-style bicubic, resize.py); no LR cache is read or written.  Everything downstream is the same.
+
+    `degradation`: a degrade.Degradation.  Every entry must then be HR-only; no `lr_pool` is built, and `batch()` synthesises the LR
+    half of every sample afresh (m2t_degrade_patches: the sample's own blur kernel, decimation, speckle and noise) from draws of the
+    Degradation's own generator -- Python's `random` sees the crop and flip draws it sees without it."""
 
     def __init__(self, HR_folder: Optional[str] = None, LR_folder: Optional[str] = None, CACHE_folder: Optional[str] = None,
                  train: bool = True, augment: bool = True, scale: int = 2, colors: int = 3, patch_size: int = 96,
                  repeat: int = 168, add_noise: bool = False, cutout: bool = False, device="cuda",
-                 images: Optional[Sequence[Tuple[np.ndarray, Optional[np.ndarray]]]] = None):
+                 images: Optional[Sequence[Tuple[np.ndarray, Optional[np.ndarray]]]] = None, degradation=None):
         if colors != 3:
             raise _lib.M2TError("US1K (MI355X build): only colors=3 is built (configs/M2Trans_x4.yml:5)")
         if add_noise or cutout:
@@ -65,6 +69,12 @@ class US1K:
             raise _lib.M2TError("patch_size must be a multiple of scale")
         self.scale, self.colors, self.patch_size, self.repeat = scale, colors, patch_size, repeat
         self.train, self.augment = train, augment
+        self.degradation = degradation
+        if degradation is not None:
+            if getattr(degradation, "scale", None) != scale:
+                raise _lib.M2TError(f"degradation was built for x{getattr(degradation, 'scale', '?')}, the dataset is x{scale}")
+            if (images is None and LR_folder is not None) or (images is not None and any(lr is not None for _, lr in images)):
+                raise _lib.M2TError("degradation synthesises the LR half: every entry must be HR-only (LR_folder=None or (hr, None))")
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.M2TError("US1K (MI355X build) keeps its cache in HBM: a HIP device is required")
@@ -106,7 +116,10 @@ class US1K:
             lr_off += lr_shape[0] * lr_shape[1] * lr_shape[2]
             hr_off += hr.size
         self.hr_pool = torch.from_numpy(np.concatenate([np.ascontiguousarray(hr).reshape(-1) for hr, _ in images])).to(self.device)
-        if not any(synth):
+        if degradation is not None:
+            self.lr_pool = None
+            self._bank = degradation.bank_on(self.device)
+        elif not any(synth):
             self.lr_pool = torch.from_numpy(np.concatenate([np.ascontiguousarray(lr).reshape(-1) for _, lr in images])).to(self.device)
         else:
             from .resize import imresize_u8
@@ -137,6 +150,8 @@ class US1K:
     def batch(self, indices: Sequence[int], rng=random, draws=None):
         """`default_collate([dataset[i] for i in indices])` of the reference: (lr [n,3,p/s,p/s], hr [n,3,p,p]) float32
         in [0,1] on the device.  `draws` (list of (lx, ly, flags)) overrides the random draws."""
+        if self.degradation is not None:
+            return self._degraded_batch(indices, rng, draws)
         n = len(indices)
         desc = np.zeros((n, 8), dtype=np.int64)
         for k, idx in enumerate(indices):
@@ -153,6 +168,29 @@ class US1K:
                                             _lib.stream_ptr()), "m2t_crop_patches")
         return lr, hr
 
+    def _degraded_batch(self, indices: Sequence[int], rng, draws):
+        """`batch` with a Degradation: per item the crop draws on `rng`, then (bank index, sigma_add, sigma_speckle, noise_id) from
+        the Degradation's own generator; one m2t_degrade_patches call."""
+        D = self.degradation
+        n = len(indices)
+        desc = np.zeros((n, _lib.DEGRADE_DESC_COLS), dtype=np.int64)
+        lev = np.zeros((n, 2), dtype=np.float64)
+        for k, idx in enumerate(indices):
+            _, hr_off, _, _, hr_h, hr_w = self._geo[idx % self.nums_trainset]
+            lx, ly, flags = draws[k] if draws is not None else self.draw(idx, rng)
+            index, lev[k, 0], lev[k, 1], nid = D.draw()
+            desc[k, :8] = (hr_off, hr_h, hr_w, lx, ly, flags, index, nid - (1 << 64) if nid >= 1 << 63 else nid)
+            desc[k, 10] = int(D.gray_noise)
+        desc[:, 8:10] = lev.view(np.int64)
+        lp, hp = self.patch_size // self.scale, self.patch_size
+        lr = torch.empty(n, self.colors, lp, lp, dtype=torch.float32, device=self.device)
+        hr = torch.empty(n, self.colors, hp, hp, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().m2t_degrade_patches(_lib.ptr(self.hr_pool), _lib.ptr(self._bank), len(D), D.ksize,
+                                                       desc.ctypes.data_as(C.c_void_p), n, self.colors, self.patch_size, self.scale,
+                                                       D.seed, _lib.ptr(lr), _lib.ptr(hr), _lib.stream_ptr()), "m2t_degrade_patches")
+        return lr, hr
+
     def loader(self, batch_size: int, shuffle: bool = True, generator: Optional[torch.Generator] = None,
                rng=random) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
         """One epoch like `DataLoader(us1k, batch_size, shuffle=True, drop_last=False)` (datas/utils.py:22)."""
@@ -166,15 +204,27 @@ class Benchmark:
     name)` float32 in [0,1] on the device (the reference's DataLoader adds the batch dimension of 1), HR cropped to the
     LR size x scale, bit-identical to the reference's tensors.  `images`: optional list of (hr, lr, name) uint8 HWC
     arrays instead of the folders.  With `LR_folder=None`, or an entry `(hr, None, name)`, the LR image is computed on the
-    device from the mod-cropped HR (m2t_imresize_u8: MATLAB-style bicubic, resize.py)."""
+    device from the mod-cropped HR (m2t_imresize_u8: MATLAB-style bicubic, resize.py).
+
+    `degradation`: a degrade.Degradation.  Every entry must then be HR-only, and the LR image is computed once, here, with
+    m2t_degrade_image_u8 from a fresh `random.Random(degradation.seed)` in image order: validation sees the same LR every epoch and
+    every run, and the Degradation's own generator is not advanced."""
 
     def __init__(self, HR_folder: Optional[str] = None, LR_folder: Optional[str] = None, scale: int = 2, colors: int = 3,
-                 device="cuda", images=None):
+                 device="cuda", images=None, degradation=None):
         if colors != 3:
             raise _lib.M2TError("Benchmark (MI355X build): only colors=3 is built (configs/M2Trans_x4.yml:5)")
         self.scale, self.colors, self.device = scale, colors, torch.device(device)
         if self.device.type != "cuda":
             raise _lib.M2TError("Benchmark (MI355X build) keeps its images in HBM: a HIP device is required")
+        self.degradation = degradation
+        if degradation is not None:
+            if getattr(degradation, "scale", None) != scale:
+                raise _lib.M2TError(f"degradation was built for x{getattr(degradation, 'scale', '?')}, the dataset is x{scale}")
+            if (images is None and LR_folder is not None) or (images is not None and any(lr is not None for _, lr, _ in images)):
+                raise _lib.M2TError("degradation synthesises the LR half: every entry must be HR-only (LR_folder=None or (hr, None, name))")
+            from .degrade import BENCHMARK_NOISE_ID
+            rng = random.Random(degradation.seed)
         if images is None:
             from PIL import Image                                             # imageio pilmode="RGB" == PIL convert("RGB")
             images = []
@@ -189,7 +239,12 @@ class Benchmark:
                 images.append((hr, lr, tag))
         self.img_name = [n for _, _, n in images]
         self._items = []
-        for hr, lr, _ in images:
+        for k, (hr, lr, _) in enumerate(images):
+            if degradation is not None:
+                hr_dev = torch.from_numpy(_modcrop_hr(hr, scale, colors)).to(self.device)
+                index, sa, ss = degradation.draw_levels(rng)
+                self._items.append((hr_dev, degradation.apply_image(hr_dev, index, sa, ss, BENCHMARK_NOISE_ID + k)))
+                continue
             if lr is None:
                 from .resize import imresize_u8
                 hr_dev = torch.from_numpy(_modcrop_hr(hr, scale, colors)).to(self.device)

@@ -262,6 +262,7 @@ def fit(model, train_step, train_set, valid_sets, *, epochs, batch_size, lr0, et
 
     stat_dict = new_stat_dict([n for n, _ in valid])
     start_epoch, resumed_lr = 1, None
+    degradation = getattr(train_set, "degradation", None)       # its own generator: the per-sample kernel and noise draws
     if resume is not None:
         path = latest_checkpoint(resume)
         if path is not None:
@@ -271,6 +272,8 @@ def fit(model, train_step, train_set, valid_sets, *, epochs, batch_size, lr0, et
             log("## select {}, resume training from epoch {}. ##".format(path, start_epoch))
             if ckpt.get("m2t_rng") is not None:
                 set_rng_state(ckpt["m2t_rng"], generator)       # the run continues exactly: draws and schedule
+                if degradation is not None and ckpt["m2t_rng"].get("degradation") is not None:
+                    degradation.set_state(ckpt["m2t_rng"]["degradation"])
                 train_step.scheduler_last_epoch = start_epoch - 1
             else:
                 # a file of the reference: its own resume re-uses the saved rate for the first epoch (epoch_rates)
@@ -332,6 +335,8 @@ def fit(model, train_step, train_set, valid_sets, *, epochs, batch_size, lr0, et
             ckpt = export_checkpoint(model, train_step, epoch=epoch, stat_dict=stat_dict, lr0=float(lr0), eta_min=float(eta_min),
                                      t_max=float(epochs))
             ckpt["m2t_rng"] = rng_state(generator)
+            if degradation is not None:
+                ckpt["m2t_rng"]["degradation"] = degradation.get_state()
             torch.save(ckpt, os.path.join(model_dir, "model_x{}_{}.pt".format(scale, epoch)))
             _dump_yaml(stat_dict, os.path.join(out_dir, "stat_dict.yml"))
         train_step.scheduler_last_epoch += 1                    # scheduler.step(), train.py:358
@@ -387,6 +392,7 @@ IGNORED_KEYS = ("gpu_ids", "threads", "num_heads")
 TRAINSTEP_KEYS = ("pixel_loss", "pixel_loss_param", "lambda_ssim", "lambda_msssim", "lambda_fft", "fft_norm", "lambda_vif", "lambda_gmsd", "accum_steps",
                   "max_grad_norm", "weight_decay", "decoupled_weight_decay", "ema_decay", "skip_nonfinite", "param_groups")
 LOOP_KEYS = ("train_hr_path", "eval_folders", "preview_every", "validate_ema", "seed", "ring_rows", "track_grad_norm")
+DATA_KEYS = ("degradation",)            # a mapping of degrade.Degradation's arguments: LR synthesis beyond bicubic
 CLI_KEYS = ("config", "resume")         # the command line's own arguments, which config.yml records as the reference's does
 
 
@@ -415,7 +421,7 @@ def resolve_config(cfg: dict, compute_dtype=None) -> dict:
     """A yaml dictionary -> {"model": the namespace dict for infer.model_namespace, "train_step": TrainStep's keyword arguments,
     "fit": fit's keyword arguments (without out_dir / resume), "data": what build_datasets needs, "ignored": the accepted keys
     that do nothing here}.  An unknown key is an M2TError that names it."""
-    known = set(REFERENCE_KEYS) | set(IGNORED_KEYS) | set(TRAINSTEP_KEYS) | set(LOOP_KEYS) | set(CLI_KEYS)
+    known = set(REFERENCE_KEYS) | set(IGNORED_KEYS) | set(TRAINSTEP_KEYS) | set(LOOP_KEYS) | set(DATA_KEYS) | set(CLI_KEYS)
     unknown = sorted(k for k in cfg if k not in known)
     if unknown:
         raise M2TError(f"unknown config key{'s' if len(unknown) > 1 else ''}: {', '.join(unknown)}")
@@ -429,6 +435,10 @@ def resolve_config(cfg: dict, compute_dtype=None) -> dict:
                        "(pass --set lambda_clip=0, or call m2trans_amd.train.fit with a TrainStep(semantic_loss=...) of your own)")
     if cfg.get("data_add_noise"):
         raise M2TError("data_add_noise is dead code in the reference (datas/us1k.py:156-167) and is not built")
+    degradation = None
+    if cfg.get("degradation") is not None:
+        from .degrade import check_config
+        degradation = check_config(cfg["degradation"])
     model = {k: cfg[k] for k in MODEL_KEYS if k in cfg and k != "model"}
     model.setdefault("n_feats", 64)
     model.setdefault("n_blocks", 8)
@@ -460,6 +470,8 @@ def resolve_config(cfg: dict, compute_dtype=None) -> dict:
             "eval_sets": eval_sets, "eval_folders": dict(cfg.get("eval_folders") or {}), "scale": int(cfg["scale"]),
             "colors": int(model["colors"]), "patch_size": int(cfg["patch_size"]), "data_repeat": int(cfg.get("data_repeat", 1)),
             "data_augment": bool(cfg.get("data_augment", True))}
+    if degradation is not None:
+        data["degradation"] = degradation
     return {"model": model, "train_step": ts, "fit": fit_kw, "data": data, "pretrain": cfg.get("pretrain"),
             "log_path": str(cfg.get("log_path") or "./experiments"), "log_name": cfg.get("log_name"),
             "ignored": [k for k in IGNORED_KEYS if k in cfg]}
@@ -481,7 +493,9 @@ def experiment_dir(log_path: str, log_name, model: str, scale: int, stamp: str) 
 def build_datasets(data: dict, device="cuda"):
     """(US1K, [(name, Benchmark)]) in the folder layout of datas/utils.py:7-53, or from plain folders."""
     from .datas import US1K, Benchmark
+    from .degrade import from_config
     from .infer import image_names
+    degradation = from_config(data["scale"], data.get("degradation"))
     common = dict(train=True, augment=data["data_augment"], scale=data["scale"], colors=data["colors"], patch_size=data["patch_size"],
                   repeat=data["data_repeat"], device=device)
     if data["training_dataset"] == "folder":
@@ -490,18 +504,19 @@ def build_datasets(data: dict, device="cuda"):
         images = [(np.asarray(Image.open(os.path.join(folder, n)).convert("RGB")), None) for n in image_names(folder)]
         if not images:
             raise M2TError(f"train_hr_path {folder}: no image file")
-        train = US1K(images=images, **common)
+        train = US1K(images=images, degradation=degradation, **common)
     else:
         root = str(data["data_path"])
-        train = US1K(os.path.join(root, "US1K/US1K_train_HR"), os.path.join(root, "US1K/US1K_train_LR_bicubic"),
-                     os.path.join(root, "us1k_cache"), **common)
+        train = US1K(os.path.join(root, "US1K/US1K_train_HR"), None if degradation is not None else os.path.join(root, "US1K/US1K_train_LR_bicubic"),
+                     os.path.join(root, "us1k_cache"), degradation=degradation, **common)
     valid = []
     for name in data["eval_sets"]:
         base = os.path.join(str(data["data_path"]), "benchmark", EVAL_SETS[name])
         valid.append((name, Benchmark(os.path.join(base, "HR"), os.path.join(base, "LR_bicubic"), scale=data["scale"],
                                       colors=data["colors"], device=device)))
     for name, hr_dir in data["eval_folders"].items():
-        valid.append((str(name), Benchmark(str(hr_dir), None, scale=data["scale"], colors=data["colors"], device=device)))
+        valid.append((str(name), Benchmark(str(hr_dir), None, scale=data["scale"], colors=data["colors"], device=device,
+                                           degradation=degradation)))
     return train, valid
 
 
