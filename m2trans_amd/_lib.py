@@ -219,6 +219,17 @@ DEGRADE_SIGNATURES = {
 DEGRADE_DESC_COLS = 11                                         # M2T_DEGRADE_DESC_COLS
 DEGRADE_KMAX = {2: 20, 3: 21, 4: 20}                           # the largest K per scale; K has the parity of the scale
 
+# the fourteenth header, include/m2t_jpeg.h (JPEG compression artefacts: a simulated baseline round trip with a per-sample quality),
+# bound on the same library; must list every symbol that header declares.  The thirteen tables above stay as they are.
+JPEG_SIGNATURES = {
+    "m2t_jpeg_quant_tables": (_i, [_i, C.POINTER(_i), C.POINTER(_i)]),
+    "m2t_jpeg_image_u8": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "m2t_degrade_jpeg_patches": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _ull, _vp, _vp, _vp]),
+    "m2t_degrade_jpeg_image_u8": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _ull, _ull, _d, _d, _i, _vp, _i, _vp, _vp]),
+}
+JPEG_DESC_COLS = 12                                            # M2T_DEGRADE_JPEG_DESC_COLS: column 11 is the quality
+JPEG_CONSTS = 320                                              # M2T_JPEG_CONSTS: T[64], recip[256]
+
 _lib = None
 
 
@@ -243,7 +254,8 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(SPECTRAL_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) \
             + list(MSSSIM_SIGNATURES.items()) + list(VIF_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()) \
             + list(PERCEPTUAL_SIGNATURES.items()) + list(RLUTRANS_SIGNATURES.items()) + list(INFER_SIGNATURES.items()) \
-            + list(TRAIN_SIGNATURES.items()) + list(TILES_SIGNATURES.items()) + list(GMSD_SIGNATURES.items()) + list(DEGRADE_SIGNATURES.items()):
+            + list(TRAIN_SIGNATURES.items()) + list(TILES_SIGNATURES.items()) + list(GMSD_SIGNATURES.items()) + list(DEGRADE_SIGNATURES.items()) \
+            + list(JPEG_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

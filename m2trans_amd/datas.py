@@ -119,6 +119,7 @@ class US1K:
         if degradation is not None:
             self.lr_pool = None
             self._bank = degradation.bank_on(self.device)
+            self._jpeg = degradation.jpeg_constants_on(self.device) if degradation.jpeg is not None else None
         elif not any(synth):
             self.lr_pool = torch.from_numpy(np.concatenate([np.ascontiguousarray(lr).reshape(-1) for _, lr in images])).to(self.device)
         else:
@@ -170,21 +171,31 @@ class US1K:
 
     def _degraded_batch(self, indices: Sequence[int], rng, draws):
         """`batch` with a Degradation: per item the crop draws on `rng`, then (bank index, sigma_add, sigma_speckle, noise_id) from
-        the Degradation's own generator; one m2t_degrade_patches call."""
+        the Degradation's own generator -- and, with `jpeg`, the quality of draw_jpeg() right after them; one m2t_degrade_patches
+        (m2t_degrade_jpeg_patches) call."""
         D = self.degradation
         n = len(indices)
-        desc = np.zeros((n, _lib.DEGRADE_DESC_COLS), dtype=np.int64)
+        desc = np.zeros((n, _lib.DEGRADE_DESC_COLS if D.jpeg is None else _lib.JPEG_DESC_COLS), dtype=np.int64)
         lev = np.zeros((n, 2), dtype=np.float64)
         for k, idx in enumerate(indices):
             _, hr_off, _, _, hr_h, hr_w = self._geo[idx % self.nums_trainset]
             lx, ly, flags = draws[k] if draws is not None else self.draw(idx, rng)
             index, lev[k, 0], lev[k, 1], nid = D.draw()
+            if D.jpeg is not None:
+                desc[k, 11] = D.draw_jpeg()
             desc[k, :8] = (hr_off, hr_h, hr_w, lx, ly, flags, index, nid - (1 << 64) if nid >= 1 << 63 else nid)
             desc[k, 10] = int(D.gray_noise)
         desc[:, 8:10] = lev.view(np.int64)
         lp, hp = self.patch_size // self.scale, self.patch_size
         lr = torch.empty(n, self.colors, lp, lp, dtype=torch.float32, device=self.device)
         hr = torch.empty(n, self.colors, hp, hp, dtype=torch.float32, device=self.device)
+        if D.jpeg is not None:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.load().m2t_degrade_jpeg_patches(_lib.ptr(self.hr_pool), _lib.ptr(self._bank), len(D), D.ksize,
+                                                                _lib.ptr(self._jpeg), desc.ctypes.data_as(C.c_void_p), n, self.colors,
+                                                                self.patch_size, self.scale, D.seed, _lib.ptr(lr), _lib.ptr(hr),
+                                                                _lib.stream_ptr()), "m2t_degrade_jpeg_patches")
+            return lr, hr
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().m2t_degrade_patches(_lib.ptr(self.hr_pool), _lib.ptr(self._bank), len(D), D.ksize,
                                                        desc.ctypes.data_as(C.c_void_p), n, self.colors, self.patch_size, self.scale,
@@ -243,7 +254,8 @@ class Benchmark:
             if degradation is not None:
                 hr_dev = torch.from_numpy(_modcrop_hr(hr, scale, colors)).to(self.device)
                 index, sa, ss = degradation.draw_levels(rng)
-                self._items.append((hr_dev, degradation.apply_image(hr_dev, index, sa, ss, BENCHMARK_NOISE_ID + k)))
+                quality = degradation.draw_jpeg(rng) if degradation.jpeg is not None else 0
+                self._items.append((hr_dev, degradation.apply_image(hr_dev, index, sa, ss, BENCHMARK_NOISE_ID + k, quality=quality)))
                 continue
             if lr is None:
                 from .resize import imresize_u8

@@ -8,6 +8,9 @@ draws of datas.US1K -- sees the same sequence with and without it.  `datas.US1K`
 yaml) and tools/make_lr.py accept one.  The device work is one fused kernel per batch; its result is defined to the byte
 (include/m2t_degrade.h) and pinned by a NumPy fp64 restatement (tests/degrade_ref.py).
 
+`jpeg=(lo, hi)` ends the pipeline with a simulated baseline JPEG round trip of a per-sample quality (include/m2t_jpeg.h, k_jpeg.hip; NumPy
+restatement tests/jpeg_ref.py); `jpeg_roundtrip` applies the stage alone to a uint8 image.
+
 Device tensors only: there is no host fallback."""
 from __future__ import annotations
 
@@ -20,7 +23,7 @@ import numpy as np
 from . import _lib
 from ._lib import M2TError
 
-CONFIG_KEYS = ("bank", "sigma", "iso_prob", "ksize", "kernels", "noise", "speckle", "gray_noise", "seed")
+CONFIG_KEYS = ("bank", "sigma", "iso_prob", "ksize", "kernels", "noise", "speckle", "gray_noise", "seed", "jpeg", "jpeg_prob")
 BENCHMARK_NOISE_ID = 1 << 63          # datas.Benchmark numbers its images from here: apart from the running counter of draw()
 
 
@@ -47,6 +50,71 @@ def gaussian_kernel(K: int, sigma1: float, sigma2: float, theta: float) -> np.nd
     return w / w.sum()
 
 
+def jpeg_constants() -> np.ndarray:
+    """The 320 fp64 constants of include/m2t_jpeg.h: T[u][x] = c_u cos((2x + 1) u pi / 16) row-major, then recip[k] = 1.0 / k
+    (recip[0] = 0, unused).  T is evaluated in 50-digit decimal arithmetic -- cos(pi / 16) by two half-angle steps from cos(pi / 4),
+    its multiples by the Chebyshev recurrence -- and rounded once, so every entry is the correctly rounded value."""
+    import decimal
+    with decimal.localcontext() as ctx:
+        ctx.prec = 50
+        one, two = decimal.Decimal(1), decimal.Decimal(2)
+        c = two.sqrt() / two                                  # cos(pi / 4)
+        for _ in range(2):
+            c = ((one + c) / two).sqrt()                      # cos(pi / 8), cos(pi / 16)
+        cos = [one, c]
+        for _ in range(30):
+            cos.append(two * c * cos[-1] - cos[-2])           # cos(k pi / 16), k = 0 .. 31
+        c0 = (one / decimal.Decimal(8)).sqrt()
+        T = [float((c0 if u == 0 else one / two) * cos[(2 * x + 1) * u % 32]) for u in range(8) for x in range(8)]
+    recip = [0.0] + [1.0 / k for k in range(1, 256)]
+    return np.array(T + recip, dtype=np.float64)
+
+
+_JPEG_CONSTS = None
+_JPEG_DEV = {}
+
+
+def _jpeg_constants_on(device):
+    """The constants as a float64 [320] tensor on `device`, uploaded on first use and kept (one per process and device)."""
+    import torch
+    global _JPEG_CONSTS
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise M2TError("the JPEG stage runs on the device: a HIP device is required")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if device not in _JPEG_DEV:
+        if _JPEG_CONSTS is None:
+            _JPEG_CONSTS = jpeg_constants()
+        _JPEG_DEV[device] = torch.from_numpy(_JPEG_CONSTS).to(device)
+    return _JPEG_DEV[device]
+
+
+def jpeg_roundtrip(img_u8_dev, quality: int, out=None):
+    """uint8 [H, W, 3] on the device -> the image after a simulated baseline JPEG round trip at 4:4:4 (m2t_jpeg_image_u8,
+    include/m2t_jpeg.h), `quality` 1 .. 100; the 8 x 8 blocks start at the image's origin."""
+    import torch
+    t = img_u8_dev
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or not t.is_cuda:
+        got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise M2TError(f"jpeg_roundtrip: a uint8 [H,W,3] device tensor is required, got {got}")
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise M2TError(f"jpeg_roundtrip: quality must be an integer 1 .. 100, got {quality!r}")
+    t = t.contiguous()
+    H, W = int(t.shape[0]), int(t.shape[1])
+    if H < 1 or W < 1:
+        raise M2TError(f"jpeg_roundtrip: the image {H}x{W} is empty")
+    if out is None:
+        out = torch.empty_like(t)
+    elif out.dtype != torch.uint8 or out.numel() != t.numel() or out.device != t.device or not out.is_contiguous() or out.data_ptr() == t.data_ptr():
+        raise M2TError(f"jpeg_roundtrip: out must be another contiguous uint8 tensor of {t.numel()} elements on {t.device}")
+    consts = _jpeg_constants_on(t.device)
+    with torch.cuda.device(t.device):
+        _lib.check(_lib.load().m2t_jpeg_image_u8(_lib.ptr(t), H, W, 3, _lib.ptr(consts), quality, _lib.ptr(out), _lib.stream_ptr()),
+                   "m2t_jpeg_image_u8")
+    return out
+
+
 def _pair(name: str, v, positive: bool = False) -> Tuple[float, float]:
     try:
         lo, hi = v
@@ -60,18 +128,21 @@ def _pair(name: str, v, positive: bool = False) -> Tuple[float, float]:
 
 class Degradation:
     """`Degradation(scale, bank=256, sigma=(0.2, 0.8 * scale), iso_prob=0.5, ksize=None, kernels=None, noise=(0, 8),
-    speckle=(0, 0.15), gray_noise=True, seed=33)`.
+    speckle=(0, 0.15), gray_noise=True, seed=33, jpeg=None, jpeg_prob=1.0)`.
 
     bank, sigma, iso_prob, ksize: the kernel bank -- `bank` anisotropic Gaussians of `ksize` x `ksize` taps; per kernel the draws are
         `iso = random() < iso_prob`, `sigma1 = uniform(*sigma)`, `sigma2 = sigma1 if iso else uniform(*sigma)`, `theta = uniform(0, pi)`.
     kernels: an ndarray [M, K, K] used instead (measured PSFs): K of the scale's parity, finite, every kernel summing to 1 within 1e-12.
     noise: the range of the additive level, in grey levels of the 0 .. 255 scale; speckle: the range of the multiplicative level.
     gray_noise: one variate per pixel for the three channels (ultrasound PNGs are grey replicated to RGB).
-    seed: seeds the object's own `random.Random` (bank first, then the per-sample draws) and is the key of the noise generator."""
+    seed: seeds the object's own `random.Random` (bank first, then the per-sample draws) and is the key of the noise generator.
+    jpeg, jpeg_prob: `jpeg=(lo, hi)`, integer qualities with 1 <= lo <= hi <= 100, ends the pipeline with a simulated baseline JPEG round
+        trip (include/m2t_jpeg.h) of a quality drawn per sample by `draw_jpeg()`; with probability 1 - jpeg_prob a sample skips the
+        stage.  None: no stage, and not one draw, call or allocation more than without the argument."""
 
     def __init__(self, scale: int, bank: int = 256, sigma: Optional[Sequence[float]] = None, iso_prob: float = 0.5,
                  ksize: Optional[int] = None, kernels=None, noise: Sequence[float] = (0.0, 8.0), speckle: Sequence[float] = (0.0, 0.15),
-                 gray_noise: bool = True, seed: int = 33):
+                 gray_noise: bool = True, seed: int = 33, jpeg: Optional[Sequence[int]] = None, jpeg_prob: float = 1.0):
         if scale not in (2, 3, 4):
             raise M2TError(f"Degradation: scale must be 2, 3 or 4, got {scale!r}")
         self.scale = int(scale)
@@ -80,6 +151,18 @@ class Degradation:
         self.seed = seed
         self.noise, self.speckle = _pair("noise", noise), _pair("speckle", speckle)
         self.gray_noise = bool(gray_noise)
+        if jpeg is not None:
+            try:
+                lo, hi = jpeg
+            except (TypeError, ValueError):
+                raise M2TError(f"Degradation: jpeg must be None or (lo, hi), got {jpeg!r}") from None
+            if any(isinstance(v, bool) or not isinstance(v, int) for v in (lo, hi)) or not 1 <= lo <= hi <= 100:
+                raise M2TError(f"Degradation: jpeg must be integer qualities with 1 <= lo <= hi <= 100, got {jpeg!r}")
+            jpeg = (lo, hi)
+        self.jpeg = jpeg
+        if isinstance(jpeg_prob, bool) or not isinstance(jpeg_prob, (int, float)) or not 0.0 <= jpeg_prob <= 1.0:
+            raise M2TError(f"Degradation: jpeg_prob must be a number in [0, 1], got {jpeg_prob!r}")
+        self.jpeg_prob = float(jpeg_prob)
         self._rng = random.Random(seed)
         self._noise_id = 0
         top = _lib.DEGRADE_KMAX[self.scale]
@@ -134,6 +217,16 @@ class Degradation:
         self._noise_id = (nid + 1) & ((1 << 64) - 1)
         return index, sa, ss, nid
 
+    def draw_jpeg(self, rng=None) -> int:
+        """The quality of the next sample from `rng` (the object's own generator by default): two draws, always --
+        `apply = random() < jpeg_prob`, `q = randint(lo, hi)` -- and `q if apply else 0` (0: the stage is skipped)."""
+        if self.jpeg is None:
+            raise M2TError("Degradation: draw_jpeg() needs jpeg=(lo, hi)")
+        rng = self._rng if rng is None else rng
+        apply = rng.random() < self.jpeg_prob
+        q = rng.randint(*self.jpeg)
+        return q if apply else 0
+
     def get_state(self) -> dict:
         """Plain picklable data: where the per-sample draws stand (the bank is a function of the constructor's arguments)."""
         return {"random": self._rng.getstate(), "noise_id": self._noise_id}
@@ -164,12 +257,18 @@ class Degradation:
             self._dev[device] = torch.from_numpy(self.kernels).to(device)
         return self._dev[device]
 
+    def jpeg_constants_on(self, device):
+        """The constants of the JPEG stage (T and recip, include/m2t_jpeg.h) as a float64 [320] tensor on `device`, uploaded once."""
+        return _jpeg_constants_on(device)
+
     @property
     def bank(self):
         return self.bank_on("cuda")
 
-    def apply_image(self, hr_u8_dev, index: int = 0, sigma_add: float = 0.0, sigma_speckle: float = 0.0, noise_id: int = 0, out=None):
-        """uint8 [H, W, 3] on the device -> the degraded uint8 [H // s, W // s, 3] (m2t_degrade_image_u8), kernel `index` of the bank."""
+    def apply_image(self, hr_u8_dev, index: int = 0, sigma_add: float = 0.0, sigma_speckle: float = 0.0, noise_id: int = 0, out=None,
+                    quality: int = 0):
+        """uint8 [H, W, 3] on the device -> the degraded uint8 [H // s, W // s, 3] (m2t_degrade_image_u8), kernel `index` of the bank.
+        `quality` 1 .. 100 ends with the JPEG stage (m2t_degrade_jpeg_image_u8); 0 is the call without it."""
         import torch
         t = hr_u8_dev
         if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or not t.is_cuda:
@@ -185,6 +284,16 @@ class Degradation:
         elif out.dtype != torch.uint8 or out.numel() != (H // s) * (W // s) * 3 or out.device != t.device or not out.is_contiguous():
             raise M2TError(f"apply_image: out must be a contiguous uint8 tensor of {(H // s) * (W // s) * 3} elements on {t.device}")
         bank = self.bank_on(t.device)
+        if isinstance(quality, bool) or not isinstance(quality, int):
+            raise M2TError(f"apply_image: quality must be an integer 0 .. 100, got {quality!r}")
+        if quality != 0:
+            consts = _jpeg_constants_on(t.device)
+            with torch.cuda.device(t.device):
+                _lib.check(_lib.load().m2t_degrade_jpeg_image_u8(_lib.ptr(t), H, W, 3, _lib.ptr(bank), len(self), self.ksize, int(index), s,
+                                                                 self.seed, int(noise_id) & ((1 << 64) - 1), float(sigma_add),
+                                                                 float(sigma_speckle), int(self.gray_noise), _lib.ptr(consts), quality,
+                                                                 _lib.ptr(out), _lib.stream_ptr()), "m2t_degrade_jpeg_image_u8")
+            return out
         with torch.cuda.device(t.device):
             _lib.check(_lib.load().m2t_degrade_image_u8(_lib.ptr(t), H, W, 3, _lib.ptr(bank), len(self), self.ksize, int(index), s,
                                                         self.seed, int(noise_id) & ((1 << 64) - 1), float(sigma_add), float(sigma_speckle),
@@ -199,7 +308,7 @@ def from_config(scale: int, cfg) -> Optional[Degradation]:
     kw = check_config(cfg)
     if isinstance(kw.get("kernels"), str):
         kw["kernels"] = np.load(kw["kernels"])
-    for k in ("sigma", "noise", "speckle"):
+    for k in ("sigma", "noise", "speckle", "jpeg"):
         if isinstance(kw.get(k), list):
             kw[k] = tuple(kw[k])
     return Degradation(int(scale), **kw)

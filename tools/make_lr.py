@@ -78,7 +78,8 @@ def main(argv=None):
         hr_dev = torch.from_numpy(np.ascontiguousarray(hr)).cuda()
         if degradation is not None:
             index, sa, ss = degradation.draw_levels(rng)
-            lr = degradation.apply_image(hr_dev, index, sa, ss, BENCHMARK_NOISE_ID + k).cpu().numpy()
+            quality = degradation.draw_jpeg(rng) if degradation.jpeg is not None else 0     # `jpeg:` in the mapping, as datas.Benchmark
+            lr = degradation.apply_image(hr_dev, index, sa, ss, BENCHMARK_NOISE_ID + k, quality=quality).cpu().numpy()
         else:
             lr = imresize_u8(hr_dev, args.scale).cpu().numpy()
         png, npy = lr_paths(args, tag)
