@@ -1,6 +1,6 @@
 """ctypes binding of libm2t.so (include/m2t.h, include/m2t_spectral.h, include/m2t_resize.h, include/m2t_msssim.h,
 include/m2t_vif.h, include/m2t_groups.h, include/m2t_perceptual.h, include/m2t_rlutrans.h, include/m2t_infer.h, include/m2t_train.h,
-include/m2t_tiles.h, include/m2t_gmsd.h).
+include/m2t_tiles.h, include/m2t_gmsd.h, include/m2t_degrade.h, include/m2t_jpeg.h, include/m2t_wavelet.h).
 
 The product path has NO fallback: if the HIP library is missing, or a call fails, this
 module raises.  Build it with ``python -m m2trans_amd.build`` (hipcc, gfx950).
@@ -230,6 +230,24 @@ JPEG_SIGNATURES = {
 JPEG_DESC_COLS = 12                                            # M2T_DEGRADE_JPEG_DESC_COLS: column 11 is the quality
 JPEG_CONSTS = 320                                              # M2T_JPEG_CONSTS: T[64], recip[256]
 
+# the fifteenth header, include/m2t_wavelet.h (the wavelet-domain loss term and the stationary wavelet transform), bound on the same
+# library; must list every symbol that header declares.  The fourteen tables above stay as they are.  lo, hi and band_weights are HOST
+# double arrays (ctypes arrays, or None where the header allows NULL).
+_dp = C.POINTER(_d)
+WAVELET_SIGNATURES = {
+    "m2t_wavelet_loss_scratch_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
+    "m2t_swt2": (_i, [_vp, _i, _i, _i, _i, _ll, _i, _dp, _dp, _i, _i, _vp, _vp, _vp]),
+    "m2t_wavelet_loss_tensor": (_i, [_vp, _vp, _i, _i, _i, _i, _ll, _i, _f, _i, _d, _dp, _dp, _i, _i, _dp, _d, _vp, _vp, _vp, _i, _vp, _vp]),
+    "m2t_wavelet_loss": (_i, [_vp, _vp, _f, _d, _f, _dp, _dp, _i, _i, _dp, _d, _vp, _i, _vp, _vp, _vp]),
+}
+WAVELET_MAX_TAPS, WAVELET_MAX_LEVELS = 8, 3
+
+
+def wavelet_min_side(taps: int, levels: int) -> int:
+    """min(H, W) the wavelet entries take: a tap index wraps at most once."""
+    return (int(taps) - 1) * 2 ** (int(levels) - 1) + 1
+
+
 _lib = None
 
 
@@ -255,7 +273,7 @@ def load():
             + list(MSSSIM_SIGNATURES.items()) + list(VIF_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()) \
             + list(PERCEPTUAL_SIGNATURES.items()) + list(RLUTRANS_SIGNATURES.items()) + list(INFER_SIGNATURES.items()) \
             + list(TRAIN_SIGNATURES.items()) + list(TILES_SIGNATURES.items()) + list(GMSD_SIGNATURES.items()) + list(DEGRADE_SIGNATURES.items()) \
-            + list(JPEG_SIGNATURES.items()):
+            + list(JPEG_SIGNATURES.items()) + list(WAVELET_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

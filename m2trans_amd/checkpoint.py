@@ -26,7 +26,8 @@ above, key for key.
 With a pixel loss other than L1 (TrainStep(pixel_loss=...)) the dict carries ``m2t_loss`` = {"pixel_loss": name, "param": eps /
 beta / None}; ``import_checkpoint`` sets the TrainStep's loss from it and leaves the loss alone when the file has no such entry.
 An L1 run writes no entry: its dict is the one above.  Every optional loss term of the step that is on (train_step.LOSS_TERMS, in
-that order, then the perceptual term, then train_step.MORE_LOSS_TERMS: ``"lambda_gmsd"`` comes last) adds its weight to the entry
+that order, then the perceptual term, then train_step.MORE_LOSS_TERMS and LATER_LOSS_TERMS: ``"lambda_gmsd"``, then ``"lambda_wavelet"`` with ``"wavelet"`` (a name or
+the two tap lists), ``"wavelet_levels"``, ``"wavelet_band_weights"`` and ``"wavelet_eps"`` behind it) adds its weight to the entry
 as ``"lambda_<term>"`` (and the entry then exists for an L1 pixel term too); ``import_checkpoint`` calls the step's ``set_lambda_<term>`` with it.  ``"lambda_fft"`` is followed by ``"fft_norm"``;
 ``"lambda_perceptual"`` by ``"perceptual_criterion"``, ``"perceptual_weights"`` and ``"perceptual_resize"`` (never the VGG19 weights;
 ``import_checkpoint`` sets them on the step's ``perceptual_loss`` object first).  The keys of a term whose weight is 0 are absent, so
@@ -106,10 +107,10 @@ def _optim_options(train_step) -> dict:
 def _pixel_loss(train_step):
     """The ``m2t_loss`` entry of a step object, or None for L1 with every optional term off (and for an object that knows no pixel
     losses)."""
-    from .train_step import LOSS_TERMS, MORE_LOSS_TERMS, resolve_pixel_loss
+    from .train_step import LATER_LOSS_TERMS, LOSS_TERMS, MORE_LOSS_TERMS, resolve_pixel_loss
     _, canon, value = resolve_pixel_loss(getattr(train_step, "pixel_loss", "l1"), getattr(train_step, "pixel_loss_param", None))
     # (the entry keeps the order it always had -- LOSS_TERMS, then the perceptual term -- and the later rows follow it)
-    names = [t.name for t in LOSS_TERMS] + ["perceptual"] + [t.name for t in MORE_LOSS_TERMS]
+    names = [t.name for t in LOSS_TERMS] + ["perceptual"] + [t.name for t in MORE_LOSS_TERMS + LATER_LOSS_TERMS]
     lam = {n: float(getattr(train_step, f"lambda_{n}", 0.0) or 0.0) for n in names}
     if canon == "l1" and not any(lam.values()):
         return None
@@ -120,6 +121,13 @@ def _pixel_loss(train_step):
         out[f"lambda_{n}"] = lam[n]
         if n == "fft":
             out["fft_norm"] = str(getattr(train_step, "fft_norm", "backward"))
+        if n == "wavelet":
+            w = getattr(train_step, "wavelet", "haar")
+            out["wavelet"] = w if isinstance(w, str) else [[float(v) for v in f] for f in w]
+            out["wavelet_levels"] = int(getattr(train_step, "wavelet_levels", 2))
+            bw = getattr(train_step, "wavelet_band_weights", None)
+            out["wavelet_band_weights"] = None if bw is None else [float(v) for v in bw]
+            out["wavelet_eps"] = float(getattr(train_step, "wavelet_eps", 0.0))
         if n == "perceptual":
             # the settings of the term, never the VGG19 weights (an integrator loads those: INTEGRATION.md)
             p = train_step.perceptual_loss
@@ -243,18 +251,31 @@ def import_checkpoint(ckpt: dict, model, train_step=None) -> int:
         else:
             from .train_step import resolve_pixel_loss
             _, train_step.pixel_loss, train_step.pixel_loss_param = resolve_pixel_loss(ml["pixel_loss"], ml.get("param"))
-        from .train_step import LOSS_TERMS, MORE_LOSS_TERMS, resolve_fft_norm, resolve_lambda
-        for t in LOSS_TERMS + MORE_LOSS_TERMS:       # (a file without a term's key leaves that weight alone: 0 on a fresh step)
+        from .train_step import ALL_LOSS_TERMS, resolve_fft_norm, resolve_lambda, resolve_wavelet
+        for t in ALL_LOSS_TERMS:       # (a file without a term's key leaves that weight alone: 0 on a fresh step)
             key = f"lambda_{t.name}"
             if key not in ml:
                 continue
+            more = ()
+            if t.name == "fft":
+                more = (ml.get("fft_norm"),)
+            if t.name == "wavelet":
+                # (the file's own settings, whatever the importing step was built with: absent weights are the default ones)
+                w = resolve_wavelet(ml.get("wavelet", "haar"), ml.get("wavelet_levels", 2), ml.get("wavelet_band_weights"),
+                                    ml.get("wavelet_eps", 0.0))
+                if hasattr(train_step, "wavelet_band_weights"):
+                    train_step.wavelet_band_weights = None
+                more = (w.wavelet, w.levels, w.band_weights, w.eps)
             if hasattr(train_step, f"set_{key}"):
-                getattr(train_step, f"set_{key}")(ml[key], *((ml.get("fft_norm"),) if t.name == "fft" else ()))
+                getattr(train_step, f"set_{key}")(ml[key], *more)
             else:
                 # a stand-in step object without the setters receives the attributes
                 setattr(train_step, key, resolve_lambda(t.name, ml[key]))
                 if t.name == "fft":
                     train_step.fft_norm = resolve_fft_norm(ml.get("fft_norm", "backward"))
+                if t.name == "wavelet":
+                    train_step.wavelet, train_step.wavelet_levels, train_step.wavelet_eps = w.wavelet, w.levels, w.eps
+                    train_step.wavelet_band_weights = None if w.band_weights is None else list(w.band_weights)
         if "lambda_perceptual" in ml:
             p = getattr(train_step, "perceptual_loss", None)
             if p is None:

@@ -11,6 +11,7 @@
 #include "../../include/m2t_msssim.h"
 #include "../../include/m2t_vif.h"
 #include "../../include/m2t_gmsd.h"
+#include "../../include/m2t_wavelet.h"
 #include "../../include/m2t_perceptual.h"
 
 static thread_local std::string g_err;
@@ -784,6 +785,22 @@ extern "C" int m2t_gmsd_loss(m2t_plan* p, const float* hr, float weight, double 
   CK(loss_entry_seed(__func__, p, p->B <= 65535, "batch too large (B <= 65535)", workspace, &s));
   return launch_gmsd_loss(s.x, hr, p->B, 3, p->Hs, p->Ws, s.xs_img, s.xs_row, rgb_range, 1, (double)weight / divisor, s.gx, loss_out,
                           nullptr, accumulate ? 1 : 0, scratch, (hipStream_t)stream);
+}
+
+// weight * mean over the coefficients of sum_band w_band rho(c_band) on an undecimated wavelet transform (k_wavelet_loss.hip;
+// include/m2t_wavelet.h)
+extern "C" int m2t_wavelet_loss(m2t_plan* p, const float* hr, float weight, double divisor, float rgb_range, const double* lo,
+                                const double* hi, int taps, int levels, const double* band_weights, double eps, float* loss_out,
+                                int accumulate, void* scratch, void* workspace, void* stream) {
+  CK(loss_entry_args(__func__, !p || !hr || !lo || !hi || !loss_out || !scratch || !workspace, rgb_range, divisor, weight));
+  if (const char* r = wavelet_filter_refusal(lo, hi, taps, levels, band_weights, eps)) return m2t_set_error_at(M2T_ERR_ARG, __func__, r);
+  if (p->Hs < ((taps - 1) << (levels - 1)) + 1 || p->Ws < ((taps - 1) << (levels - 1)) + 1)
+    return m2t_set_error_at(M2T_ERR_ARG, __func__, "the SR height and width must be at least (taps - 1) * 2^(levels - 1) + 1");
+  LossSeed s;
+  CK(loss_entry_seed(__func__, p, p->B * 3 <= 65535, "batch too large (B * 3 <= 65535)", workspace, &s));
+  return launch_wavelet_loss(s.x, hr, p->B, 3, p->Hs, p->Ws, s.xs_img, s.xs_row, rgb_range, 1, (double)weight / divisor, lo, hi, taps,
+                             levels, band_weights, eps, nullptr, s.gx, loss_out, nullptr, accumulate ? 1 : 0, scratch,
+                             (hipStream_t)stream);
 }
 
 // weight * sum_k w_k mean(rho(F_k(sr) - F_k(hr))) on VGG19 features (k_vgg.hip, m2t_vgg.hip; include/m2t_perceptual.h).  The tower's

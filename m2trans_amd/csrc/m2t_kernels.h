@@ -394,6 +394,19 @@ bool gmsd_loss_size_supported(int H, int W);
 size_t gmsd_loss_scratch_bytes(int B, int C, int H, int W);
 int launch_gmsd_loss(const float* x, const float* y, int B, int C, int H, int W, long long xs_img, int xs_row, float R, int clamp,
                      double scale, float* gx_add, float* loss_out, double* per_image_out, int accumulate, void* scratch, hipStream_t st);
+// ---- k_wavelet_loss.hip (the wavelet-domain loss term, its gradient and the transform alone: m2t_swt2 / m2t_wavelet_loss_tensor /
+// m2t_wavelet_loss) ----------
+// The strides, gx_add, loss_out and accumulate of launch_ssim_loss; lo / hi [taps] and band_weights [3 levels + 1] (or nullptr: 1 for
+// every detail band, 0 for LL) are HOST arrays read at call time; per_band_out (or nullptr): double [3 levels + 1], the unweighted
+// band sums (0 for a band of weight 0).  swt_out != nullptr: only the transform of x, fp32 [B][C][3 levels + 1][H][W] (y may be null).
+// The refusals return the text of the first rule broken, nullptr when none is.
+const char* wavelet_shape_refusal(int B, int C, int H, int W, int levels, int taps);
+const char* wavelet_filter_refusal(const double* lo, const double* hi, int taps, int levels, const double* band_weights, double eps);
+size_t wavelet_loss_scratch_bytes(int B, int C, int H, int W, int levels, int taps);
+int launch_wavelet_loss(const float* x, const float* y, int B, int C, int H, int W, long long xs_img, int xs_row, float R, int clamp,
+                        double scale, const double* lo, const double* hi, int taps, int levels, const double* band_weights, double eps,
+                        float* swt_out, float* gx_add, float* loss_out, double* per_band_out, int accumulate, void* scratch,
+                        hipStream_t st);
 // ---- k_fft_loss.hip (the L1 loss on the coefficients of a 2-D real FFT and its gradient: m2t_fft_loss_tensor / m2t_fft_loss) ----------
 // x [B][C][H][W] with image stride xs_img, channel stride xs_img / C, row stride xs_row; y contiguous; gx_add (or nullptr) has x's strides:
 // gx_add[q] += scale * d sum(|Re D| + |Im D|) / dx[q] (through the clamp mask when clamp); loss_out = (accumulate ? loss_out : 0) + scale * sum.

@@ -692,6 +692,100 @@ class GMSDLoss(nn.Module):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# The wavelet-domain term: an L1 (or Charbonnier) on the detail bands of an undecimated 2-D wavelet transform with periodic borders
+# (the model itself moves between its scales through a Haar DWT).  Value, gradient and the transform alone are HIP
+# (m2t_wavelet_loss_tensor / m2t_swt2 of include/m2t_wavelet.h, k_wavelet_loss.hip); there is no torch fallback -- torch has no SWT.
+# ---------------------------------------------------------------------------------------------------------------
+def _wavelet_check(what, x, w, min_what="image"):
+    if int(x.shape[1]) not in (1, 3):
+        raise M2TError(f"{what}: the wavelet kernels take 1 or 3 channels, got {int(x.shape[1])}")
+    H, W = int(x.shape[2]), int(x.shape[3])
+    need = _lib.wavelet_min_side(len(w.lo), w.levels)
+    if min(H, W) < need:
+        raise M2TError(f"{what}: {min_what} {H}x{W} is too small for {len(w.lo)} taps at {w.levels} levels (height and width must be at "
+                       f"least {need}: a tap index wraps at most once)")
+
+
+def _wavelet_scratch(what, lib, xc, w):
+    B, Cn, H, W = xc.shape
+    nbytes = lib.m2t_wavelet_loss_scratch_bytes(B, Cn, H, W, w.levels, len(w.lo))
+    if nbytes == 0:
+        raise M2TError(f"{what}: no scratch size for [{B},{Cn},{H},{W}] (1 or 3 channels, B * C at most 65535)")
+    return torch.empty(nbytes, dtype=torch.uint8, device=xc.device)
+
+
+def _wavelet_call(x, y, data_range, w, want_grad, want_per_band=False):
+    """(loss [1] float32, gradient of the mean or None, band sums [3 J + 1] float64 or None) of device tensors [B,C,H,W]."""
+    from .train_step import wavelet_call_args
+    lib = _lib.load()
+    xc, yc = x.detach().contiguous().float(), y.detach().contiguous().float()
+    B, Cn, H, W = xc.shape
+    scratch = _wavelet_scratch("wavelet_loss", lib, xc, w)
+    out = torch.empty(1, dtype=torch.float32, device=xc.device)
+    grad = torch.zeros_like(xc) if want_grad else None
+    per = torch.empty(3 * w.levels + 1, dtype=torch.float64, device=xc.device) if want_per_band else None
+    with torch.cuda.device(xc.device):
+        _lib.check(lib.m2t_wavelet_loss_tensor(_lib.ptr(xc), _lib.ptr(yc), B, Cn, H, W, Cn * H * W, W, float(data_range), 0,
+                                               1.0 / (B * Cn * H * W), *wavelet_call_args(w), _lib.ptr(grad), _lib.ptr(out),
+                                               _lib.ptr(per), 0, _lib.ptr(scratch), _lib.stream_ptr()), "m2t_wavelet_loss_tensor")
+    return out, grad, per
+
+
+def wavelet_loss(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0, wavelet="haar", levels: int = 2, band_weights=None,
+                 eps: float = 0.0) -> torch.Tensor:
+    """The mean over the coefficients of ``sum_band w_band rho(c_band)`` on the undecimated (stationary, a-trous) 2-D wavelet
+    transform of ``x / data_range - y / data_range`` with periodic borders, for device tensors [B,C,H,W] with C = 1 or 3;
+    differentiable with respect to ``x`` only.  ``wavelet``: ``'haar'``, ``'db2'`` (the orthonormal filters divided by sqrt(2)) or a
+    pair ``(lo, hi)`` of 2 to 8 taps each; ``levels`` 1 .. 3; ``band_weights``: 3 levels + 1 numbers for (LH, HL, HH) of each level,
+    then LL -- by default 1 for every detail band and 0 for LL; ``rho(c) = |c|`` for ``eps = 0`` and ``sqrt(c^2 + eps^2)`` otherwise.
+    Inputs are NOT clamped to the data range.  fp64 inside the kernels, fp32 in and out."""
+    from .train_step import resolve_wavelet
+    _pair_check("wavelet_loss", x, y, device=False)
+    w = resolve_wavelet(wavelet, levels, band_weights, eps)
+    if not (math.isfinite(float(data_range)) and float(data_range) > 0.0):
+        raise M2TError(f"wavelet_loss: data_range must be a finite number > 0, got {data_range!r}")
+    _wavelet_check("wavelet_loss", x, w)
+    _pair_check("wavelet_loss", x, y, y_no_grad=True)
+    return _EagerGradFn.apply(x, lambda want_grad: _wavelet_call(x, y, data_range, w, want_grad)[:2])
+
+
+class WaveletLoss(nn.Module):
+    """``wavelet_loss`` as a module."""
+
+    def __init__(self, data_range: float = 1.0, wavelet="haar", levels: int = 2, band_weights=None, eps: float = 0.0):
+        super().__init__()
+        from .train_step import resolve_wavelet
+        w = resolve_wavelet(wavelet, levels, band_weights, eps)
+        self.data_range, self.wavelet, self.levels, self.band_weights, self.eps = float(data_range), w.wavelet, w.levels, w.band_weights, w.eps
+
+    def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        return wavelet_loss(x, y, self.data_range, self.wavelet, self.levels, self.band_weights, self.eps)
+
+
+def swt2(x: torch.Tensor, wavelet="haar", levels: int = 2) -> torch.Tensor:
+    """The undecimated 2-D wavelet transform of a device tensor [B,C,H,W] (C = 1 or 3) with periodic borders: float32
+    [B,C,3 levels + 1,H,W], the bands (LH_1, HL_1, HH_1, ..., LH_J, HL_J, HH_J, LL_J), each value one fp32 rounding of the fp64
+    coefficient.  Not differentiable."""
+    from .train_step import resolve_wavelet, wavelet_call_args
+    if x.dim() != 4:
+        raise M2TError(f"swt2: expected a [B,C,H,W] tensor, got {tuple(x.shape)}")
+    w = resolve_wavelet(wavelet, levels)
+    _wavelet_check("swt2", x, w)
+    if not x.is_cuda:
+        raise M2TError("swt2 needs a HIP device tensor (there is no host implementation)")
+    lib = _lib.load()
+    xc = x.detach().contiguous().float()
+    B, Cn, H, W = xc.shape
+    scratch = _wavelet_scratch("swt2", lib, xc, w)
+    out = torch.empty((B, Cn, 3 * w.levels + 1, H, W), dtype=torch.float32, device=xc.device)
+    lo, hi, taps, J, _, _ = wavelet_call_args(w)
+    with torch.cuda.device(xc.device):
+        _lib.check(lib.m2t_swt2(_lib.ptr(xc), B, Cn, H, W, Cn * H * W, W, lo, hi, taps, J, _lib.ptr(out), _lib.ptr(scratch),
+                                _lib.stream_ptr()), "m2t_swt2")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # The frequency-domain term: an L1 on the coefficients of rfft2 (the reference imports torch.fft, losses.py:5, and never calls it;
 # MIMO-UNet's F.l1_loss(view_as_real(rfft2(x)), view_as_real(rfft2(y)))).  Value and gradient are HIP (m2t_fft_loss_tensor of
 # include/m2t_spectral.h, k_fft_loss.hip); there is no torch fallback.

@@ -29,7 +29,7 @@ import torch
 
 from . import _lib, augment
 from ._lib import M2TError
-from .train_step import LOSS_TERMS, MORE_LOSS_TERMS, cosine_lr
+from .train_step import ALL_LOSS_TERMS, LOSS_TERMS, MORE_LOSS_TERMS, cosine_lr
 
 EVAL_SETS = {"CCA-US": "UI5", "US-CASE": "US15", "US1K_23": "US1K_23"}        # datas/utils.py:27-43: name -> benchmark/<folder>
 
@@ -95,8 +95,8 @@ class StepMeter:
 
 def meter_columns(train_step) -> List[str]:
     """The columns `fit` meters for this step object: the total loss, the pixel term, the clip term, every optional term that is on
-    (LOSS_TERMS, MORE_LOSS_TERMS, then the perceptual term) and, when the step tracks them, the gradient norm and the clip coefficient."""
-    names = ["loss", "pixel", "clip"] + [t.name for t in LOSS_TERMS + MORE_LOSS_TERMS if getattr(train_step, f"lambda_{t.name}", 0.0) > 0.0]
+    (ALL_LOSS_TERMS, then the perceptual term) and, when the step tracks them, the gradient norm and the clip coefficient."""
+    names = ["loss", "pixel", "clip"] + [t.name for t in ALL_LOSS_TERMS if getattr(train_step, f"lambda_{t.name}", 0.0) > 0.0]
     if getattr(train_step, "lambda_perceptual", 0.0) > 0.0:
         names.append("perceptual")
     if getattr(train_step, "grad_norm", None) is not None:
@@ -389,7 +389,8 @@ REFERENCE_KEYS = MODEL_KEYS + ("pretrain", "patch_size", "batch_size", "data_rep
                                "lambda_clip", "save_image", "data_path", "training_dataset", "eval_sets")
 IGNORED_KEYS = ("gpu_ids", "threads", "num_heads")
 # ... and the project's own, each handed to TrainStep unchanged (TrainStep validates them)
-TRAINSTEP_KEYS = ("pixel_loss", "pixel_loss_param", "lambda_ssim", "lambda_msssim", "lambda_fft", "fft_norm", "lambda_vif", "lambda_gmsd", "accum_steps",
+TRAINSTEP_KEYS = ("pixel_loss", "pixel_loss_param", "lambda_ssim", "lambda_msssim", "lambda_fft", "fft_norm", "lambda_vif", "lambda_gmsd", "lambda_wavelet",
+                  "wavelet", "wavelet_levels", "wavelet_band_weights", "wavelet_eps", "accum_steps",
                   "max_grad_norm", "weight_decay", "decoupled_weight_decay", "ema_decay", "skip_nonfinite", "param_groups")
 LOOP_KEYS = ("train_hr_path", "eval_folders", "preview_every", "validate_ema", "seed", "ring_rows", "track_grad_norm")
 DATA_KEYS = ("degradation",)            # a mapping of degrade.Degradation's arguments: LR synthesis beyond bicubic

@@ -30,8 +30,8 @@ L1_Charbonnier_loss): the kind only selects the per-pixel function inside the ke
 m2t_pixel_loss_deferred), so every kind runs the schedule of the L1 step -- the seed fused into the x4 tail backward, accumulation,
 the overlapped exchange and the optimizer options included.
 
-Optional loss terms (all off by default; LOSS_TERMS and MORE_LOSS_TERMS below are their table, and its order -- SSIM, MS-SSIM, FFT,
-VIF, GMSD, then the perceptual term -- is the order of the calls).  Every term that is on takes the MATERIALISED seed: the immediate pixel loss, then one
+Optional loss terms (all off by default; LOSS_TERMS, MORE_LOSS_TERMS and LATER_LOSS_TERMS below are their table, and its order -- SSIM, MS-SSIM, FFT,
+VIF, GMSD, wavelet, then the perceptual term -- is the order of the calls).  Every term that is on takes the MATERIALISED seed: the immediate pixel loss, then one
 ``m2t_<term>_loss`` call per term that adds its gradient into the seed, then the backward pass; the seed fused into the x4 tail
 backward does not apply.  An SR size a term does not take is refused on the host before anything is launched.  With a weight of 0
 nothing is allocated for the term and the step issues the calls it issued before.  Value and gradient are HIP, fp64 inside unless
@@ -56,6 +56,11 @@ said otherwise.
   ``lambda_gmsd * mean GMSD`` per image, the deviation of the gradient-magnitude similarity map of the pooled luminance of
   ``clamp(sr, 0, rgb_range)`` and ``hr`` (m2t_gmsd_loss of include/m2t_gmsd.h; SR height and width >= 2).  A distortion: there is no
   "1 -".  Exactly 0 gradient where the pooled output is locally flat (torch's autograd gives NaN there).
+* ``lambda_wavelet``, ``wavelet=``, ``wavelet_levels=``, ``wavelet_band_weights=``, ``wavelet_eps=`` (the model itself moves between
+  its scales through a Haar DWT): ``lambda_wavelet * mean`` over the coefficients of ``sum_band w_band rho(c_band)`` on the undecimated
+  (stationary) wavelet transform of ``clamp(sr, 0, rgb_range) / rgb_range - hr / rgb_range`` with periodic borders: ``'haar'``, ``'db2'``
+  or a pair of tap lists, 1 .. 3 levels, by default an L1 on every detail band and nothing on LL (m2t_wavelet_loss of
+  include/m2t_wavelet.h; SR height and width >= (taps - 1) * 2^(levels - 1) + 1).  The row sits in LATER_LOSS_TERMS, behind GMSD.
 * ``lambda_perceptual``, ``perceptual_loss=`` (PerceptualLoss of the reference's losses.py:222-270): ``lambda_perceptual * sum_k w_k
   mean(crit(F_k(sr) - F_k(hr)))`` on VGG19 features; the tower, its weights, its workspace, the criterion and the tap weights are
   those of the losses.PerceptualLoss object (m2t_vgg_loss of include/m2t_perceptual.h, bf16 compute; SR height and width >= 16).
@@ -138,7 +143,70 @@ resolve_lambda_msssim = functools.partial(resolve_lambda, "msssim")
 resolve_lambda_fft = functools.partial(resolve_lambda, "fft")
 resolve_lambda_vif = functools.partial(resolve_lambda, "vif")
 resolve_lambda_gmsd = functools.partial(resolve_lambda, "gmsd")
+resolve_lambda_wavelet = functools.partial(resolve_lambda, "wavelet")
 resolve_lambda_perceptual = functools.partial(resolve_lambda, "perceptual")
+
+_S3 = math.sqrt(3.0)
+_DB2 = ((1.0 + _S3) / 8.0, (3.0 + _S3) / 8.0, (3.0 - _S3) / 8.0, (1.0 - _S3) / 8.0)
+# the built-in analysis pairs of include/m2t_wavelet.h: the orthonormal filters divided by sqrt(2) (sum lo = 1, sum hi = 0)
+WAVELETS = {
+    "haar": ((0.5, 0.5), (0.5, -0.5)),
+    "db2": (_DB2, tuple((-1.0) ** k * _DB2[3 - k] for k in range(4))),
+}
+
+
+class Wavelet(NamedTuple):
+    """What ``resolve_wavelet`` gives: ``wavelet`` as it is kept and written to a checkpoint (a name, or the two tap lists), the
+    taps, the level count, the band weights (None = 1 for every detail band, 0 for LL) and eps."""
+    wavelet: object
+    lo: tuple
+    hi: tuple
+    levels: int
+    band_weights: Optional[tuple]
+    eps: float
+
+
+def resolve_wavelet(wavelet="haar", levels=2, band_weights=None, eps=0.0) -> Wavelet:
+    """The wavelet arguments of TrainStep / losses.wavelet_loss / losses.swt2, by the rules of include/m2t_wavelet.h; M2TError
+    naming what is wrong: the name, the tap lists, the level count, the weight vector or eps."""
+    if isinstance(wavelet, str):
+        key = wavelet.lower()
+        if key not in WAVELETS:
+            raise _lib.M2TError(f"wavelet must be one of {sorted(WAVELETS)} or a pair (lo, hi) of tap lists, got {wavelet!r}")
+        canon, (lo, hi) = key, WAVELETS[key]
+    else:
+        try:
+            lo, hi = (tuple(float(v) for v in f) for f in wavelet)
+        except (TypeError, ValueError):
+            raise _lib.M2TError(f"wavelet must be one of {sorted(WAVELETS)} or a pair (lo, hi) of tap lists, got {wavelet!r}") from None
+        if len(lo) != len(hi) or not 2 <= len(lo) <= _lib.WAVELET_MAX_TAPS or not all(math.isfinite(v) for v in lo + hi):
+            raise _lib.M2TError(f"wavelet taps: lo and hi must be two lists of equal length, 2 to {_lib.WAVELET_MAX_TAPS} finite numbers "
+                                f"each, got {wavelet!r}")
+        canon = (list(lo), list(hi))
+    if isinstance(levels, bool) or not isinstance(levels, int) or not 1 <= levels <= _lib.WAVELET_MAX_LEVELS:
+        raise _lib.M2TError(f"wavelet_levels must be an integer from 1 to {_lib.WAVELET_MAX_LEVELS}, got {levels!r}")
+    if band_weights is not None:
+        try:
+            band_weights = tuple(float(v) for v in band_weights)
+        except (TypeError, ValueError):
+            band_weights = ()
+        if len(band_weights) != 3 * levels + 1 or not all(math.isfinite(v) and v >= 0.0 for v in band_weights) or not any(band_weights):
+            raise _lib.M2TError(f"wavelet_band_weights must be {3 * levels + 1} finite numbers >= 0, not all 0 (three detail bands per level, "
+                                f"then LL), got {band_weights!r}")
+    try:
+        e = float(eps)
+    except (TypeError, ValueError):
+        e = math.nan
+    if not (math.isfinite(e) and e >= 0.0):
+        raise _lib.M2TError(f"wavelet_eps must be a finite number >= 0, got {eps!r}")
+    return Wavelet(canon, lo, hi, levels, band_weights, e)
+
+
+def wavelet_call_args(w: Wavelet) -> tuple:
+    """The wavelet arguments of the C entries (lo, hi, taps, levels, band_weights, eps): host double arrays, None for the default
+    weights."""
+    arr = lambda v: (C.c_double * len(v))(*v)
+    return arr(w.lo), arr(w.hi), len(w.lo), w.levels, None if w.band_weights is None else arr(w.band_weights), w.eps
 
 
 def resolve_fft_norm(name) -> str:
@@ -162,6 +230,12 @@ def vif_size_supported(h: int, w: int) -> bool:
 def gmsd_size_supported(h: int, w: int) -> bool:
     """The sizes the GMSD term takes (the rule of include/m2t_gmsd.h, decided on the host): min(H, W) >= 2."""
     return min(int(h), int(w)) >= _lib.GMSD_MIN_SIDE
+
+
+def wavelet_size_supported(h: int, w: int, levels: int = 1, taps: int = 2) -> bool:
+    """The sizes the wavelet term takes (the rule of include/m2t_wavelet.h, decided on the host): min(H, W) >= (taps - 1) *
+    2^(levels - 1) + 1."""
+    return min(int(h), int(w)) >= _lib.wavelet_min_side(taps, levels)
 
 
 def perceptual_size_supported(h: int, w: int) -> bool:
@@ -195,6 +269,7 @@ class LossTerm(NamedTuple):
     no_scratch: str         # the refusal of a shape the library names no scratch size for
     count: Callable         # (B, Hs, Ws) -> what the term's mean runs over on this rank (the global divisor is built from it)
     extra: Callable         # (step) -> the term's own arguments of m2t_<n>_loss, between rgb_range and the value
+    shape_args: Callable = lambda step: ()      # (step) -> what size_ok and m2t_<n>_loss_scratch_bytes take behind the sizes
 
 
 # in call order: pixel -> these (each if on) -> MORE_LOSS_TERMS (each if on) -> the perceptual term (if on) -> backward
@@ -229,7 +304,17 @@ MORE_LOSS_TERMS = (
              lambda b, hs, ws: b,                                     # images (luminance: not times 3)
              lambda step: ()),
 )
-ALL_LOSS_TERMS = LOSS_TERMS + MORE_LOSS_TERMS
+# ... and the rows that came after MORE_LOSS_TERMS was pinned to its one name
+LATER_LOSS_TERMS = (
+    LossTerm("wavelet", wavelet_size_supported,
+             "the SR image {Hs}x{Ws} is smaller than the reach of the filters (height and width must be at least (taps - 1) * "
+             "2^(levels - 1) + 1)",
+             "no scratch size for a batch of {B} SR images {Hs}x{Ws} (B * 3 <= 65535)",
+             lambda b, hs, ws: b * 3 * hs * ws,                       # coefficients of one band
+             lambda step: step._wavelet_args(),
+             lambda step: step._wavelet_shape_args()),
+)
+ALL_LOSS_TERMS = LOSS_TERMS + MORE_LOSS_TERMS + LATER_LOSS_TERMS
 _TERM = {t.name: t for t in ALL_LOSS_TERMS}
 
 
@@ -257,9 +342,11 @@ class TrainStep:
     # The state of the optional terms, off: what __init__ starts from and what a step object assembled without __init__ has.  A term
     # of LOSS_TERMS has its weight, its device [1] value and its per-shape scratch cache (None: the dict is made per object, on first
     # use or by the setter); the perceptual term keeps its value next to the PerceptualLoss object, whose workspace is its own.
-    lambda_ssim = lambda_msssim = lambda_fft = lambda_vif = lambda_gmsd = lambda_perceptual = 0.0
-    ssim_loss = msssim_loss = fft_loss = vif_loss = gmsd_loss = perceptual_loss_value = None
-    _ssim_scratch = _msssim_scratch = _fft_scratch = _vif_scratch = _gmsd_scratch = None
+    lambda_ssim = lambda_msssim = lambda_fft = lambda_vif = lambda_gmsd = lambda_wavelet = lambda_perceptual = 0.0
+    ssim_loss = msssim_loss = fft_loss = vif_loss = gmsd_loss = wavelet_loss = perceptual_loss_value = None
+    _ssim_scratch = _msssim_scratch = _fft_scratch = _vif_scratch = _gmsd_scratch = _wavelet_scratch = None
+    wavelet, wavelet_levels, wavelet_band_weights, wavelet_eps = "haar", 2, None, 0.0
+    _wavelet_call = None          # the C arguments of the wavelet term, made by the setter or on first use
     fft_norm = "backward"
     perceptual_loss = None
     groups = None
@@ -274,7 +361,8 @@ class TrainStep:
                  track_grad_norm: bool = False, pixel_loss: str = "l1", pixel_loss_param: Optional[float] = None,
                  lambda_ssim: float = 0.0, lambda_fft: float = 0.0, fft_norm: str = "backward",
                  lambda_msssim: float = 0.0, lambda_vif: float = 0.0, param_groups=None, perceptual_loss=None,
-                 lambda_perceptual: float = 0.0, lambda_gmsd: float = 0.0):
+                 lambda_perceptual: float = 0.0, lambda_gmsd: float = 0.0, lambda_wavelet: float = 0.0, wavelet="haar",
+                 wavelet_levels: int = 2, wavelet_band_weights=None, wavelet_eps: float = 0.0):
         self.model = model
         # parameter groups / frozen tensors (param_groups.py): resolved against the model's names here, on the host, fixed for the
         # life of this object.  None (the default): nothing is allocated and the step issues the calls it always issued
@@ -287,6 +375,7 @@ class TrainStep:
         self.set_lambda_fft(lambda_fft, fft_norm)
         self.set_lambda_vif(lambda_vif)
         self.set_lambda_gmsd(lambda_gmsd)
+        self.set_lambda_wavelet(lambda_wavelet, wavelet, wavelet_levels, wavelet_band_weights, wavelet_eps)
         self.perceptual_loss = perceptual_loss
         self.set_lambda_perceptual(lambda_perceptual)
         # gradient accumulation: one optimizer step consumes accum_steps equal micro-batches (forward_backward calls); the
@@ -447,6 +536,32 @@ class TrainStep:
         this); refused in the middle of an accumulation cycle."""
         self._set_lambda(_TERM["gmsd"], value)
 
+    def set_lambda_wavelet(self, value, wavelet=None, levels=None, band_weights=None, eps=None):
+        """Weight of the wavelet-domain term (0 = off) and, where given, its filter pair ('haar', 'db2' or (lo, hi)), level count
+        (1 .. 3), band weights (3 levels + 1 numbers: three detail bands per level, then LL) and eps (0 = L1, > 0 = Charbonnier);
+        None keeps what the step has.  Takes effect with the next forward_backward (checkpoint.import_checkpoint calls this);
+        refused in the middle of an accumulation cycle."""
+        _refuse_mid_cycle(self, "set_lambda_wavelet")
+        lam = resolve_lambda("wavelet", value)      # (a refused weight or argument leaves the step as it was)
+        w = resolve_wavelet(self.wavelet if wavelet is None else wavelet, self.wavelet_levels if levels is None else levels,
+                            self.wavelet_band_weights if band_weights is None else band_weights,
+                            self.wavelet_eps if eps is None else eps)
+        self.wavelet, self.wavelet_levels, self.wavelet_eps = w.wavelet, w.levels, w.eps
+        self.wavelet_band_weights = None if w.band_weights is None else list(w.band_weights)
+        self._wavelet_call = wavelet_call_args(w) if lam > 0.0 else None
+        self._wavelet_scratch = {}                  # (sized by the level count)
+        self._set_lambda(_TERM["wavelet"], lam)
+
+    def _wavelet_args(self) -> tuple:
+        if self._wavelet_call is None:
+            self._wavelet_call = wavelet_call_args(resolve_wavelet(self.wavelet, self.wavelet_levels, self.wavelet_band_weights,
+                                                                   self.wavelet_eps))
+        return self._wavelet_call
+
+    def _wavelet_shape_args(self) -> tuple:
+        a = self._wavelet_args()
+        return a[3], a[2]                           # levels, taps
+
     def _scratch_for(self, term: LossTerm, lib, hr_img):
         """The scratch of one term for this (micro-)batch shape, allocated once; an SR size the term does not take is refused here,
         on the host, before anything is launched."""
@@ -456,11 +571,12 @@ class TrainStep:
         if cache is None:
             cache = {}
             setattr(self, f"_{n}_scratch", cache)
-        key = (B, Hs, Ws)
+        more = term.shape_args(self)
+        key = (B, Hs, Ws) + more
         if key not in cache:
-            if not term.size_ok(Hs, Ws):
+            if not term.size_ok(Hs, Ws, *more):
                 raise _lib.M2TError(f"lambda_{n} > 0: " + term.too_small.format(B=B, Hs=Hs, Ws=Ws))
-            nbytes = int(getattr(lib, f"m2t_{n}_loss_scratch_bytes")(B, 3, Hs, Ws))
+            nbytes = int(getattr(lib, f"m2t_{n}_loss_scratch_bytes")(B, 3, Hs, Ws, *more))
             if nbytes == 0:
                 raise _lib.M2TError(f"lambda_{n} > 0: " + term.no_scratch.format(B=B, Hs=Hs, Ws=Ws))
             cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=hr_img.device)
@@ -534,7 +650,7 @@ class TrainStep:
 
     # -- what forward_backward iterates ------------------------------------------------------------------------------------
     def _terms_on(self, lib) -> list:
-        """The optional terms that are on, in call order -- the rows of LOSS_TERMS, of MORE_LOSS_TERMS, then the perceptual term -- each as (value,
+        """The optional terms that are on, in call order -- the rows of ALL_LOSS_TERMS, then the perceptual term -- each as (value,
         prepare, call): the term's device [1] tensor; prepare(hr_img), which refuses an SR size the term does not take and makes
         sure of its scratch before anything is launched; call(plan, hr_img, first, ws, st), its m2t_*_loss call."""
         on = [(getattr(self, f"{t.name}_loss"), functools.partial(self._scratch_for, t, lib), functools.partial(self._term_call, t, lib))
