@@ -371,13 +371,20 @@ int m2t_bicubic_resize_backward(const float* g_dst, float* g_src, int NC, int Hi
 typedef struct m2t_text m2t_text;
 int m2t_text_create(m2t_text** out, int max_seqs, int max_len /* <= 128 */, int dtype);
 void m2t_text_destroy(m2t_text* p);
-/* "workspace_bytes", "num_params", "num_param_tensors", "max_seqs", "max_len", "param:<name>", "numel:<name>" */
+/* "workspace_bytes", "num_params", "num_param_tensors", "max_seqs", "max_len", "param:<name>", "numel:<name>",
+ * "ws:<region>" (byte offset in the workspace) / "wsn:<region>" (element count at max_seqs x max_len) for the regions
+ * packed, fbias, ids, mask, X, XM, Y, QKV, AO, MH (plan element type; ids, mask int32) and pooled (float32).  After an encode
+ * the first n * len rows of X, XM, Y, QKV, AO, MH hold the LAST layer's output, attention-block LayerNorm, fc2 + residual sum,
+ * q|k|v, attention output and GELU(fc1); rows beyond n * len are not written. */
 long long m2t_text_query(const m2t_text* p, const char* key);
 const char* m2t_text_param_name(const m2t_text* p, int index);
 int m2t_text_load_weights(m2t_text* p, const float* weights, void* workspace, void* stream);
 /* ids_host, mask_host: int[n][len] in HOST memory (tokenizer output; position ids are 0..len-1 and token types 0, BertModel's
  * defaults).  The reference passes outputs['token_type_ids'] in the input_ids slot (losses.py:65): a caller that wants the
- * reference's value passes those zeros here.  -> emb [n][512] float32 on the device, unit norm. */
+ * reference's value passes those zeros here.  -> emb [n][512] float32 on the device, unit norm.
+ * A key is attended iff its mask value is non-zero; a sequence with NO attended key gets uniform weights 1 / len over its len
+ * keys (what the additive finfo.min mask of transformers gives).  An id outside [0, 28996) is M2T_ERR_ARG, before any launch
+ * or copy.  (include/m2t_text.h: the same call with BertModel's hidden_states as a second output.) */
 int m2t_text_encode(m2t_text* p, const int* ids_host, const int* mask_host, int n, int len, float* emb, void* workspace,
                     void* stream);
 

@@ -8,10 +8,12 @@
 // sample (losses.py:63-65), and because it passes token_type_ids in the input_ids slot (losses.py:65) the result
 // depends only on the caption's token COUNT -- m2trans_amd/losses.py caches one embedding per count.
 // Built from the library's GEMM (bias / bias + GELU / bias + residual epilogues) and LayerNorm launchers plus three
-// small kernels here (embedding + LayerNorm, masked multi-head attention for short sequences, pooling + projection).
+// small kernels here (embedding + LayerNorm, masked multi-head attention for short sequences, pooling + projection); the fp32
+// handle forms q | k | v in a fourth, with fp64 accumulation.
 #include "m2t_kernels.h"
 #include "m2t_layout.h"
 #include "../../include/m2t.h"
+#include "../../include/m2t_text.h"
 
 namespace {
 constexpr int TX_H = 768, TX_HEADS = 12, TX_DH = 64, TX_FF = 3072, TX_LAYERS = 12, TX_VOCAB = 28996, TX_POS = 512, TX_TYPES = 2;
@@ -47,8 +49,57 @@ __global__ void __launch_bounds__(256) text_embed_kernel(const int* __restrict__
   }
 }
 
+// fp32 handle only: QKV [M][N] = X [M][K] . W [N][K]^T + bias with fp64 ACCUMULATION (a product of two fp32 values is exact in
+// fp64) and one rounding, at the store.  The scores are the one place of the tower where an ABSOLUTE error becomes a relative one
+// (softmax), so the error of q and k is multiplied by |score|: with scores of +-300 the 6e-7 of an fp32-accumulating GEMM over
+// K = 768 came out of the layer as 2e-5 to 3e-5 (tests/test_gpu_text_stages.py, layer 1 of `max`, `edge64`, `allmasked`); the parity
+// mode pays an fp64 multiply-add here instead.  64 x 64 outputs per workgroup, 4 x 4 per thread, 16-deep stages.  N % 64 == 0, K % 16 == 0.
+__global__ void __launch_bounds__(256) text_qkv_f64acc_kernel(const float* __restrict__ A, const float* __restrict__ W,
+                                                              const float* __restrict__ bias, float* __restrict__ Y, int M, int N, int K) {
+  __shared__ float As[16][65], Ws[16][65];      // [k][row]
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
+  double acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
+  for (int k0 = 0; k0 < K; k0 += 16) {
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      const int idx = threadIdx.x + 256 * it, r = idx >> 4, c = idx & 15;
+      As[c][r] = (m0 + r < M) ? A[(long long)(m0 + r) * K + k0 + c] : 0.f;
+      Ws[c][r] = W[(long long)(n0 + r) * K + k0 + c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) {
+      double a[4], w[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { a[i] = (double)As[kk][ty + 16 * i]; w[i] = (double)Ws[kk][tx + 16 * i]; }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = fma(a[i], w[j], acc[i][j]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int m = m0 + ty + 16 * i;
+    if (m >= M) continue;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int n = n0 + tx + 16 * j;
+      Y[(long long)m * N + n] = (float)(acc[i][j] + (double)bias[n]);
+    }
+  }
+}
+
 // BertSelfAttention for short sequences (len <= 128): one workgroup per (sequence, head), one wave per query row.
 // qkv [rows][3 * 768] (q | k | v); scores = q . k / 8 + (mask ? 0 : -inf); softmax; out [rows][768]
+// A key is attended iff mask != 0.  A sequence with NO attended key gets uniform weights 1 / len over its len keys: the additive
+// finfo.min mask of transformers (and oracle/text_oracle.py) absorbs every score there, so its softmax is uniform.
 template <typename T>
 __global__ void __launch_bounds__(256) text_attn_kernel(const T* __restrict__ qkv, const int* __restrict__ mask, T* __restrict__ out, int len) {
   __shared__ float Ks[128][TX_DH + 1], Vs[128][TX_DH + 1];
@@ -77,9 +128,10 @@ __global__ void __launch_bounds__(256) text_attn_kernel(const T* __restrict__ qk
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
     float e0 = (sc[0] > -1.0e38f) ? __expf(sc[0] - mx) : 0.f, e1 = (sc[1] > -1.0e38f) ? __expf(sc[1] - mx) : 0.f;
     const float sum = wave_sum(e0 + e1);
-    const float inv = (sum > 0.f) ? 1.0f / sum : 0.f;
-    Ps[wv][lane] = e0 * inv;
-    Ps[wv][lane + 64] = e1 * inv;
+    const bool none = !(sum > 0.f);                        // no attended key: the uniform rule above
+    const float inv = none ? 0.f : 1.0f / sum, uni = 1.0f / (float)len;
+    Ps[wv][lane] = none ? (lane < len ? uni : 0.f) : e0 * inv;
+    Ps[wv][lane + 64] = none ? (lane + 64 < len ? uni : 0.f) : e1 * inv;
     __builtin_amdgcn_wave_barrier();
     float o = 0.f;
     for (int key = 0; key < len; ++key) o += Ps[wv][key] * Vs[key][lane];
@@ -165,6 +217,7 @@ extern "C" int m2t_text_create(m2t_text** out, int max_seqs, int max_len, int dt
   p->lay.ws.add("ids", rows, 4);
   p->lay.ws.add("mask", rows, 4);
   p->lay.ws.add("X", rows * TX_H, es);
+  p->lay.ws.add("XM", rows * TX_H, es);      // the attention-block LayerNorm of a layer (kept apart from X so every stage input survives)
   p->lay.ws.add("Y", rows * TX_H, es);
   p->lay.ws.add("QKV", rows * 3 * TX_H, es);
   p->lay.ws.add("AO", rows * TX_H, es);
@@ -180,7 +233,7 @@ extern "C" long long m2t_text_query(const m2t_text* p, const char* key) {
   const std::string k(key);
   if (k == "max_seqs") return p->max_seqs;
   if (k == "max_len") return p->max_len;
-  return p->lay.query(k, 0);      // (no ws: / wsn: / packed: keys on this handle)
+  return p->lay.query(k, m2t_layout::Q_WS | m2t_layout::Q_WSN);      // (no packed: keys on this handle)
 }
 extern "C" const char* m2t_text_param_name(const m2t_text* p, int i) {
   return p ? p->lay.param_name(i) : nullptr;
@@ -220,20 +273,31 @@ static int text_gemm(int dt, int emode, const void* A, int K, const void* W, voi
 // medmodel.encode_text(input_ids, attention_mask) (losses.py:65,74): ids_host / mask_host int[n][len] in HOST memory
 // (the reference passes `token_type_ids` as input_ids: the caller reproduces that by passing those values here)
 // -> emb [n][512] fp32 on the device, unit L2 norm
-extern "C" int m2t_text_encode(m2t_text* p, const int* ids_host, const int* mask_host, int n, int len, float* emb, void* workspace,
-                               void* stream) {
+// hidden_out (nullable): [13][n][len][768] of T on the device <- X after the embedding and after each layer (HF hidden_states)
+extern "C" int m2t_text_encode_ex(m2t_text* p, const int* ids_host, const int* mask_host, int n, int len, float* emb, void* workspace,
+                                  void* stream, void* hidden_out) {
   if (!p || !ids_host || !mask_host || !emb || !workspace) return m2t_set_error(M2T_ERR_ARG, "m2t_text_encode: null argument");
   if (!p->weights) return m2t_set_error(M2T_ERR_STATE, "m2t_text_encode: call m2t_text_load_weights first");
   if (n < 1 || n > p->max_seqs || len < 1 || len > p->max_len) return m2t_set_error(M2T_ERR_ARG, "m2t_text_encode: n / len out of range");
+  const int rows = n * len;
+  for (int i = 0; i < rows; ++i)      // HF raises on such an id; the kernel's clamp stays as a guard only
+    if (ids_host[i] < 0 || ids_host[i] >= TX_VOCAB) return m2t_set_error(M2T_ERR_ARG, "m2t_text_encode: input id outside [0, 28996)");
   hipStream_t st = (hipStream_t)stream;
   const int dt = p->dt;
   const float* wt = p->weights;
-  const int rows = n * len;
+  const size_t hs_bytes = (size_t)rows * TX_H * p->lay.esz;
+#define TX_KEEP_HIDDEN(i)                                                                                             \
+  do {                                                                                                                \
+    if (hidden_out) {                                                                                                 \
+      hipError_t he = hipMemcpyAsync((char*)hidden_out + (size_t)(i) * hs_bytes, X, hs_bytes, hipMemcpyDeviceToDevice, st); \
+      if (he != hipSuccess) return m2t_set_hip_error(he, __FILE__, __LINE__);                                         \
+    }                                                                                                                 \
+  } while (0)
   hipError_t e = hipMemcpyAsync(WSP("ids"), ids_host, sizeof(int) * rows, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(WSP("mask"), mask_host, sizeof(int) * rows, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);       // the host arrays may be temporaries
   if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
-  void *X = WSP("X"), *Y = WSP("Y"), *QKV = WSP("QKV"), *AO = WSP("AO"), *MH = WSP("MH");
+  void *X = WSP("X"), *XM = WSP("XM"), *Y = WSP("Y"), *QKV = WSP("QKV"), *AO = WSP("AO"), *MH = WSP("MH");
   float* pooled = (float*)WSP("pooled");
   const float* fbias = (const float*)WSP("fbias");
   const int* ids = (const int*)WSP("ids");
@@ -253,19 +317,28 @@ extern "C" int m2t_text_encode(m2t_text* p, const int* ids_host, const int* mask
                        wt + p->lay.poff.at("embeddings.position_embeddings.weight"), wt + p->lay.poff.at("embeddings.token_type_embeddings.weight"),
                        wt + p->lay.poff.at("embeddings.LayerNorm.weight"), wt + p->lay.poff.at("embeddings.LayerNorm.bias"), (bf16_t*)X, rows, len);
   M2T_LAUNCH_CHECK();
+  TX_KEEP_HIDDEN(0);
   for (int l = 0; l < TX_LAYERS; ++l) {
     const std::string b = "encoder.layer." + std::to_string(l) + ".";
-    CK(text_gemm(dt, M2T_E_BIAS, X, TX_H, p->lay.packed_ptr(workspace, b + "qkv"), QKV, 3 * TX_H, rows, fbias + p->lay.fb.at(b + "qkv_bias"), nullptr, st));
+    if (dt == M2T_F32) {      // the parity mode forms q | k | v with fp64 accumulation (see text_qkv_f64acc_kernel)
+      static_assert((3 * TX_H) % 64 == 0 && TX_H % 16 == 0, "text_qkv_f64acc_kernel tiles");
+      hipLaunchKernelGGL(text_qkv_f64acc_kernel, dim3(3 * TX_H / 64, (rows + 63) / 64), dim3(256), 0, st, (const float*)X,
+                         (const float*)p->lay.packed_ptr(workspace, b + "qkv"), fbias + p->lay.fb.at(b + "qkv_bias"), (float*)QKV, rows, 3 * TX_H, TX_H);
+      M2T_LAUNCH_CHECK();
+    } else {
+      CK(text_gemm(dt, M2T_E_BIAS, X, TX_H, p->lay.packed_ptr(workspace, b + "qkv"), QKV, 3 * TX_H, rows, fbias + p->lay.fb.at(b + "qkv_bias"), nullptr, st));
+    }
     if (dt == M2T_F32) hipLaunchKernelGGL(text_attn_kernel<float>, dim3(n * TX_HEADS), dim3(256), 0, st, (const float*)QKV, mask, (float*)AO, len);
     else hipLaunchKernelGGL(text_attn_kernel<bf16_t>, dim3(n * TX_HEADS), dim3(256), 0, st, (const bf16_t*)QKV, mask, (bf16_t*)AO, len);
     M2T_LAUNCH_CHECK();
     // BertSelfOutput: LayerNorm(dense(attention) + hidden); BertOutput: LayerNorm(dense(gelu(dense(h))) + h)
     CK(text_gemm(dt, M2T_E_BIAS_RESID, AO, TX_H, p->lay.packed_ptr(workspace, b + "o"), Y, TX_H, rows, wt + p->lay.poff.at(b + "attention.output.dense.bias"), X, st));
-    CK(launch_layernorm(dt, Y, wt + p->lay.poff.at(b + "attention.output.LayerNorm.weight"), wt + p->lay.poff.at(b + "attention.output.LayerNorm.bias"), X, rows, TX_H, st, 1e-12f));
-    CK(text_gemm(dt, M2T_E_BIAS_GELU, X, TX_H, p->lay.packed_ptr(workspace, b + "fc1"), MH, TX_FF, rows, wt + p->lay.poff.at(b + "intermediate.dense.bias"), nullptr, st));
-    CK(text_gemm(dt, M2T_E_BIAS_RESID, MH, TX_FF, p->lay.packed_ptr(workspace, b + "fc2"), Y, TX_H, rows, wt + p->lay.poff.at(b + "output.dense.bias"), X, st));
+    CK(launch_layernorm(dt, Y, wt + p->lay.poff.at(b + "attention.output.LayerNorm.weight"), wt + p->lay.poff.at(b + "attention.output.LayerNorm.bias"), XM, rows, TX_H, st, 1e-12f));
+    CK(text_gemm(dt, M2T_E_BIAS_GELU, XM, TX_H, p->lay.packed_ptr(workspace, b + "fc1"), MH, TX_FF, rows, wt + p->lay.poff.at(b + "intermediate.dense.bias"), nullptr, st));
+    CK(text_gemm(dt, M2T_E_BIAS_RESID, MH, TX_FF, p->lay.packed_ptr(workspace, b + "fc2"), Y, TX_H, rows, wt + p->lay.poff.at(b + "output.dense.bias"), XM, st));
     CK(launch_layernorm(dt, Y, wt + p->lay.poff.at(b + "output.LayerNorm.weight"), wt + p->lay.poff.at(b + "output.LayerNorm.bias"), X, rows, TX_H, st, 1e-12f));
     // hidden_states[l + 1] = X: the package pools hidden states 1, 2 and -1
+    TX_KEEP_HIDDEN(l + 1);
     if (l == 0 || l == 1 || l == TX_LAYERS - 1) {
       if (dt == M2T_F32) hipLaunchKernelGGL(text_pool_kernel<float>, dim3(n), dim3(256), 0, st, (const float*)X, pooled, len, l == 0 ? 0 : 1);
       else hipLaunchKernelGGL(text_pool_kernel<bf16_t>, dim3(n), dim3(256), 0, st, (const bf16_t*)X, pooled, len, l == 0 ? 0 : 1);
@@ -274,5 +347,10 @@ extern "C" int m2t_text_encode(m2t_text* p, const int* ids_host, const int* mask
   }
   hipLaunchKernelGGL(text_head_kernel, dim3(n), dim3(512), 0, st, pooled, wt + p->lay.poff.at("projection_head.weight"), emb);
   M2T_LAUNCH_CHECK();
+#undef TX_KEEP_HIDDEN
   return 0;
+}
+extern "C" int m2t_text_encode(m2t_text* p, const int* ids_host, const int* mask_host, int n, int len, float* emb, void* workspace,
+                               void* stream) {
+  return m2t_text_encode_ex(p, ids_host, mask_host, n, len, emb, workspace, stream, nullptr);
 }

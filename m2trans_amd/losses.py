@@ -214,8 +214,9 @@ class TextEncoder:
                                                          _lib.stream_ptr()), "m2t_text_load_weights")
         self.loaded = True
 
-    def encode(self, input_ids, attention_mask) -> torch.Tensor:
-        """input_ids, attention_mask: [n, len] integer arrays (host) -> [n,512] unit-norm embeddings on the device."""
+    def encode(self, input_ids, attention_mask, hidden_states: bool = False):
+        """input_ids, attention_mask: [n, len] integer arrays (host) -> [n,512] unit-norm embeddings on the device.
+        ``hidden_states=True`` -> ``(emb, hs)``, hs [13, n, len, 768] in the handle's element type: BertModel's hidden_states."""
         if not self.loaded:
             raise M2TError("TextEncoder: weights not loaded")
         ids = torch.as_tensor(input_ids, dtype=torch.int32).reshape(-1, torch.as_tensor(input_ids).shape[-1]).contiguous().cpu()
@@ -223,10 +224,14 @@ class TextEncoder:
         n, ln = ids.shape
         emb = torch.empty(n, 512, dtype=torch.float32, device=self.device)
         ip, mp = C.cast(ids.data_ptr(), C.POINTER(C.c_int)), C.cast(mask.data_ptr(), C.POINTER(C.c_int))
+        hs = None
+        if hidden_states:
+            hs = torch.empty(13, n, ln, 768, dtype=torch.float32 if self.dtype == _lib.F32 else torch.bfloat16, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(_lib.load().m2t_text_encode(self.handle, ip, mp, n, ln, _lib.ptr(emb), _lib.ptr(self.workspace),
-                                                   _lib.stream_ptr()), "m2t_text_encode")
-        return emb
+            _lib.check(_lib.load().m2t_text_encode_ex(self.handle, ip, mp, n, ln, _lib.ptr(emb), _lib.ptr(self.workspace),
+                                                      _lib.stream_ptr(), _lib.ptr(hs) if hidden_states else None),
+                       "m2t_text_encode")
+        return (emb, hs) if hidden_states else emb
 
     def __del__(self):
         try:

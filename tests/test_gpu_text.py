@@ -34,6 +34,25 @@ def test_text_encode_matches_oracle(dtype, tol):
     assert float((got - want).norm(dim=1).max()) < tol, float((got - want).norm(dim=1).max())
 
 
+def test_text_encode_refuses_bad_arguments():
+    """M2T_ERR_ARG for n / len beyond the handle and for an input id outside [0, 28996) (transformers raises there; a clamp would
+    read another token's row) -- before any launch or copy: the workspace keeps the bytes it had."""
+    from m2trans_amd._lib import M2TError
+    enc = _encoder("fp32", T.closed_form_text_params(VOCAB))
+    start = enc.query("ws:ids")
+    enc.workspace[start:].fill_(0xA5)
+    ok = torch.ones(2, 5, dtype=torch.long)
+    for ids, mask in ((torch.ones(5, 5, dtype=torch.long), torch.ones(5, 5, dtype=torch.long)),          # n > max_seqs
+                      (torch.ones(1, 33, dtype=torch.long), torch.ones(1, 33, dtype=torch.long)),        # len > max_len
+                      (torch.tensor([[1, 2, 28996, 3, 4], [1, 2, 3, 4, 5]]), ok),
+                      (torch.tensor([[1, 2, 3, 4, 5], [1, 2, 3, 4, -1]]), ok)):
+        with pytest.raises(M2TError, match="status"):
+            enc.encode(ids, mask)
+    torch.cuda.synchronize()
+    assert bool((enc.workspace[start:] == 0xA5).all())
+    assert enc.encode(torch.tensor([[1, 2, 28995, 3, 0]]), torch.ones(1, 5, dtype=torch.long)).shape == (1, 512)
+
+
 def test_semantic_loss_uses_the_token_count_quirk_and_checkpoint_prefixes():
     """losses.py:64-65: token_type_ids in the input_ids slot -> one feature per token count; weights arrive under the
     MedCLIP checkpoint's prefixes (text_model.model.*, text_model.projection_head.weight, pooler ignored)."""

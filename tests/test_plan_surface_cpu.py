@@ -144,21 +144,55 @@ def walk(lib):
     lib.m2t_swin_destroy(h)
     assert lib.m2t_text_create(C.byref(h), 8, 77, 1) == 0
     inv, names = _encoder_inventory(lib.m2t_text_query, lib.m2t_text_param_name, h,
-                                    ("packed", "fbias", "ids", "mask", "X", "Y", "QKV", "AO", "MH", "pooled"),
-                                    ("encoder.layer.0.qkv", "encoder.layer.11.fc2"), ("max_seqs", "max_len", "max_images"))
+                                    TEXT_WS, ("encoder.layer.0.qkv", "encoder.layer.11.fc2"), ("max_seqs", "max_len", "max_images"))
     out["text_inventory"] = np.asarray(inv, dtype=np.int64)
     out["text_names"] = np.frombuffer("\n".join(names).encode(), dtype=np.uint8)
     lib.m2t_text_destroy(h)
     return out
 
 
+TEXT_WS = ("packed", "fbias", "ids", "mask", "X", "Y", "QKV", "AO", "MH", "pooled")      # the names walk() asks the text handle for
+
+
+def text_workspace_layout(max_seqs, max_len, es):
+    """{region: (byte offset, element count)}, total bytes of the m2t_text workspace, restated from the geometry (BERT-base: 12
+    layers of q|k|v, o, fc1, fc2 packs and a fused q|k|v bias) and the rule of m2t_layout.h (each region aligned to 256 bytes):
+    since the stage gate of the text tower the handle answers ws: / wsn: (the recorded table, older, holds -1 there) and owns one
+    more region, XM."""
+    rows, hid, ff = max_seqs * max_len, 768, 3072
+    sizes = (("packed", 12 * (4 * hid * hid + 2 * ff * hid), es), ("fbias", 12 * 3 * hid, 4), ("ids", rows, 4), ("mask", rows, 4),
+             ("X", rows * hid, es), ("XM", rows * hid, es), ("Y", rows * hid, es), ("QKV", rows * 3 * hid, es), ("AO", rows * hid, es),
+             ("MH", rows * ff, es), ("pooled", max_seqs * hid, 4))
+    out, off = {}, 0
+    for name, n, e in sizes:
+        off = (off + 255) & ~255
+        out[name] = (off, n)
+        off += n * e
+    return out, (off + 255) & ~255
+
+
 def test_plan_query_surface_equals_the_recorded_table():
     from m2trans_amd import _lib
-    got = walk(load_library(_lib.LIB_PATH))
+    lib = load_library(_lib.LIB_PATH)
+    got = walk(lib)
     assert got["settings"].shape[0] > 30000, "truncated walk"
-    want = np.load(GOLDEN)
-    assert sorted(want.files) == sorted(got)
-    for name in want.files:
+    want = {k: v for k, v in np.load(GOLDEN).items()}
+    assert sorted(want) == sorted(got)
+    # text handle (8, 77, bf16): cell 0 (workspace_bytes) and the ws: / wsn: cells are checked against the restated layout, every
+    # other cell against the recorded table
+    lay, total = text_workspace_layout(8, 77, 2)
+    first = 8 + 2 * (int(want["text_inventory"][2]) + 1)
+    cells = [0] + list(range(first, first + 2 * len(TEXT_WS)))
+    assert [int(v) for v in got["text_inventory"][cells]] == [total] + [v for nm in TEXT_WS for v in lay[nm]]
+    assert all(int(v) == -1 for v in want["text_inventory"][cells[1:]])
+    got["text_inventory"] = got["text_inventory"].copy()
+    got["text_inventory"][cells] = want["text_inventory"][cells]
+    h = C.c_void_p()
+    assert lib.m2t_text_create(C.byref(h), 8, 77, 1) == 0
+    assert (lib.m2t_text_query(h, b"ws:XM"), lib.m2t_text_query(h, b"wsn:XM")) == lay["XM"]
+    assert lib.m2t_text_query(h, b"ws:no_such_tensor") == -1 and lib.m2t_text_query(h, b"packed:encoder.layer.0.qkv") == -1
+    lib.m2t_text_destroy(h)
+    for name in want:
         assert got[name].dtype == want[name].dtype and got[name].shape == want[name].shape, name
         bad = np.argwhere(got[name] != want[name])
         assert bad.size == 0, f"{name}: {len(bad)} cells differ, first at {bad[0].tolist()}: got {got[name][tuple(bad[0])]}, recorded {want[name][tuple(bad[0])]}"
