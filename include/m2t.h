@@ -319,11 +319,16 @@ int m2t_window_attention_bwd(int dtype, const void* qkv, const float* rel_h, con
  * through the last random crop (a paste) or, for N = 1, through the adjoint of the bicubic resize.  The tower is frozen:
  * data gradients only.  Weights: ONE flat float32 buffer in the order reported
  * by m2t_swin_param_name() (HF swin-tiny checkpoint names of transformers 4.24 + "projection_head.weight"
- * [512,768], the MedCLIP vision projection). */
+ * [512,768], the MedCLIP vision projection).  (include/m2t_swin.h: the encode and backward calls with every stage as an
+ * extra output.) */
 typedef struct m2t_swin m2t_swin;
 int m2t_swin_create(m2t_swin** out, int max_images, int dtype);
 void m2t_swin_destroy(m2t_swin* p);
-/* "workspace_bytes", "num_params", "num_param_tensors", "param:<name>", "numel:<name>" */
+/* "workspace_bytes", "num_params", "num_param_tensors", "max_images", "param:<name>", "numel:<name>"; "ws:<region>" /
+ * "wsn:<region>": byte offset / element count of a workspace region (packed, fbias, crops, A0, X, Hn, QKV, AO, MH, emb);
+ * "gws:<region>" / "gwsn:<region>": the same for the grad workspace in the layout of the last
+ * m2t_swin_grad_workspace_bytes(p, n_grad), -1 before any (stash regions: e0, s<stage>b<block>.xin | .qkv | .xmid | .gder,
+ * m0..m2, xf, hnf; scratch: gR, gF, gT, gC, gQ, gA, MD; everything before gR: transposed weights).  Unknown key: -1. */
 long long m2t_swin_query(const m2t_swin* p, const char* key);
 const char* m2t_swin_param_name(const m2t_swin* p, int index);
 /* once per weight set: converts / fuses the frozen weights into the workspace */

@@ -1,6 +1,6 @@
 """ctypes binding of libm2t.so (include/m2t.h, include/m2t_spectral.h, include/m2t_resize.h, include/m2t_msssim.h,
 include/m2t_vif.h, include/m2t_groups.h, include/m2t_perceptual.h, include/m2t_rlutrans.h, include/m2t_infer.h, include/m2t_train.h,
-include/m2t_tiles.h, include/m2t_gmsd.h, include/m2t_degrade.h, include/m2t_jpeg.h, include/m2t_wavelet.h, include/m2t_text.h).
+include/m2t_tiles.h, include/m2t_gmsd.h, include/m2t_degrade.h, include/m2t_jpeg.h, include/m2t_wavelet.h, include/m2t_text.h, include/m2t_swin.h).
 
 The product path has NO fallback: if the HIP library is missing, or a call fails, this
 module raises.  Build it with ``python -m m2trans_amd.build`` (hipcc, gfx950).
@@ -254,6 +254,13 @@ TEXT_SIGNATURES = {
     "m2t_text_encode_ex": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), _i, _i, _vp, _vp, _vp, _vp]),
 }
 
+# the seventeenth header, include/m2t_swin.h (the image tower's encode / backward with every stage as an extra output), bound on the
+# same library; must list every symbol that header declares.  The sixteen tables above stay as they are.
+SWIN_SIGNATURES = {
+    "m2t_swin_encode_ex": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, C.POINTER(_i), _i, _vp, _vp, _vp, _vp]),
+    "m2t_swin_backward_ex": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -279,7 +286,7 @@ def load():
             + list(MSSSIM_SIGNATURES.items()) + list(VIF_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()) \
             + list(PERCEPTUAL_SIGNATURES.items()) + list(RLUTRANS_SIGNATURES.items()) + list(INFER_SIGNATURES.items()) \
             + list(TRAIN_SIGNATURES.items()) + list(TILES_SIGNATURES.items()) + list(GMSD_SIGNATURES.items()) + list(DEGRADE_SIGNATURES.items()) \
-            + list(JPEG_SIGNATURES.items()) + list(WAVELET_SIGNATURES.items()) + list(TEXT_SIGNATURES.items()):
+            + list(JPEG_SIGNATURES.items()) + list(WAVELET_SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(SWIN_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

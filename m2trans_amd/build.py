@@ -24,7 +24,7 @@ HEADERS = ["m2t_common.h", "m2t_kernels.h", "m2t_gemm_load.h", "m2t_haar.h", "m2
            os.path.join("..", "..", "include", "m2t_train.h"), os.path.join("..", "..", "include", "m2t_tiles.h"),
            os.path.join("..", "..", "include", "m2t_gmsd.h"), os.path.join("..", "..", "include", "m2t_degrade.h"),
            os.path.join("..", "..", "include", "m2t_jpeg.h"), os.path.join("..", "..", "include", "m2t_wavelet.h"),
-           os.path.join("..", "..", "include", "m2t_text.h")]
+           os.path.join("..", "..", "include", "m2t_text.h"), os.path.join("..", "..", "include", "m2t_swin.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-ffp-contract=off", "-fvisibility=hidden",
          "-Rpass-analysis=kernel-resource-usage"]

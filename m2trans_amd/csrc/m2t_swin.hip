@@ -7,6 +7,7 @@
 #include "m2t_layout.h"
 #include <cstring>
 #include "../../include/m2t.h"
+#include "../../include/m2t_swin.h"
 
 namespace {
 const int DEPTHS[4] = {2, 2, 6, 2};
@@ -110,7 +111,15 @@ extern "C" long long m2t_swin_query(const m2t_swin* p, const char* key) {
   if (!p || !key) return -1;
   const std::string k(key);
   if (k == "max_images") return p->max_images;
-  return p->lay.query(k, m2t_layout::Q_WS);
+  // grad workspace, in the layout of the last m2t_swin_grad_workspace_bytes(p, n_grad): byte offset / element count
+  const bool goff = k.rfind("gws:", 0) == 0, gcnt = k.rfind("gwsn:", 0) == 0;
+  if (goff || gcnt) {
+    if (p->gws_n < 1) return -1;
+    auto it = p->gws.t.find(k.substr(goff ? 4 : 5));
+    if (it == p->gws.t.end()) return -1;
+    return goff ? (long long)it->second.off : (long long)it->second.n;
+  }
+  return p->lay.query(k, m2t_layout::Q_WS | m2t_layout::Q_WSN);
 }
 // i-th parameter name in flat order (so the Python side never duplicates the inventory)
 extern "C" const char* m2t_swin_param_name(const m2t_swin* p, int i) {
@@ -166,16 +175,22 @@ static int swin_gemm(int dt, int emode, const void* A, int K, const void* W, voi
 // (source index, y0, x0) -> emb [n][512] (unit norm, fp32, device)
 extern "C" int m2t_swin_encode(m2t_swin* p, const float* src, int n_src, int Hs, int Ws, const int* crops_host, int n,
                                float* emb, void* workspace, void* stream) {
-  return m2t_swin_encode_pair(p, src, n_src, nullptr, 0, Hs, Ws, crops_host, n, emb, workspace, stream);
+  return m2t_swin_encode_ex(p, src, n_src, nullptr, 0, Hs, Ws, crops_host, n, emb, workspace, stream, nullptr);
 }
 
 // the same with the source images in TWO tensors (indices 0 .. n_a - 1 in src_a, n_a .. n_a + n_b - 1 in src_b): the SR and
 // HR batches of SemanticLoss.batch are encoded in one pass without concatenating them first
 static int encode_impl(m2t_swin* p, const float* src, int n_a, const float* src_b, int n_b, int Hs, int Ws, const int* crops_host, int n,
-                       float* emb, void* workspace, int n_grad, void* grad_ws, hipStream_t st);
+                       float* emb, void* workspace, int n_grad, void* grad_ws, void* hidden_out, hipStream_t st);
 extern "C" int m2t_swin_encode_pair(m2t_swin* p, const float* src, int n_a, const float* src_b, int n_b, int Hs, int Ws,
                                     const int* crops_host, int n, float* emb, void* workspace, void* stream) {
-  return encode_impl(p, src, n_a, src_b, n_b, Hs, Ws, crops_host, n, emb, workspace, 0, nullptr, (hipStream_t)stream);
+  return m2t_swin_encode_ex(p, src, n_a, src_b, n_b, Hs, Ws, crops_host, n, emb, workspace, stream, nullptr);
+}
+// m2t_swin_encode_pair that also copies the stage inputs of all n crops to hidden_out (include/m2t_swin.h has the order); the copies
+// are device-to-device on the call's stream between the launches, which are those of the plain call
+extern "C" int m2t_swin_encode_ex(m2t_swin* p, const float* src, int n_a, const float* src_b, int n_b, int Hs, int Ws,
+                                  const int* crops_host, int n, float* emb, void* workspace, void* stream, void* hidden_out) {
+  return encode_impl(p, src, n_a, src_b, n_b, Hs, Ws, crops_host, n, emb, workspace, 0, nullptr, hidden_out, (hipStream_t)stream);
 }
 
 // ---- opt-in data gradient: grad workspace layout -------------------------------------------------------------------------
@@ -257,11 +272,11 @@ extern "C" int m2t_swin_encode_grad(m2t_swin* p, const float* src_a, int n_a, co
                                     const int* crops_host, int n, int n_grad, float* emb, void* workspace, void* grad_ws, void* stream) {
   if (!p || !grad_ws) return m2t_set_error(M2T_ERR_ARG, "m2t_swin_encode_grad: null");
   if (n_grad < 1 || n_grad > n) return m2t_set_error(M2T_ERR_ARG, "m2t_swin_encode_grad: n_grad must be in [1, n]");
-  return encode_impl(p, src_a, n_a, src_b, n_b, Hs, Ws, crops_host, n, emb, workspace, n_grad, grad_ws, (hipStream_t)stream);
+  return encode_impl(p, src_a, n_a, src_b, n_b, Hs, Ws, crops_host, n, emb, workspace, n_grad, grad_ws, nullptr, (hipStream_t)stream);
 }
 
 static int encode_impl(m2t_swin* p, const float* src, int n_a, const float* src_b, int n_b, int Hs, int Ws, const int* crops_host, int n,
-                       float* emb, void* workspace, int n_grad, void* grad_ws, hipStream_t st) {
+                       float* emb, void* workspace, int n_grad, void* grad_ws, void* hidden_out, hipStream_t st) {
   const int n_src = n_a + n_b;
   if (!p || !src || !crops_host || !emb || !workspace || n_a < 1 || n_b < 0 || (n_b > 0 && !src_b))
     return m2t_set_error(M2T_ERR_ARG, "m2t_swin_encode: null / bad source counts");
@@ -280,7 +295,15 @@ static int encode_impl(m2t_swin* p, const float* src, int n_a, const float* src_
     p->grad_ws = grad_ws;
   }
   // grad mode: the first n_grad crops' copy of a token tensor (contiguous rows at the front of the batch) into the stash
+  // hidden_out (m2t_swin_encode_ex): all n crops' copy, the tensors one after the other in the order of the calls below
+  size_t hcur = 0;
   auto stash = [&](const void* from, const std::string& to, size_t elems_per_crop) -> int {
+    if (hidden_out) {
+      const size_t nb = elems_per_crop * n * p->lay.esz;
+      const hipError_t e1 = hipMemcpyAsync((char*)hidden_out + hcur, from, nb, hipMemcpyDeviceToDevice, st);
+      if (e1 != hipSuccess) return m2t_set_hip_error(e1, __FILE__, __LINE__);
+      hcur += nb;
+    }
     if (!G) return 0;
     const hipError_t e2 = hipMemcpyAsync(GWP(to), from, elems_per_crop * n_grad * p->lay.esz, hipMemcpyDeviceToDevice, st);
     return e2 == hipSuccess ? 0 : m2t_set_hip_error(e2, __FILE__, __LINE__);
@@ -383,6 +406,12 @@ static int swin_gemm_g(int dt, int emode, const void* A, int K, const void* W, v
 // vector-Jacobian product of encode_image for the n_grad crops stashed by the last m2t_swin_encode_grad:
 // g_emb [n_grad,512] -> g_crops [n_grad,3,224,224] fp32 (overwritten)
 extern "C" int m2t_swin_backward(m2t_swin* p, const float* g_emb, int n_grad, float* g_crops, void* workspace, void* grad_ws, void* stream) {
+  return m2t_swin_backward_ex(p, g_emb, n_grad, g_crops, workspace, grad_ws, stream, nullptr);
+}
+// the same, with the fp32 residual-stream gradient copied to grad_taps after every step that completes it (include/m2t.h has
+// the order); device-to-device copies on the call's stream between the launches of the plain call
+extern "C" int m2t_swin_backward_ex(m2t_swin* p, const float* g_emb, int n_grad, float* g_crops, void* workspace, void* grad_ws, void* stream,
+                                    float* grad_taps) {
   if (!p || !g_emb || !g_crops || !workspace || !grad_ws) return m2t_set_error(M2T_ERR_ARG, "m2t_swin_backward: null");
   if (!p->weights) return m2t_set_error(M2T_ERR_STATE, "m2t_swin_backward: call m2t_swin_load_weights first");
   if (p->grad_n < 1 || p->grad_n != n_grad || p->grad_ws != grad_ws || p->gws_packed != grad_ws)
@@ -394,8 +423,16 @@ extern "C" int m2t_swin_backward(m2t_swin* p, const float* g_emb, int n_grad, fl
   float *gR = (float*)GWP("gR"), *gF = (float*)GWP("gF");
   void *gT = GWP("gT"), *gC = GWP("gC"), *gQ = GWP("gQ"), *gA = GWP("gA");
   const int ng = n_grad;
+  size_t tcur = 0;
+  auto tap = [&](const float* from, size_t elems) -> int {
+    if (!grad_taps) return 0;
+    const hipError_t e1 = hipMemcpyAsync(grad_taps + tcur, from, elems * sizeof(float), hipMemcpyDeviceToDevice, st);
+    tcur += elems;
+    return e1 == hipSuccess ? 0 : m2t_set_hip_error(e1, __FILE__, __LINE__);
+  };
   CK(launch_swin_head_bwd(dt, GWP("hnf"), wt + p->lay.poff.at("projection_head.weight"), g_emb, gC, ng, st));
   CK(launch_layernorm_bwd(dt, GWP("xf"), gC, wt + p->lay.poff.at("layernorm.weight"), nullptr, gR, gT, (long long)ng * 49, 768, st));
+  CK(tap(gR, (size_t)ng * 49 * 768));
   for (int s = 3; s >= 0; --s) {
     const int H = 56 >> s, C = 96 << s;
     const long long M = (long long)ng * H * H;
@@ -407,12 +444,14 @@ extern "C" int m2t_swin_backward(m2t_swin* p, const float* g_emb, int n_grad, fl
       CK(swin_gemm_g(dt, M2T_E_GELU_GRAD, gT, C, GWP(b + "fc2T"), gA, 4 * C, M, GWP(sb + "gder"), st));
       CK(swin_gemm_g(dt, M2T_E_PLAIN, gA, 4 * C, GWP(b + "fc1T"), gC, C, M, nullptr, st));
       CK(launch_layernorm_bwd(dt, GWP(sb + "xmid"), gC, wt + p->lay.poff.at(b + "layernorm_after.weight"), gR, gR, gT, M, C, st));
+      CK(tap(gR, (size_t)M * C));
       // attention: o_proj^T, window attention, qkv^T, LayerNorm backward into the residual stream
       CK(swin_gemm_g(dt, M2T_E_PLAIN, gT, C, GWP(b + "oT"), gC, C, M, nullptr, st));
       CK(launch_swin_attn_bwd(dt, GWP(sb + "qkv"), wt + p->lay.poff.at(b + "attention.self.relative_position_bias_table"), gC, gQ, ng, H, H, C,
                                HEADS[s], shift, st));
       CK(swin_gemm_g(dt, M2T_E_PLAIN, gQ, 3 * C, GWP(b + "qkvT"), gC, C, M, nullptr, st));
       CK(launch_layernorm_bwd(dt, GWP(sb + "xin"), gC, wt + p->lay.poff.at(b + "layernorm_before.weight"), gR, gR, gT, M, C, st));
+      CK(tap(gR, (size_t)M * C));
     }
     if (s > 0) {
       // patch merging of stage s - 1 (C' = C / 2 channels at 2H x 2H): reduction^T, LayerNorm backward (4 C'), scatter
@@ -420,11 +459,13 @@ extern "C" int m2t_swin_backward(m2t_swin* p, const float* g_emb, int n_grad, fl
       CK(swin_gemm_g(dt, M2T_E_PLAIN, gT, C, GWP(d + "redT"), gC, 2 * C, M, nullptr, st));
       CK(launch_layernorm_bwd(dt, GWP("m" + std::to_string(s - 1)), gC, wt + p->lay.poff.at(d + "norm.weight"), nullptr, gF, nullptr, M, 2 * C, st));
       CK(launch_swin_merge_scatter(dt, gF, gR, gT, ng, 2 * H, 2 * H, C / 2, st));
+      CK(tap(gR, (size_t)M * 2 * C));
     }
   }
   // embedding LayerNorm (its incoming gradient is the fp32 residual stream) and the patch projection^T + patchify adjoint, fp32
   CK(launch_layernorm_bwd(dt, GWP("e0"), nullptr, wt + p->lay.poff.at("embeddings.norm.weight"), nullptr, gF, nullptr, (long long)ng * 3136, 96, st,
                            1e-5f, gR));
+  CK(tap(gF, (size_t)ng * 3136 * 96));
   CK(launch_swin_embed_bwd(gF, wt + p->lay.poff.at("embeddings.patch_embeddings.projection.weight"), g_crops, ng, st));
   return 0;
 }

@@ -89,14 +89,69 @@ class SwinEncoder:
                                                          _lib.stream_ptr()), "m2t_swin_load_weights")
         self.loaded = True
 
-    def encode(self, src: torch.Tensor, crops: Sequence[Sequence[int]]) -> torch.Tensor:
-        """src [n_src,3,Hs,Ws] fp32 on the device; crops [(src index, row0, col0)] -> [n,512] unit-norm embeddings."""
+    DEPTHS = (2, 2, 6, 2)
+
+    @classmethod
+    def hidden_layout(cls, n: int):
+        """[(name, element offset, shape)] of ``hidden_out`` of m2t_swin_encode_ex for n crops (include/m2t_swin.h)"""
+        out, off = [], 0
+
+        def add(name, rows, width):
+            nonlocal off
+            out.append((name, off, (n, rows, width)))
+            off += n * rows * width
+        add("e0", 3136, 96)
+        for s, depth in enumerate(cls.DEPTHS):
+            t, c = 3136 >> (2 * s), 96 << s
+            for j in range(depth):
+                add(f"s{s}b{j}.xin", t, c)
+                add(f"s{s}b{j}.qkv", t, 3 * c)
+                add(f"s{s}b{j}.xmid", t, c)
+            if s < 3:
+                add(f"m{s}", t // 4, 4 * c)
+        add("xf", 49, 768)
+        add("hnf", 49, 768)
+        return out
+
+    @classmethod
+    def tap_layout(cls, n_grad: int):
+        """[(name, float offset, shape)] of ``grad_taps`` of m2t_swin_backward_ex for n_grad crops (include/m2t_swin.h)"""
+        out, off = [], 0
+
+        def add(name, rows, width):
+            nonlocal off
+            out.append((name, off, (n_grad, rows, width)))
+            off += n_grad * rows * width
+        add("xf", 49, 768)
+        for s in (3, 2, 1, 0):
+            t, c = 3136 >> (2 * s), 96 << s
+            for j in reversed(range(cls.DEPTHS[s])):
+                add(f"s{s}b{j}.xmid", t, c)
+                add(f"s{s}b{j}.xin", t, c)
+            if s > 0:
+                add(f"s{s - 1}.out", 4 * t, c // 2)
+        add("e0", 3136, 96)
+        return out
+
+    def encode(self, src: torch.Tensor, crops: Sequence[Sequence[int]], hidden_states: bool = False):
+        """src [n_src,3,Hs,Ws] fp32 on the device; crops [(src index, row0, col0)] -> [n,512] unit-norm embeddings.
+        hidden_states=True: -> (emb, {name: tensor [n, rows, width]} in the compute type, the names of ``hidden_layout``);
+        the embedding is the plain call's, bit for bit (m2t_swin_encode_ex)."""
         if not self.loaded:
             raise M2TError("SwinEncoder: weights not loaded")
         src = src.contiguous().float()
         n = len(crops)
         arr = (C.c_int * (3 * n))(*[int(v) for c in crops for v in c])
         emb = torch.empty(n, 512, dtype=torch.float32, device=self.device)
+        if hidden_states:
+            lay = self.hidden_layout(n)
+            total = lay[-1][1] + math.prod(lay[-1][2])
+            hid = torch.empty(total, dtype=torch.float32 if self.dtype == _lib.F32 else torch.bfloat16, device=self.device)
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.load().m2t_swin_encode_ex(self.handle, _lib.ptr(src), src.shape[0], None, 0, src.shape[2], src.shape[3], arr,
+                                                          n, _lib.ptr(emb), _lib.ptr(self.workspace), _lib.stream_ptr(), _lib.ptr(hid)),
+                           "m2t_swin_encode_ex")
+            return emb, {k: hid[o:o + math.prod(shp)].view(shp) for k, o, shp in lay}
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().m2t_swin_encode(self.handle, _lib.ptr(src), src.shape[0], src.shape[2], src.shape[3], arr, n,
                                                    _lib.ptr(emb), _lib.ptr(self.workspace), _lib.stream_ptr()), "m2t_swin_encode")
@@ -142,10 +197,20 @@ class SwinEncoder:
                                                 _lib.ptr(self.grad_workspace), _lib.stream_ptr()), "m2t_swin_encode_grad")
         return emb
 
-    def backward(self, g_emb: torch.Tensor, n_grad: int) -> torch.Tensor:
-        """vector-Jacobian product of the last ``encode_grad``: g_emb [n_grad,512] -> g_crops [n_grad,3,224,224] fp32"""
+    def backward(self, g_emb: torch.Tensor, n_grad: int, taps: bool = False):
+        """vector-Jacobian product of the last ``encode_grad``: g_emb [n_grad,512] -> g_crops [n_grad,3,224,224] fp32.
+        taps=True: -> (g_crops, {name: fp32 residual-stream gradient [n_grad, rows, width]}, the names of ``tap_layout``);
+        g_crops is the plain call's, bit for bit (m2t_swin_backward_ex)."""
         g_emb = g_emb.contiguous().float()
         g = torch.empty(n_grad, 3, 224, 224, dtype=torch.float32, device=self.device)
+        if taps:
+            lay = self.tap_layout(n_grad)
+            buf = torch.empty(lay[-1][1] + math.prod(lay[-1][2]), dtype=torch.float32, device=self.device)
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.load().m2t_swin_backward_ex(self.handle, _lib.ptr(g_emb), n_grad, _lib.ptr(g), _lib.ptr(self.workspace),
+                                                            _lib.ptr(self.grad_workspace), _lib.stream_ptr(), _lib.ptr(buf)),
+                           "m2t_swin_backward_ex")
+            return g, {k: buf[o:o + math.prod(shp)].view(shp) for k, o, shp in lay}
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().m2t_swin_backward(self.handle, _lib.ptr(g_emb), n_grad, _lib.ptr(g), _lib.ptr(self.workspace),
                                                      _lib.ptr(self.grad_workspace), _lib.stream_ptr()), "m2t_swin_backward")

@@ -136,7 +136,7 @@ def walk(lib):
     h = C.c_void_p()
     assert lib.m2t_swin_create(C.byref(h), 8, 1) == 0
     inv, names = _encoder_inventory(lib.m2t_swin_query, lib.m2t_swin_param_name, h,
-                                    ("packed", "fbias", "crops", "A0", "X", "Hn", "QKV", "AO", "MH", "emb"),
+                                    SWIN_WS,
                                     ("pe", "encoder.layers.0.blocks.0.qkv", "encoder.layers.0.blocks.1.fc1F", "encoder.layers.2.downsample.red"),
                                     ("max_images",))
     out["swin_inventory"] = np.asarray(inv, dtype=np.int64)
@@ -151,6 +151,7 @@ def walk(lib):
     return out
 
 
+SWIN_WS = ("packed", "fbias", "crops", "A0", "X", "Hn", "QKV", "AO", "MH", "emb")               # the names walk() asks the swin handle for
 TEXT_WS = ("packed", "fbias", "ids", "mask", "X", "Y", "QKV", "AO", "MH", "pooled")      # the names walk() asks the text handle for
 
 
@@ -192,6 +193,21 @@ def test_plan_query_surface_equals_the_recorded_table():
     assert (lib.m2t_text_query(h, b"ws:XM"), lib.m2t_text_query(h, b"wsn:XM")) == lay["XM"]
     assert lib.m2t_text_query(h, b"ws:no_such_tensor") == -1 and lib.m2t_text_query(h, b"packed:encoder.layer.0.qkv") == -1
     lib.m2t_text_destroy(h)
+    # swin handle (8, bf16): since the stage gate of the image tower it answers wsn: (the recorded table, older, holds -1 there).
+    # Those ten cells are checked against the geometry and against the recorded ws: offsets (each region ends, rounded up to 256
+    # bytes, where the next begins), every other cell against the recorded table
+    inv, rec = got["swin_inventory"], want["swin_inventory"]
+    first = 6 + 2 * (int(rec[2]) + 1)
+    ws_cells, wsn_cells = list(range(first, first + 2 * len(SWIN_WS), 2)), list(range(first + 1, first + 2 * len(SWIN_WS), 2))
+    assert all(int(rec[c]) == -1 for c in wsn_cells) and int(inv[first + 2 * len(SWIN_WS) + 1]) == -1        # wsn:no_such_tensor
+    tok = 8 * 3136 * 96
+    assert [int(inv[c]) for c in wsn_cells[2:]] == [8 * 3, tok // 2, tok, tok, 3 * tok, tok, 4 * tok, 8 * 512]
+    ends = [int(rec[c]) for c in ws_cells[1:]] + [int(rec[0])]
+    for c_off, c_n, nm, end in zip(ws_cells, wsn_cells, SWIN_WS, ends):
+        es = 4 if nm in ("fbias", "crops", "emb") else 2
+        assert (int(rec[c_off]) + int(inv[c_n]) * es + 255) // 256 * 256 == end, nm
+    got["swin_inventory"] = inv.copy()
+    got["swin_inventory"][wsn_cells] = rec[wsn_cells]
     for name in want:
         assert got[name].dtype == want[name].dtype and got[name].shape == want[name].shape, name
         bad = np.argwhere(got[name] != want[name])
