@@ -1,6 +1,7 @@
 """ctypes binding of libm2t.so (include/m2t.h, include/m2t_spectral.h, include/m2t_resize.h, include/m2t_msssim.h,
 include/m2t_vif.h, include/m2t_groups.h, include/m2t_perceptual.h, include/m2t_rlutrans.h, include/m2t_infer.h, include/m2t_train.h,
-include/m2t_tiles.h, include/m2t_gmsd.h, include/m2t_degrade.h, include/m2t_jpeg.h, include/m2t_wavelet.h, include/m2t_text.h, include/m2t_swin.h).
+include/m2t_tiles.h, include/m2t_gmsd.h, include/m2t_degrade.h, include/m2t_jpeg.h, include/m2t_wavelet.h, include/m2t_text.h, include/m2t_swin.h,
+include/m2t_consistency.h).
 
 The product path has NO fallback: if the HIP library is missing, or a call fails, this
 module raises.  Build it with ``python -m m2trans_amd.build`` (hipcc, gfx950).
@@ -261,6 +262,16 @@ SWIN_SIGNATURES = {
     "m2t_swin_backward_ex": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# the eighteenth header, include/m2t_consistency.h (LR-consistency: the bicubic-down loss term, the adjoint of the down-sampler and
+# back-projection), bound on the same library; must list every symbol that header declares.  The seventeen tables above stay as they are.
+CONSISTENCY_SIGNATURES = {
+    "m2t_consistency_scratch_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
+    "m2t_imresize_adjoint_f32": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp]),
+    "m2t_consistency_loss_tensor": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _ll, _i, _f, _i, _d, _d, _vp, _vp, _vp, _i, _vp, _vp]),
+    "m2t_consistency_loss": (_i, [_vp, _vp, _f, _d, _f, _d, _vp, _i, _vp, _vp, _vp]),
+    "m2t_back_project_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _d, _i, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -286,7 +297,8 @@ def load():
             + list(MSSSIM_SIGNATURES.items()) + list(VIF_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()) \
             + list(PERCEPTUAL_SIGNATURES.items()) + list(RLUTRANS_SIGNATURES.items()) + list(INFER_SIGNATURES.items()) \
             + list(TRAIN_SIGNATURES.items()) + list(TILES_SIGNATURES.items()) + list(GMSD_SIGNATURES.items()) + list(DEGRADE_SIGNATURES.items()) \
-            + list(JPEG_SIGNATURES.items()) + list(WAVELET_SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(SWIN_SIGNATURES.items()):
+            + list(JPEG_SIGNATURES.items()) + list(WAVELET_SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(SWIN_SIGNATURES.items()) \
+            + list(CONSISTENCY_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -27,7 +27,8 @@ With a pixel loss other than L1 (TrainStep(pixel_loss=...)) the dict carries ``m
 beta / None}; ``import_checkpoint`` sets the TrainStep's loss from it and leaves the loss alone when the file has no such entry.
 An L1 run writes no entry: its dict is the one above.  Every optional loss term of the step that is on (train_step.LOSS_TERMS, in
 that order, then the perceptual term, then train_step.MORE_LOSS_TERMS and LATER_LOSS_TERMS: ``"lambda_gmsd"``, then ``"lambda_wavelet"`` with ``"wavelet"`` (a name or
-the two tap lists), ``"wavelet_levels"``, ``"wavelet_band_weights"`` and ``"wavelet_eps"`` behind it) adds its weight to the entry
+the two tap lists), ``"wavelet_levels"``, ``"wavelet_band_weights"`` and ``"wavelet_eps"`` behind it; last the LR-consistency term, which has no row in
+the table: ``"lambda_consistency"`` with ``"consistency_eps"``) adds its weight to the entry
 as ``"lambda_<term>"`` (and the entry then exists for an L1 pixel term too); ``import_checkpoint`` calls the step's ``set_lambda_<term>`` with it.  ``"lambda_fft"`` is followed by ``"fft_norm"``;
 ``"lambda_perceptual"`` by ``"perceptual_criterion"``, ``"perceptual_weights"`` and ``"perceptual_resize"`` (never the VGG19 weights;
 ``import_checkpoint`` sets them on the step's ``perceptual_loss`` object first).  The keys of a term whose weight is 0 are absent, so
@@ -110,7 +111,8 @@ def _pixel_loss(train_step):
     from .train_step import LATER_LOSS_TERMS, LOSS_TERMS, MORE_LOSS_TERMS, resolve_pixel_loss
     _, canon, value = resolve_pixel_loss(getattr(train_step, "pixel_loss", "l1"), getattr(train_step, "pixel_loss_param", None))
     # (the entry keeps the order it always had -- LOSS_TERMS, then the perceptual term -- and the later rows follow it)
-    names = [t.name for t in LOSS_TERMS] + ["perceptual"] + [t.name for t in MORE_LOSS_TERMS + LATER_LOSS_TERMS]
+    # (... and the consistency term, which has no row in the table, follows the rows)
+    names = [t.name for t in LOSS_TERMS] + ["perceptual"] + [t.name for t in MORE_LOSS_TERMS + LATER_LOSS_TERMS] + ["consistency"]
     lam = {n: float(getattr(train_step, f"lambda_{n}", 0.0) or 0.0) for n in names}
     if canon == "l1" and not any(lam.values()):
         return None
@@ -128,6 +130,8 @@ def _pixel_loss(train_step):
             bw = getattr(train_step, "wavelet_band_weights", None)
             out["wavelet_band_weights"] = None if bw is None else [float(v) for v in bw]
             out["wavelet_eps"] = float(getattr(train_step, "wavelet_eps", 0.0))
+        if n == "consistency":
+            out["consistency_eps"] = float(getattr(train_step, "consistency_eps", 0.0))
         if n == "perceptual":
             # the settings of the term, never the VGG19 weights (an integrator loads those: INTEGRATION.md)
             p = train_step.perceptual_loss
@@ -276,6 +280,13 @@ def import_checkpoint(ckpt: dict, model, train_step=None) -> int:
                 if t.name == "wavelet":
                     train_step.wavelet, train_step.wavelet_levels, train_step.wavelet_eps = w.wavelet, w.levels, w.eps
                     train_step.wavelet_band_weights = None if w.band_weights is None else list(w.band_weights)
+        if "lambda_consistency" in ml:
+            from .train_step import resolve_consistency_eps
+            if hasattr(train_step, "set_lambda_consistency"):
+                train_step.set_lambda_consistency(ml["lambda_consistency"], ml.get("consistency_eps", 0.0))
+            else:
+                train_step.lambda_consistency = resolve_lambda("consistency", ml["lambda_consistency"])
+                train_step.consistency_eps = resolve_consistency_eps(ml.get("consistency_eps", 0.0))
         if "lambda_perceptual" in ml:
             p = getattr(train_step, "perceptual_loss", None)
             if p is None:

@@ -12,6 +12,7 @@
 #include "../../include/m2t_vif.h"
 #include "../../include/m2t_gmsd.h"
 #include "../../include/m2t_wavelet.h"
+#include "../../include/m2t_consistency.h"
 #include "../../include/m2t_perceptual.h"
 
 static thread_local std::string g_err;
@@ -801,6 +802,18 @@ extern "C" int m2t_wavelet_loss(m2t_plan* p, const float* hr, float weight, doub
   return launch_wavelet_loss(s.x, hr, p->B, 3, p->Hs, p->Ws, s.xs_img, s.xs_row, rgb_range, 1, (double)weight / divisor, lo, hi, taps,
                              levels, band_weights, eps, nullptr, s.gx, loss_out, nullptr, accumulate ? 1 : 0, scratch,
                              (hipStream_t)stream);
+}
+
+// weight * mean rho((D clamp(sr) - lr) / R), D the bicubic down-sampler of the plan's scale (k_consistency.hip; include/m2t_consistency.h).
+// The target is the step's own LR batch, not hr.
+extern "C" int m2t_consistency_loss(m2t_plan* p, const float* lr, float weight, double divisor, float rgb_range, double eps, float* loss_out,
+                                    int accumulate, void* scratch, void* workspace, void* stream) {
+  CK(loss_entry_args(__func__, !p || !lr || !loss_out || !scratch || !workspace, rgb_range, divisor, weight));
+  if (!(eps >= 0.0) || !std::isfinite(eps)) return m2t_set_error_at(M2T_ERR_ARG, __func__, "eps must be a finite number >= 0");
+  LossSeed s;
+  CK(loss_entry_seed(__func__, p, p->B * 3 <= 65535, "batch too large (B * 3 <= 65535)", workspace, &s));
+  return launch_consistency_loss(s.x, lr, p->B, 3, p->H0, p->W0, p->scale, s.xs_img, s.xs_row, rgb_range, 1, eps, (double)weight / divisor,
+                                 s.gx, loss_out, nullptr, accumulate ? 1 : 0, scratch, (hipStream_t)stream);
 }
 
 // weight * sum_k w_k mean(rho(F_k(sr) - F_k(hr))) on VGG19 features (k_vgg.hip, m2t_vgg.hip; include/m2t_perceptual.h).  The tower's

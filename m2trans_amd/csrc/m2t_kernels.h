@@ -407,6 +407,14 @@ int launch_wavelet_loss(const float* x, const float* y, int B, int C, int H, int
                         double scale, const double* lo, const double* hi, int taps, int levels, const double* band_weights, double eps,
                         float* swt_out, float* gx_add, float* loss_out, double* per_band_out, int accumulate, void* scratch,
                         hipStream_t st);
+// ---- k_consistency.hip (LR-consistency: m2t_consistency_loss_tensor / m2t_consistency_loss / m2t_back_project_f32) ----------
+// x [B][C][H s][W s] with the strides of launch_ssim_loss, y contiguous [B][C][H][W] (the LR side); gx_add, loss_out and accumulate of
+// launch_ssim_loss; stats_out (or nullptr): double [3] = {mean |r|, max |r|, mean r^2}.  scratch: consistency_scratch_bytes(B, C, H, W, s)
+// bytes (0 for an unsupported shape).  Arguments are checked by the callers.
+size_t consistency_scratch_bytes(int B, int C, int H, int W, int s);
+int launch_consistency_loss(const float* x, const float* y, int B, int C, int H, int W, int s, long long xs_img, int xs_row, float R,
+                            int clamp, double eps, double scale, float* gx_add, float* loss_out, double* stats_out, int accumulate,
+                            void* scratch, hipStream_t st);
 // ---- k_fft_loss.hip (the L1 loss on the coefficients of a 2-D real FFT and its gradient: m2t_fft_loss_tensor / m2t_fft_loss) ----------
 // x [B][C][H][W] with image stride xs_img, channel stride xs_img / C, row stride xs_row; y contiguous; gx_add (or nullptr) has x's strides:
 // gx_add[q] += scale * d sum(|Re D| + |Im D|) / dx[q] (through the clamp mask when clamp); loss_out = (accumulate ? loss_out : 0) + scale * sum.

@@ -236,6 +236,52 @@ class Tiled(nn.Module):
         return tiled(self.model, lr, self.tile, self.overlap, self.tile_batch, self.with_seam)
 
 
+def back_project(sr: torch.Tensor, lr: torch.Tensor, scale: int, iters: int = 3, beta: float = 1.0, rgb_range: float = 1.0,
+                 with_stats: bool = False):
+    """Irani-Peleg back-projection towards LR-consistency: `iters` times ``sr <- clamp(sr + beta * U(lr - D(clamp(sr))), 0,
+    rgb_range)``, D / U the bicubic x`scale` down- / up-sampler of `resize.imresize` (m2t_back_project_f32 of
+    include/m2t_consistency.h: the residual in fp64, one fp32 rounding per updated pixel).  Device tensors sr [B,C,H*scale,W*scale] and
+    lr [B,C,H,W], C = 1 or 3, 0 < beta < 2; returns a NEW tensor.  with_stats: also a float64 device tensor [iters + 1, 3], row k =
+    {mean |r|, max |r|, mean r^2} of r = (lr - D(clamp(sr_k))) / rgb_range before update k, the last row taken after the last update
+    (LR-PSNR = -10 log10 of the third column).  No host read."""
+    from .losses import _consistency_check
+    _consistency_check("back_project", sr, lr, scale, 0.0, rgb_range, lr_no_grad=False)
+    iters = int(iters)
+    if iters < 0:
+        raise M2TError(f"back_project: iters must be >= 0, got {iters}")
+    import math
+    if not (math.isfinite(float(beta)) and 0.0 < float(beta) < 2.0):
+        raise M2TError(f"back_project: beta must be a finite number inside (0, 2), got {beta!r}")
+    lib = _lib.load()
+    out = sr.detach().float().clone(memory_format=torch.contiguous_format)
+    yc = lr.detach().contiguous().float()
+    B, Cn, H, W = yc.shape
+    nbytes = lib.m2t_consistency_scratch_bytes(B, Cn, H, W, int(scale))
+    if nbytes == 0:
+        raise M2TError(f"back_project: no scratch size for LR [{B},{Cn},{H},{W}] x{scale} (SR sides at most 16384, B * C at most 65535)")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=out.device)
+    stats = torch.empty(iters + 1, 3, dtype=torch.float64, device=out.device) if with_stats else None
+    with torch.cuda.device(out.device):
+        st = _lib.stream_ptr()
+        for k in range(iters + (1 if with_stats else 0)):
+            _lib.check(lib.m2t_back_project_f32(_lib.ptr(out), _lib.ptr(yc), B, Cn, H, W, int(scale), float(rgb_range), float(beta),
+                                                int(k < iters), _lib.ptr(stats[k]) if with_stats else None, _lib.ptr(scratch), st),
+                       "m2t_back_project_f32")
+    return (out, stats) if with_stats else out
+
+
+class BackProject(nn.Module):
+    """`back_project` as a module around `model` (``lr -> sr``): composes OUTSIDE `Tiled` / `SelfEnsemble`
+    (``BackProject(Tiled(SelfEnsemble(model)), 4)``: consistency is a property of the whole image) and drops into `metrics.evaluate`."""
+
+    def __init__(self, model, scale: int, iters: int = 3, beta: float = 1.0, rgb_range: float = 1.0):
+        super().__init__()
+        self.model, self.scale, self.iters, self.beta, self.rgb_range = model, int(scale), int(iters), float(beta), float(rgb_range)
+
+    def forward(self, lr):
+        return back_project(self.model(lr), lr, self.scale, self.iters, self.beta, self.rgb_range)
+
+
 def to_uint8(sr: torch.Tensor, rgb_range: float = 1.0) -> torch.Tensor:
     """float32 [1,C,H,W] or [C,H,W] on the device, C = 1 or 3 -> uint8 [H,W,C] on the device with the rounding of torchvision's
     save_image: min(max(v * (255 / rgb_range) + 0.5, 0), 255) truncated; a NaN becomes 0."""
@@ -299,13 +345,16 @@ def _save_map(grey_of: torch.Tensor, path) -> float:
 
 
 def upscale_folder(model, in_dir, out_dir, self_ensemble: bool = False, spread_dir=None, rgb_range: float = 1.0,
-                   device="cuda", tile=None, overlap: int = 16, tile_batch=None, seam_dir=None) -> list:
+                   device="cuda", tile=None, overlap: int = 16, tile_batch=None, seam_dir=None, back_project_iters: int = 0,
+                   back_project_beta: float = 1.0) -> list:
     """Every image of `in_dir` through `model` into `out_dir` as `<name>.png`; returns the written names.  self_ensemble: through
     the eight views.  spread_dir (needs self_ensemble): the per-pixel maximum over RGB of the spread as an 8-bit grey PNG of the same
     name, scaled by the image's own maximum (grey 255 = that maximum); `spread.json` beside the files maps each name to that maximum,
     in units of `rgb_range`.  tile: through `tiled` with that tile size, `overlap` and `tile_batch` (None: 16, or 2 with
     self_ensemble, which makes 16 views per call); the ensemble is then taken per tile.  seam_dir (needs tile): the seam map, written
-    like the spread, with `seam.json`."""
+    like the spread, with `seam.json`.  back_project_iters > 0: every output goes through that many iterations of `back_project` (step
+    `back_project_beta`) against its own input before it is written, and `consistency.json` beside the results holds, per image,
+    the mean / max residual and the LR-PSNR before and after."""
     if spread_dir is not None and not self_ensemble:
         raise M2TError("upscale_folder: spread_dir needs self_ensemble=True (the spread is that of the eight views)")
     if seam_dir is not None and tile is None:
@@ -320,7 +369,7 @@ def upscale_folder(model, in_dir, out_dir, self_ensemble: bool = False, spread_d
     if seam_dir is not None:
         os.makedirs(str(seam_dir), exist_ok=True)
     run = _self_ensemble                                        # (the keyword of this function shadows the module's function)
-    factors, seams = {}, {}
+    factors, seams, cons = {}, {}, {}
     with torch.no_grad():
         for name, out in zip(names, outs):
             lr = load_image(os.path.join(str(in_dir), name), device, rgb_range)
@@ -341,6 +390,9 @@ def upscale_folder(model, in_dir, out_dir, self_ensemble: bool = False, spread_d
             else:
                 sr, spread = run(model, lr, with_spread=True)
                 factors[out] = _save_map(spread, os.path.join(str(spread_dir), out))
+            if back_project_iters > 0:
+                sr, cons[out] = back_project(sr, lr, sr.shape[2] // lr.shape[2], back_project_iters, back_project_beta, rgb_range,
+                                             with_stats=True)
             save_image(sr, os.path.join(str(out_dir), out), rgb_range)
     if spread_dir is not None:
         with open(os.path.join(str(spread_dir), "spread.json"), "w") as f:
@@ -348,7 +400,21 @@ def upscale_folder(model, in_dir, out_dir, self_ensemble: bool = False, spread_d
     if seam_dir is not None:
         with open(os.path.join(str(seam_dir), "seam.json"), "w") as f:
             json.dump({"rgb_range": float(rgb_range), "max_seam": seams}, f, indent=1, sort_keys=True)
+    if back_project_iters > 0:
+        with open(os.path.join(str(out_dir), "consistency.json"), "w") as f:
+            json.dump({"rgb_range": float(rgb_range), "iters": int(back_project_iters), "beta": float(back_project_beta),
+                       "images": {n: consistency_record(t.cpu()) for n, t in cons.items()}}, f, indent=1, sort_keys=True)
     return outs
+
+
+def consistency_record(stats: torch.Tensor) -> dict:
+    """The first and the last row of `back_project`'s statistics (host tensor [iters + 1, 3]) as the entry of consistency.json."""
+    import math
+
+    def row(r):
+        mse = float(r[2])
+        return {"mean_residual": float(r[0]), "max_residual": float(r[1]), "lr_psnr": -10.0 * math.log10(mse) if mse > 0.0 else float("inf")}
+    return {"before": row(stats[0]), "after": row(stats[-1])}
 
 
 # ------------------------------------------------------------------------------------------------------------------------- CLI
@@ -368,7 +434,19 @@ def parse_args(argv=None):
     ap.add_argument("--tile_batch", type=int, default=None, metavar="N", help="with --tile: tiles per model call (default 16, or 2 with "
                     "--self_ensemble: 16 views per call)")
     ap.add_argument("--seam", default=None, metavar="DIR", help="with --tile: write the per-pixel disagreement of overlapping tiles there")
+    ap.add_argument("--back_project", type=int, default=None, metavar="K", help="K iterations of back-projection on every output against "
+                    "its input (LR-consistency); writes consistency.json beside the results")
+    ap.add_argument("--back_project_beta", type=float, default=None, metavar="B", help="with --back_project: the step, 0 < B < 2 (default 1)")
     args = ap.parse_args(argv)
+    if args.back_project_beta is not None and args.back_project is None:
+        ap.error("--back_project_beta needs --back_project")
+    if args.back_project is not None:
+        if args.back_project < 1:
+            ap.error("--back_project must be at least 1")
+        if args.back_project_beta is None:
+            args.back_project_beta = 1.0
+        elif not (0.0 < args.back_project_beta < 2.0):
+            ap.error("--back_project_beta must lie inside (0, 2)")
     if args.spread is not None and not args.self_ensemble:
         ap.error("--spread needs --self_ensemble")
     if args.seam is not None and args.tile is None:
@@ -416,9 +494,14 @@ def main(argv=None) -> int:
     model.eval()
     outs = upscale_folder(model, args.input, args.output, self_ensemble=args.self_ensemble, spread_dir=args.spread,
                           rgb_range=float(getattr(ns, "rgb_range", 1.0)), tile=args.tile, overlap=args.tile_overlap,
-                          tile_batch=args.tile_batch, seam_dir=args.seam)
-    print(json.dumps({"images": len(outs), "output": args.output, "self_ensemble": bool(args.self_ensemble), "spread": args.spread,
-                      "tile": args.tile, "tile_overlap": args.tile_overlap if args.tile is not None else None, "seam": args.seam}))
+                          tile_batch=args.tile_batch, seam_dir=args.seam, back_project_iters=args.back_project or 0,
+                          back_project_beta=args.back_project_beta or 1.0)
+    line = {"images": len(outs), "output": args.output, "self_ensemble": bool(args.self_ensemble), "spread": args.spread,
+            "tile": args.tile, "tile_overlap": args.tile_overlap if args.tile is not None else None, "seam": args.seam}
+    if args.back_project is not None:
+        line.update({"back_project": args.back_project, "back_project_beta": args.back_project_beta,
+                     "consistency": os.path.join(args.output, "consistency.json")})
+    print(json.dumps(line))
     return 0
 
 

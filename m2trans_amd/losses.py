@@ -717,6 +717,71 @@ class VIFLoss(nn.Module):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# LR-consistency (the "dual regression" / cycle term): rho(D(clamp(sr)) - lr), D the bicubic down-sampler that made the training
+# pairs.  The only term that needs no HR: ``ConsistencyLoss(4)(model(lr), lr).backward()`` fine-tunes on real LR frames.  Value and
+# gradient are HIP (m2t_consistency_loss_tensor of include/m2t_consistency.h, k_consistency.hip); there is no torch fallback.
+# ---------------------------------------------------------------------------------------------------------------
+def _consistency_check(what, sr, lr, scale, eps, data_range, lr_no_grad=True):
+    if scale not in (2, 3, 4):
+        raise M2TError(f"{what}: scale must be 2, 3 or 4, got {scale!r}")
+    if not (math.isfinite(float(data_range)) and float(data_range) > 0.0):
+        raise M2TError(f"{what}: data_range must be a finite number > 0, got {data_range!r}")
+    if not (math.isfinite(float(eps)) and float(eps) >= 0.0):
+        raise M2TError(f"{what}: eps must be a finite number >= 0, got {eps!r}")
+    if sr.dim() != 4 or lr.dim() != 4 or tuple(sr.shape) != (lr.shape[0], lr.shape[1], lr.shape[2] * scale, lr.shape[3] * scale):
+        raise M2TError(f"{what}: expected sr [B,C,H*{scale},W*{scale}] and lr [B,C,H,W], got {tuple(sr.shape)} and {tuple(lr.shape)}")
+    if int(sr.shape[1]) not in (1, 3):
+        raise M2TError(f"{what}: 1 or 3 channels, got {int(sr.shape[1])}")
+    if not (sr.is_cuda and lr.is_cuda):
+        raise M2TError(f"{what} needs HIP device tensors (there is no host implementation)")
+    if lr_no_grad and lr.requires_grad:
+        raise M2TError(f"{what} gives the gradient with respect to sr only: lr must not require grad (detach it)")
+
+
+def _consistency_call(sr, lr, scale, eps, data_range, clamp, want_grad, want_stats=False):
+    """(loss [1] float32 = mean rho(r), its gradient or None, {mean |r|, max |r|, mean r^2} float64 [3] or None)."""
+    lib = _lib.load()
+    xc, yc = sr.detach().contiguous().float(), lr.detach().contiguous().float()
+    B, Cn, H, W = yc.shape
+    nbytes = lib.m2t_consistency_scratch_bytes(B, Cn, H, W, int(scale))
+    if nbytes == 0:
+        raise M2TError(f"consistency: no scratch size for LR [{B},{Cn},{H},{W}] x{scale} (SR sides at most 16384, B * C at most 65535)")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=xc.device)
+    out = torch.empty(1, dtype=torch.float32, device=xc.device)
+    grad = torch.zeros_like(xc) if want_grad else None
+    stats = torch.empty(3, dtype=torch.float64, device=xc.device) if want_stats else None
+    Hs, Ws = H * int(scale), W * int(scale)
+    with torch.cuda.device(xc.device):
+        _lib.check(lib.m2t_consistency_loss_tensor(_lib.ptr(xc), _lib.ptr(yc), B, Cn, H, W, int(scale), Cn * Hs * Ws, Ws, float(data_range),
+                                                   int(bool(clamp)), float(eps), 1.0 / (B * Cn * H * W), _lib.ptr(grad), _lib.ptr(out),
+                                                   _lib.ptr(stats), 0, _lib.ptr(scratch), _lib.stream_ptr()), "m2t_consistency_loss_tensor")
+    return out, grad, stats
+
+
+def consistency_loss(sr: torch.Tensor, lr: torch.Tensor, scale: int, eps: float = 0.0, data_range: float = 1.0,
+                     clamp: bool = True) -> torch.Tensor:
+    """mean rho((D(c(sr)) - lr) / data_range) over the LR elements: D the bicubic x`scale` down-sampler of `resize.imresize`,
+    c the clamp to [0, data_range] (clamp=False: none), rho(r) = |r| for eps = 0 and sqrt(r^2 + eps^2) otherwise.  Device tensors
+    sr [B,C,H*scale,W*scale] and lr [B,C,H,W], C = 1 or 3; differentiable with respect to ``sr`` only, through the adjoint of D and
+    the clamp mask (the ends of the range pass).  fp64 inside the kernels, fp32 in and out."""
+    _consistency_check("consistency_loss", sr, lr, scale, eps, data_range)
+    return _EagerGradFn.apply(sr, lambda want_grad: _consistency_call(sr, lr, scale, eps, data_range, clamp, want_grad)[:2])
+
+
+class ConsistencyLoss(nn.Module):
+    """``consistency_loss`` as a module: ``ConsistencyLoss(4)(model(lr), lr)``."""
+
+    def __init__(self, scale: int, eps: float = 0.0, data_range: float = 1.0):
+        super().__init__()
+        if scale not in (2, 3, 4):
+            raise M2TError(f"ConsistencyLoss: scale must be 2, 3 or 4, got {scale!r}")
+        self.scale, self.eps, self.data_range = int(scale), float(eps), float(data_range)
+
+    def forward(self, sr: torch.Tensor, lr: torch.Tensor) -> torch.Tensor:
+        return consistency_loss(sr, lr, self.scale, self.eps, self.data_range)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # The gradient-magnitude term: GMSD (the reference scores every model by it, test.py:95-122; piq ships GMSDLoss next to the classes
 # the reference imports).  Value and gradient are HIP (m2t_gmsd_loss_tensor of include/m2t_gmsd.h, k_gmsd_loss.hip); there is no torch
 # fallback -- autograd through sqrt(gx^2 + gy^2) is NaN wherever the image is locally flat.

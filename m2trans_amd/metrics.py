@@ -167,3 +167,30 @@ def evaluate(model, pairs, scale: int, rgb_range: float = 1.0, with_gmsd: bool =
     if with_vif:
         out.append(round(float(torch.cat(vrows).sum()) / len(psnr) + 5e-5, 4))
     return tuple(out)
+
+
+def lr_psnr_device(sr: torch.Tensor, lr: torch.Tensor, scale: int, rgb_range: float = 1.0) -> torch.Tensor:
+    """LR-PSNR, the consistency score of the NTIRE reports: ``-10 log10(mean r^2)`` with r = (D(clamp(sr)) - lr) / rgb_range, D the
+    bicubic x`scale` down-sampler; device tensors sr [B,C,H*scale,W*scale], lr [B,C,H,W] -> float64 [1] on the device (inf for an
+    exactly consistent pair).  The value-only path of `m2t_consistency_loss_tensor` (k_consistency.hip): no host read."""
+    from .losses import _consistency_call, _consistency_check
+    _consistency_check("lr_psnr_device", sr, lr, scale, 0.0, rgb_range, lr_no_grad=False)
+    _, _, stats = _consistency_call(sr, lr, scale, 0.0, rgb_range, True, False, True)
+    return -10.0 * torch.log10(stats[2:3])
+
+
+def evaluate_with_lr_psnr(model, pairs, scale: int, rgb_range: float = 1.0, self_ensemble: bool = False, **with_metrics):
+    """`evaluate` with the average LR-PSNR of (sr, lr) appended to its outputs, rounded like PSNR; the model runs once per pair
+    (`evaluate`'s own signature is pinned, so the score has an entry of its own).  The per-image values stay on the device until
+    `evaluate` has made its one host synchronisation."""
+    if self_ensemble:
+        from .infer import SelfEnsemble
+        model = SelfEnsemble(model)
+    rows = []
+
+    def scored(lr):
+        sr = model(lr)
+        rows.append(lr_psnr_device(sr, lr, scale, rgb_range))
+        return sr
+    out = evaluate(scored, pairs, scale, rgb_range, **with_metrics)
+    return out + (round(float(torch.cat(rows).sum()) / len(rows) + 5e-3, 2),)

@@ -95,6 +95,22 @@ def imresize(x: torch.Tensor, scale: int, up: bool = False, clamp_max: float = 0
     return out
 
 
+def imresize_adjoint(g: torch.Tensor, scale: int) -> torch.Tensor:
+    """The adjoint D^T of the bicubic down-sampler (include/m2t_consistency.h): float32 [N,C,h,w] on the device -> float32
+    [N,C,h*scale,w*scale] with ``<imresize(x, scale), g> = <x, imresize_adjoint(g, scale)>``; the mirrored border makes it more than a
+    transposed stencil (border pixels also receive the reflected taps).  The fp64 result is rounded once to fp32."""
+    if g.dtype != torch.float32 or g.dim() != 4 or not g.is_cuda:
+        raise _lib.M2TError(f"imresize_adjoint takes a float32 [N,C,h,w] device tensor, got {g.dtype} {tuple(g.shape)} on {g.device}")
+    g = g.contiguous()
+    N, C, h, w = g.shape
+    out = torch.empty(N, C, h * int(scale), w * int(scale), dtype=torch.float32, device=g.device)
+    lib = _lib.load()
+    with torch.cuda.device(g.device):
+        _lib.check(lib.m2t_imresize_adjoint_f32(_lib.ptr(g), N * C, h, w, _lib.ptr(out), int(scale), 0, _lib.stream_ptr()),
+                   "m2t_imresize_adjoint_f32")
+    return out
+
+
 class BicubicUp:
     """The interpolation baseline as a callable ``lr -> sr`` (clamped to [0, rgb_range]), usable as `model` of `metrics.evaluate`:
     the "Bicubic" row of a results table is ``evaluate(BicubicUp(s), pairs, s, ...)``.

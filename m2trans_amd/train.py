@@ -95,8 +95,10 @@ class StepMeter:
 
 def meter_columns(train_step) -> List[str]:
     """The columns `fit` meters for this step object: the total loss, the pixel term, the clip term, every optional term that is on
-    (ALL_LOSS_TERMS, then the perceptual term) and, when the step tracks them, the gradient norm and the clip coefficient."""
+    (ALL_LOSS_TERMS, then consistency, then the perceptual term) and, when the step tracks them, the gradient norm and the clip coefficient."""
     names = ["loss", "pixel", "clip"] + [t.name for t in ALL_LOSS_TERMS if getattr(train_step, f"lambda_{t.name}", 0.0) > 0.0]
+    if getattr(train_step, "lambda_consistency", 0.0) > 0.0:
+        names.append("consistency")
     if getattr(train_step, "lambda_perceptual", 0.0) > 0.0:
         names.append("perceptual")
     if getattr(train_step, "grad_norm", None) is not None:
@@ -390,7 +392,7 @@ REFERENCE_KEYS = MODEL_KEYS + ("pretrain", "patch_size", "batch_size", "data_rep
 IGNORED_KEYS = ("gpu_ids", "threads", "num_heads")
 # ... and the project's own, each handed to TrainStep unchanged (TrainStep validates them)
 TRAINSTEP_KEYS = ("pixel_loss", "pixel_loss_param", "lambda_ssim", "lambda_msssim", "lambda_fft", "fft_norm", "lambda_vif", "lambda_gmsd", "lambda_wavelet",
-                  "wavelet", "wavelet_levels", "wavelet_band_weights", "wavelet_eps", "accum_steps",
+                  "wavelet", "wavelet_levels", "wavelet_band_weights", "wavelet_eps", "lambda_consistency", "consistency_eps", "accum_steps",
                   "max_grad_norm", "weight_decay", "decoupled_weight_decay", "ema_decay", "skip_nonfinite", "param_groups")
 LOOP_KEYS = ("train_hr_path", "eval_folders", "preview_every", "validate_ema", "seed", "ring_rows", "track_grad_norm")
 DATA_KEYS = ("degradation",)            # a mapping of degrade.Degradation's arguments: LR synthesis beyond bicubic
@@ -440,6 +442,9 @@ def resolve_config(cfg: dict, compute_dtype=None) -> dict:
     if cfg.get("degradation") is not None:
         from .degrade import check_config
         degradation = check_config(cfg["degradation"])
+        if float(cfg.get("lambda_consistency") or 0.0) > 0.0:
+            raise M2TError("lambda_consistency > 0 together with degradation: the consistency term's operator is the bicubic down-sampler, "
+                           "not the degradation's per-sample blur kernels (drop one of the two keys)")
     model = {k: cfg[k] for k in MODEL_KEYS if k in cfg and k != "model"}
     model.setdefault("n_feats", 64)
     model.setdefault("n_blocks", 8)

@@ -31,7 +31,7 @@ m2t_pixel_loss_deferred), so every kind runs the schedule of the L1 step -- the 
 the overlapped exchange and the optimizer options included.
 
 Optional loss terms (all off by default; LOSS_TERMS, MORE_LOSS_TERMS and LATER_LOSS_TERMS below are their table, and its order -- SSIM, MS-SSIM, FFT,
-VIF, GMSD, wavelet, then the perceptual term -- is the order of the calls).  Every term that is on takes the MATERIALISED seed: the immediate pixel loss, then one
+VIF, GMSD, wavelet, then consistency and the perceptual term, which have paths of their own -- is the order of the calls).  Every term that is on takes the MATERIALISED seed: the immediate pixel loss, then one
 ``m2t_<term>_loss`` call per term that adds its gradient into the seed, then the backward pass; the seed fused into the x4 tail
 backward does not apply.  An SR size a term does not take is refused on the host before anything is launched.  With a weight of 0
 nothing is allocated for the term and the step issues the calls it issued before.  Value and gradient are HIP, fp64 inside unless
@@ -61,6 +61,11 @@ said otherwise.
   (stationary) wavelet transform of ``clamp(sr, 0, rgb_range) / rgb_range - hr / rgb_range`` with periodic borders: ``'haar'``, ``'db2'``
   or a pair of tap lists, 1 .. 3 levels, by default an L1 on every detail band and nothing on LL (m2t_wavelet_loss of
   include/m2t_wavelet.h; SR height and width >= (taps - 1) * 2^(levels - 1) + 1).  The row sits in LATER_LOSS_TERMS, behind GMSD.
+* ``lambda_consistency``, ``consistency_eps`` (the "dual regression" / cycle term; the only one that compares with the LR input and
+  not with HR): ``lambda_consistency * mean rho((D(clamp(sr, 0, rgb_range)) - lr) / rgb_range)`` over the LR elements, D the bicubic
+  down-sampler that made the training pairs, rho = |.| or Charbonnier with ``consistency_eps`` (m2t_consistency_loss of
+  include/m2t_consistency.h).  Its target is the step's own ``lr_img``, so it has a path of its own beside the table, called behind
+  the table's rows and in front of the perceptual term.
 * ``lambda_perceptual``, ``perceptual_loss=`` (PerceptualLoss of the reference's losses.py:222-270): ``lambda_perceptual * sum_k w_k
   mean(crit(F_k(sr) - F_k(hr)))`` on VGG19 features; the tower, its weights, its workspace, the criterion and the tap weights are
   those of the losses.PerceptualLoss object (m2t_vgg_loss of include/m2t_perceptual.h, bf16 compute; SR height and width >= 16).
@@ -145,6 +150,18 @@ resolve_lambda_vif = functools.partial(resolve_lambda, "vif")
 resolve_lambda_gmsd = functools.partial(resolve_lambda, "gmsd")
 resolve_lambda_wavelet = functools.partial(resolve_lambda, "wavelet")
 resolve_lambda_perceptual = functools.partial(resolve_lambda, "perceptual")
+resolve_lambda_consistency = functools.partial(resolve_lambda, "consistency")
+
+
+def resolve_consistency_eps(value) -> float:
+    """TrainStep's ``consistency_eps`` as a float; M2TError unless it is a finite number >= 0 (0 = L1, > 0 = Charbonnier)."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = math.nan
+    if not (math.isfinite(v) and v >= 0.0):
+        raise _lib.M2TError(f"consistency_eps must be a finite number >= 0, got {value!r}")
+    return v
 
 _S3 = math.sqrt(3.0)
 _DB2 = ((1.0 + _S3) / 8.0, (3.0 + _S3) / 8.0, (3.0 - _S3) / 8.0, (1.0 - _S3) / 8.0)
@@ -349,6 +366,8 @@ class TrainStep:
     _wavelet_call = None          # the C arguments of the wavelet term, made by the setter or on first use
     fft_norm = "backward"
     perceptual_loss = None
+    # the LR-consistency term: its target is the step's own lr_img, so it has a path of its own beside the table
+    lambda_consistency, consistency_eps, consistency_loss, _consistency_scratch = 0.0, 0.0, None, None
     groups = None
     _need_stage = None
 
@@ -362,7 +381,8 @@ class TrainStep:
                  lambda_ssim: float = 0.0, lambda_fft: float = 0.0, fft_norm: str = "backward",
                  lambda_msssim: float = 0.0, lambda_vif: float = 0.0, param_groups=None, perceptual_loss=None,
                  lambda_perceptual: float = 0.0, lambda_gmsd: float = 0.0, lambda_wavelet: float = 0.0, wavelet="haar",
-                 wavelet_levels: int = 2, wavelet_band_weights=None, wavelet_eps: float = 0.0):
+                 wavelet_levels: int = 2, wavelet_band_weights=None, wavelet_eps: float = 0.0, lambda_consistency: float = 0.0,
+                 consistency_eps: float = 0.0):
         self.model = model
         # parameter groups / frozen tensors (param_groups.py): resolved against the model's names here, on the host, fixed for the
         # life of this object.  None (the default): nothing is allocated and the step issues the calls it always issued
@@ -376,6 +396,7 @@ class TrainStep:
         self.set_lambda_vif(lambda_vif)
         self.set_lambda_gmsd(lambda_gmsd)
         self.set_lambda_wavelet(lambda_wavelet, wavelet, wavelet_levels, wavelet_band_weights, wavelet_eps)
+        self.set_lambda_consistency(lambda_consistency, consistency_eps)
         self.perceptual_loss = perceptual_loss
         self.set_lambda_perceptual(lambda_perceptual)
         # gradient accumulation: one optimizer step consumes accum_steps equal micro-batches (forward_backward calls); the
@@ -608,6 +629,46 @@ class TrainStep:
                                        *term.extra(self), _lib.ptr(getattr(self, f"{n}_loss")), self._store_or_add(first),
                                        _lib.ptr(self._scratch_for(term, lib, hr_img)), ws, st), entry)
 
+    # -- the LR-consistency term: the same slot in the order and in the total; its target is lr_img, its scratch is sized by the LR ---
+    def set_lambda_consistency(self, value, eps=None):
+        """Weight of the LR-consistency term (0 = off) and, when given, its eps (0 = L1, > 0 = Charbonnier): ``lambda_consistency *
+        mean rho((D(clamp(sr)) - lr) / rgb_range)`` over the LR elements, D the bicubic down-sampler of the model's scale
+        (m2t_consistency_loss of include/m2t_consistency.h); the target is the step's own ``lr_img``.  Takes effect with the next
+        forward_backward (checkpoint.import_checkpoint calls this); refused in the middle of an accumulation cycle."""
+        _refuse_mid_cycle(self, "set_lambda_consistency")
+        lam = resolve_lambda("consistency", value)      # (a refused weight leaves eps as it was)
+        if eps is not None:
+            self.consistency_eps = resolve_consistency_eps(eps)
+        self.lambda_consistency = lam
+        if lam > 0.0:
+            if self.consistency_loss is None:
+                self.consistency_loss = torch.zeros(1, dtype=torch.float32, device=self.model.flat_params.device)
+        else:
+            self.consistency_loss = None
+            self._consistency_scratch = {}
+
+    def _consistency_scratch_for(self, lib, lr_img, hr_img=None):
+        """The term's scratch for this (micro-)batch shape, allocated once per shape."""
+        B, _, H0, W0 = lr_img.shape
+        if self._consistency_scratch is None:
+            self._consistency_scratch = {}
+        key = (B, H0, W0)
+        if key not in self._consistency_scratch:
+            nbytes = int(lib.m2t_consistency_scratch_bytes(B, 3, H0, W0, int(self.model.scale)))
+            if nbytes == 0:
+                raise _lib.M2TError(f"lambda_consistency > 0: no scratch size for a batch of {B} LR images {H0}x{W0} at scale "
+                                    f"{self.model.scale} (B * 3 <= 65535, SR sides at most 16384)")
+            self._consistency_scratch[key] = torch.empty(nbytes, dtype=torch.uint8, device=lr_img.device)
+        return self._consistency_scratch[key]
+
+    def _consistency_loss_call(self, lib, lr_img, plan, hr_img, first: bool, ws, st):
+        """m2t_consistency_loss of one (micro-)batch, behind the immediate pixel loss and the table's terms: adds into the materialised
+        seed.  The divisor is the GLOBAL number of LR elements."""
+        divisor = global_divisor(lr_img.numel(), self.world_size, self.accum_steps)
+        _lib.check(lib.m2t_consistency_loss(plan.handle, _lib.ptr(lr_img), self.lambda_consistency, divisor, float(self.model.rgb_range),
+                                            float(self.consistency_eps), _lib.ptr(self.consistency_loss), self._store_or_add(first),
+                                            _lib.ptr(self._consistency_scratch_for(lib, lr_img)), ws, st), "m2t_consistency_loss")
+
     # -- the perceptual term: the same slot in the order and in the total, its own preconditions, workspace and call ---------------
     def set_lambda_perceptual(self, value):
         """Weight of the VGG19 feature term (0 = off); needs ``perceptual_loss=`` (a losses.PerceptualLoss with weights loaded, resize
@@ -649,12 +710,16 @@ class TrainStep:
                                     _lib.ptr(self._perceptual_workspace_for(hr_img)), ws, st), "m2t_vgg_loss")
 
     # -- what forward_backward iterates ------------------------------------------------------------------------------------
-    def _terms_on(self, lib) -> list:
-        """The optional terms that are on, in call order -- the rows of ALL_LOSS_TERMS, then the perceptual term -- each as (value,
-        prepare, call): the term's device [1] tensor; prepare(hr_img), which refuses an SR size the term does not take and makes
-        sure of its scratch before anything is launched; call(plan, hr_img, first, ws, st), its m2t_*_loss call."""
+    def _terms_on(self, lib, lr_img=None) -> list:
+        """The optional terms that are on, in call order -- the rows of ALL_LOSS_TERMS, then consistency, then the perceptual term --
+        each as (value, prepare, call): the term's device [1] tensor; prepare(hr_img), which refuses an SR size the term does not
+        take and makes sure of its scratch before anything is launched; call(plan, hr_img, first, ws, st), its m2t_*_loss call.
+        lr_img: the (micro-)batch's LR tensor, the target of the consistency term."""
         on = [(getattr(self, f"{t.name}_loss"), functools.partial(self._scratch_for, t, lib), functools.partial(self._term_call, t, lib))
               for t in ALL_LOSS_TERMS if getattr(self, f"lambda_{t.name}") > 0.0]
+        if self.lambda_consistency > 0.0:
+            on.append((self.consistency_loss, functools.partial(self._consistency_scratch_for, lib, lr_img),
+                       functools.partial(self._consistency_loss_call, lib, lr_img)))
         if self.lambda_perceptual > 0.0:
             on.append((self.perceptual_loss_value, self._perceptual_workspace_for, functools.partial(self._perceptual_loss_call, lib)))
         return on
@@ -723,7 +788,7 @@ class TrainStep:
         B = lr_img.shape[0]
         if tuple(hr_img.shape) != (B, 3, lr_img.shape[2] * m.scale, lr_img.shape[3] * m.scale):
             raise _lib.M2TError("hr shape must be [B,3,H*scale,W*scale]")
-        on = self._terms_on(lib)
+        on = self._terms_on(lib, lr_img)
         for _, prepare, _ in on:
             prepare(hr_img)                         # (refuses an SR size the term does not take before any launch)
         divisor = global_divisor(hr_img.numel(), self.world_size, self.accum_steps)      # global mean (equal shards, equal micro-batches)
