@@ -25,11 +25,11 @@ above, key for key.
 
 With a pixel loss other than L1 (TrainStep(pixel_loss=...)) the dict carries ``m2t_loss`` = {"pixel_loss": name, "param": eps /
 beta / None}; ``import_checkpoint`` sets the TrainStep's loss from it and leaves the loss alone when the file has no such entry.
-An L1 run writes no entry: its dict is the one above.  Every optional loss term of the step that is on (train_step.LOSS_TERMS, in
-that order, then the perceptual term, then train_step.MORE_LOSS_TERMS and LATER_LOSS_TERMS: ``"lambda_gmsd"``, then ``"lambda_wavelet"`` with ``"wavelet"`` (a name or
-the two tap lists), ``"wavelet_levels"``, ``"wavelet_band_weights"`` and ``"wavelet_eps"`` behind it; last the LR-consistency term, which has no row in
-the table: ``"lambda_consistency"`` with ``"consistency_eps"``) adds its weight to the entry
-as ``"lambda_<term>"`` (and the entry then exists for an L1 pixel term too); ``import_checkpoint`` calls the step's ``set_lambda_<term>`` with it.  ``"lambda_fft"`` is followed by ``"fft_norm"``;
+An L1 run writes no entry: its dict is the one above.  Every optional loss term of the step that is on (the rows of
+train_step.LOSS_TERMS and the perceptual term, in the order of LOSS_KEY_ORDER below, which is not the call order) adds its weight to
+the entry as ``"lambda_<term>"`` (and the entry then exists for an L1 pixel term too); ``import_checkpoint`` calls the step's
+``set_lambda_<term>`` with it.  ``"lambda_fft"`` is followed by ``"fft_norm"``; ``"lambda_wavelet"`` by ``"wavelet"`` (a name or the two
+tap lists), ``"wavelet_levels"``, ``"wavelet_band_weights"`` and ``"wavelet_eps"``; ``"lambda_consistency"`` by ``"consistency_eps"``;
 ``"lambda_perceptual"`` by ``"perceptual_criterion"``, ``"perceptual_weights"`` and ``"perceptual_resize"`` (never the VGG19 weights;
 ``import_checkpoint`` sets them on the step's ``perceptual_loss`` object first).  The keys of a term whose weight is 0 are absent, so
 with every weight 0 the dict is the one described above, byte for byte.
@@ -105,19 +105,21 @@ def _optim_options(train_step) -> dict:
             "skip_nonfinite": bool(getattr(train_step, "skip_nonfinite", False))}
 
 
+# the order of the "lambda_<term>" keys of the ``m2t_loss`` entry: the order in which the terms came to the file format, kept so that a
+# checkpoint comes out byte for byte as it always did.  The names are those of train_step.LOSS_TERMS plus the perceptual term.
+LOSS_KEY_ORDER = ("ssim", "msssim", "fft", "vif", "perceptual", "gmsd", "wavelet", "consistency")
+
+
 def _pixel_loss(train_step):
     """The ``m2t_loss`` entry of a step object, or None for L1 with every optional term off (and for an object that knows no pixel
     losses)."""
-    from .train_step import LATER_LOSS_TERMS, LOSS_TERMS, MORE_LOSS_TERMS, resolve_pixel_loss
+    from .train_step import resolve_pixel_loss
     _, canon, value = resolve_pixel_loss(getattr(train_step, "pixel_loss", "l1"), getattr(train_step, "pixel_loss_param", None))
-    # (the entry keeps the order it always had -- LOSS_TERMS, then the perceptual term -- and the later rows follow it)
-    # (... and the consistency term, which has no row in the table, follows the rows)
-    names = [t.name for t in LOSS_TERMS] + ["perceptual"] + [t.name for t in MORE_LOSS_TERMS + LATER_LOSS_TERMS] + ["consistency"]
-    lam = {n: float(getattr(train_step, f"lambda_{n}", 0.0) or 0.0) for n in names}
+    lam = {n: float(getattr(train_step, f"lambda_{n}", 0.0) or 0.0) for n in LOSS_KEY_ORDER}
     if canon == "l1" and not any(lam.values()):
         return None
     out = {"pixel_loss": canon, "param": value}
-    for n in names:
+    for n in LOSS_KEY_ORDER:
         if lam[n] == 0.0:
             continue
         out[f"lambda_{n}"] = lam[n]
@@ -255,8 +257,8 @@ def import_checkpoint(ckpt: dict, model, train_step=None) -> int:
         else:
             from .train_step import resolve_pixel_loss
             _, train_step.pixel_loss, train_step.pixel_loss_param = resolve_pixel_loss(ml["pixel_loss"], ml.get("param"))
-        from .train_step import ALL_LOSS_TERMS, resolve_fft_norm, resolve_lambda, resolve_wavelet
-        for t in ALL_LOSS_TERMS:       # (a file without a term's key leaves that weight alone: 0 on a fresh step)
+        from .train_step import LOSS_TERMS, resolve_consistency_eps, resolve_fft_norm, resolve_lambda, resolve_wavelet
+        for t in LOSS_TERMS:           # (a file without a term's key leaves that weight alone: 0 on a fresh step)
             key = f"lambda_{t.name}"
             if key not in ml:
                 continue
@@ -270,6 +272,8 @@ def import_checkpoint(ckpt: dict, model, train_step=None) -> int:
                 if hasattr(train_step, "wavelet_band_weights"):
                     train_step.wavelet_band_weights = None
                 more = (w.wavelet, w.levels, w.band_weights, w.eps)
+            if t.name == "consistency":
+                more = (ml.get("consistency_eps", 0.0),)
             if hasattr(train_step, f"set_{key}"):
                 getattr(train_step, f"set_{key}")(ml[key], *more)
             else:
@@ -280,13 +284,8 @@ def import_checkpoint(ckpt: dict, model, train_step=None) -> int:
                 if t.name == "wavelet":
                     train_step.wavelet, train_step.wavelet_levels, train_step.wavelet_eps = w.wavelet, w.levels, w.eps
                     train_step.wavelet_band_weights = None if w.band_weights is None else list(w.band_weights)
-        if "lambda_consistency" in ml:
-            from .train_step import resolve_consistency_eps
-            if hasattr(train_step, "set_lambda_consistency"):
-                train_step.set_lambda_consistency(ml["lambda_consistency"], ml.get("consistency_eps", 0.0))
-            else:
-                train_step.lambda_consistency = resolve_lambda("consistency", ml["lambda_consistency"])
-                train_step.consistency_eps = resolve_consistency_eps(ml.get("consistency_eps", 0.0))
+                if t.name == "consistency":
+                    train_step.consistency_eps = resolve_consistency_eps(more[0])
         if "lambda_perceptual" in ml:
             p = getattr(train_step, "perceptual_loss", None)
             if p is None:

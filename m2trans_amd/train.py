@@ -29,7 +29,7 @@ import torch
 
 from . import _lib, augment
 from ._lib import M2TError
-from .train_step import ALL_LOSS_TERMS, LOSS_TERMS, MORE_LOSS_TERMS, cosine_lr
+from .train_step import LOSS_TERMS, cosine_lr
 
 EVAL_SETS = {"CCA-US": "UI5", "US-CASE": "US15", "US1K_23": "US1K_23"}        # datas/utils.py:27-43: name -> benchmark/<folder>
 
@@ -95,10 +95,8 @@ class StepMeter:
 
 def meter_columns(train_step) -> List[str]:
     """The columns `fit` meters for this step object: the total loss, the pixel term, the clip term, every optional term that is on
-    (ALL_LOSS_TERMS, then consistency, then the perceptual term) and, when the step tracks them, the gradient norm and the clip coefficient."""
-    names = ["loss", "pixel", "clip"] + [t.name for t in ALL_LOSS_TERMS if getattr(train_step, f"lambda_{t.name}", 0.0) > 0.0]
-    if getattr(train_step, "lambda_consistency", 0.0) > 0.0:
-        names.append("consistency")
+    (LOSS_TERMS, then the perceptual term) and, when the step tracks them, the gradient norm and the clip coefficient."""
+    names = ["loss", "pixel", "clip"] + [t.name for t in LOSS_TERMS if getattr(train_step, f"lambda_{t.name}", 0.0) > 0.0]
     if getattr(train_step, "lambda_perceptual", 0.0) > 0.0:
         names.append("perceptual")
     if getattr(train_step, "grad_norm", None) is not None:

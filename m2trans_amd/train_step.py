@@ -30,8 +30,8 @@ L1_Charbonnier_loss): the kind only selects the per-pixel function inside the ke
 m2t_pixel_loss_deferred), so every kind runs the schedule of the L1 step -- the seed fused into the x4 tail backward, accumulation,
 the overlapped exchange and the optimizer options included.
 
-Optional loss terms (all off by default; LOSS_TERMS, MORE_LOSS_TERMS and LATER_LOSS_TERMS below are their table, and its order -- SSIM, MS-SSIM, FFT,
-VIF, GMSD, wavelet, then consistency and the perceptual term, which have paths of their own -- is the order of the calls).  Every term that is on takes the MATERIALISED seed: the immediate pixel loss, then one
+Optional loss terms (all off by default; LOSS_TERMS below is their one table, and its order -- SSIM, MS-SSIM, FFT, VIF, GMSD, wavelet,
+consistency, then the perceptual term, which has a path of its own behind the table -- is the order of the calls).  Every term that is on takes the MATERIALISED seed: the immediate pixel loss, then one
 ``m2t_<term>_loss`` call per term that adds its gradient into the seed, then the backward pass; the seed fused into the x4 tail
 backward does not apply.  An SR size a term does not take is refused on the host before anything is launched.  With a weight of 0
 nothing is allocated for the term and the step issues the calls it issued before.  Value and gradient are HIP, fp64 inside unless
@@ -60,12 +60,11 @@ said otherwise.
   its scales through a Haar DWT): ``lambda_wavelet * mean`` over the coefficients of ``sum_band w_band rho(c_band)`` on the undecimated
   (stationary) wavelet transform of ``clamp(sr, 0, rgb_range) / rgb_range - hr / rgb_range`` with periodic borders: ``'haar'``, ``'db2'``
   or a pair of tap lists, 1 .. 3 levels, by default an L1 on every detail band and nothing on LL (m2t_wavelet_loss of
-  include/m2t_wavelet.h; SR height and width >= (taps - 1) * 2^(levels - 1) + 1).  The row sits in LATER_LOSS_TERMS, behind GMSD.
+  include/m2t_wavelet.h; SR height and width >= (taps - 1) * 2^(levels - 1) + 1).
 * ``lambda_consistency``, ``consistency_eps`` (the "dual regression" / cycle term; the only one that compares with the LR input and
   not with HR): ``lambda_consistency * mean rho((D(clamp(sr, 0, rgb_range)) - lr) / rgb_range)`` over the LR elements, D the bicubic
   down-sampler that made the training pairs, rho = |.| or Charbonnier with ``consistency_eps`` (m2t_consistency_loss of
-  include/m2t_consistency.h).  Its target is the step's own ``lr_img``, so it has a path of its own beside the table, called behind
-  the table's rows and in front of the perceptual term.
+  include/m2t_consistency.h).  Its target is the step's own ``lr_img``, which also sizes its scratch: the last row of the table.
 * ``lambda_perceptual``, ``perceptual_loss=`` (PerceptualLoss of the reference's losses.py:222-270): ``lambda_perceptual * sum_k w_k
   mean(crit(F_k(sr) - F_k(hr)))`` on VGG19 features; the tower, its weights, its workspace, the criterion and the tap weights are
   those of the losses.PerceptualLoss object (m2t_vgg_loss of include/m2t_perceptual.h, bf16 compute; SR height and width >= 16).
@@ -277,19 +276,23 @@ def fft_size_supported(n: int) -> bool:
 
 class LossTerm(NamedTuple):
     """One optional term whose scratch the step owns.  From the name follow the step's attributes ``lambda_<n>`` (weight, 0 = off),
-    ``<n>_loss`` (device float [1], already weighted: this rank's share of the global mean) and ``_<n>_scratch`` ((B, Hs, Ws) -> the
-    kernels' scratch, allocated once per plan shape), and the entries ``m2t_<n>_loss`` / ``m2t_<n>_loss_scratch_bytes``; the fields
-    are what differs between the terms.  The two refusals follow "lambda_<n> > 0: " and are formatted with B, Hs, Ws."""
+    ``<n>_loss`` (device float [1], already weighted: this rank's share of the global mean) and ``_<n>_scratch`` ((B, H, W) of the
+    target -> the kernels' scratch, allocated once per plan shape), and the entries ``m2t_<n>_loss`` / ``m2t_<n>_loss_scratch_bytes``;
+    the fields are what differs between the terms.  The two refusals follow "lambda_<n> > 0: " and are formatted with B, Hs, Ws of the
+    target (and, by position, with scratch_tail)."""
     name: str
-    size_ok: Callable       # (Hs, Ws) -> bool: the SR sizes the kernels take, decided on the host
+    size_ok: Callable       # (Hs, Ws) -> bool: the target sizes the kernels take, decided on the host
     too_small: str          # the refusal of a size outside that rule
     no_scratch: str         # the refusal of a shape the library names no scratch size for
     count: Callable         # (B, Hs, Ws) -> what the term's mean runs over on this rank (the global divisor is built from it)
     extra: Callable         # (step) -> the term's own arguments of m2t_<n>_loss, between rgb_range and the value
     shape_args: Callable = lambda step: ()      # (step) -> what size_ok and m2t_<n>_loss_scratch_bytes take behind the sizes
+    target: str = "hr_img"                      # the image of the (micro-)batch the term holds SR against: it sizes count and scratch
+    scratch_entry: Optional[str] = None         # the scratch size entry, where it is not m2t_<n>_loss_scratch_bytes
+    scratch_tail: Callable = lambda step: ()    # (step) -> that entry's trailing arguments that are no part of the shape
 
 
-# in call order: pixel -> these (each if on) -> MORE_LOSS_TERMS (each if on) -> the perceptual term (if on) -> backward
+# in call order: pixel -> these (each if on) -> the perceptual term (if on) -> backward
 LOSS_TERMS = (
     LossTerm("ssim", lambda hs, ws: min(hs, ws) >= 11,
              "the SR image {Hs}x{Ws} is smaller than the 11 x 11 SSIM window",
@@ -312,17 +315,11 @@ LOSS_TERMS = (
              "no scratch size for a batch of {B} SR images {Hs}x{Ws} (B <= 65535)",
              lambda b, hs, ws: b,                                     # images (luminance: not times 3)
              lambda step: (_lib.VIF_SIGMA_N_SQ,)),
-)
-# the rows that came after LOSS_TERMS was pinned to its four names: the same type, iterated directly behind it everywhere
-MORE_LOSS_TERMS = (
     LossTerm("gmsd", gmsd_size_supported,
              "the SR image {Hs}x{Ws} is smaller than one 2 x 2 cell (height and width must be at least 2)",
              "no scratch size for a batch of {B} SR images {Hs}x{Ws} (B <= 65535)",
              lambda b, hs, ws: b,                                     # images (luminance: not times 3)
              lambda step: ()),
-)
-# ... and the rows that came after MORE_LOSS_TERMS was pinned to its one name
-LATER_LOSS_TERMS = (
     LossTerm("wavelet", wavelet_size_supported,
              "the SR image {Hs}x{Ws} is smaller than the reach of the filters (height and width must be at least (taps - 1) * "
              "2^(levels - 1) + 1)",
@@ -330,9 +327,14 @@ LATER_LOSS_TERMS = (
              lambda b, hs, ws: b * 3 * hs * ws,                       # coefficients of one band
              lambda step: step._wavelet_args(),
              lambda step: step._wavelet_shape_args()),
+    # the one term held against the LR input: every LR size is taken, the library alone decides whether it names a scratch size
+    LossTerm("consistency", lambda h0, w0: True, "",
+             "no scratch size for a batch of {B} LR images {Hs}x{Ws} at scale {0} (B * 3 <= 65535, SR sides at most 16384)",
+             lambda b, h0, w0: b * 3 * h0 * w0,                       # LR elements
+             lambda step: (float(step.consistency_eps),),
+             target="lr_img", scratch_entry="m2t_consistency_scratch_bytes", scratch_tail=lambda step: (int(step.model.scale),)),
 )
-ALL_LOSS_TERMS = LOSS_TERMS + MORE_LOSS_TERMS + LATER_LOSS_TERMS
-_TERM = {t.name: t for t in ALL_LOSS_TERMS}
+_TERM = {t.name: t for t in LOSS_TERMS}
 
 
 _STREAMS: dict = {}
@@ -359,15 +361,14 @@ class TrainStep:
     # The state of the optional terms, off: what __init__ starts from and what a step object assembled without __init__ has.  A term
     # of LOSS_TERMS has its weight, its device [1] value and its per-shape scratch cache (None: the dict is made per object, on first
     # use or by the setter); the perceptual term keeps its value next to the PerceptualLoss object, whose workspace is its own.
-    lambda_ssim = lambda_msssim = lambda_fft = lambda_vif = lambda_gmsd = lambda_wavelet = lambda_perceptual = 0.0
-    ssim_loss = msssim_loss = fft_loss = vif_loss = gmsd_loss = wavelet_loss = perceptual_loss_value = None
-    _ssim_scratch = _msssim_scratch = _fft_scratch = _vif_scratch = _gmsd_scratch = _wavelet_scratch = None
+    lambda_ssim = lambda_msssim = lambda_fft = lambda_vif = lambda_gmsd = lambda_wavelet = lambda_consistency = lambda_perceptual = 0.0
+    ssim_loss = msssim_loss = fft_loss = vif_loss = gmsd_loss = wavelet_loss = consistency_loss = perceptual_loss_value = None
+    _ssim_scratch = _msssim_scratch = _fft_scratch = _vif_scratch = _gmsd_scratch = _wavelet_scratch = _consistency_scratch = None
     wavelet, wavelet_levels, wavelet_band_weights, wavelet_eps = "haar", 2, None, 0.0
     _wavelet_call = None          # the C arguments of the wavelet term, made by the setter or on first use
     fft_norm = "backward"
+    consistency_eps = 0.0
     perceptual_loss = None
-    # the LR-consistency term: its target is the step's own lr_img, so it has a path of its own beside the table
-    lambda_consistency, consistency_eps, consistency_loss, _consistency_scratch = 0.0, 0.0, None, None
     groups = None
     _need_stage = None
 
@@ -583,53 +584,6 @@ class TrainStep:
         a = self._wavelet_args()
         return a[3], a[2]                           # levels, taps
 
-    def _scratch_for(self, term: LossTerm, lib, hr_img):
-        """The scratch of one term for this (micro-)batch shape, allocated once; an SR size the term does not take is refused here,
-        on the host, before anything is launched."""
-        n = term.name
-        B, _, Hs, Ws = hr_img.shape
-        cache = getattr(self, f"_{n}_scratch")
-        if cache is None:
-            cache = {}
-            setattr(self, f"_{n}_scratch", cache)
-        more = term.shape_args(self)
-        key = (B, Hs, Ws) + more
-        if key not in cache:
-            if not term.size_ok(Hs, Ws, *more):
-                raise _lib.M2TError(f"lambda_{n} > 0: " + term.too_small.format(B=B, Hs=Hs, Ws=Ws))
-            nbytes = int(getattr(lib, f"m2t_{n}_loss_scratch_bytes")(B, 3, Hs, Ws, *more))
-            if nbytes == 0:
-                raise _lib.M2TError(f"lambda_{n} > 0: " + term.no_scratch.format(B=B, Hs=Hs, Ws=Ws))
-            cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=hr_img.device)
-        return cache[key]
-
-    def _msssim_scratch_for(self, lib, hr_img):
-        return self._scratch_for(_TERM["msssim"], lib, hr_img)
-
-    def _fft_scratch_for(self, lib, hr_img):
-        return self._scratch_for(_TERM["fft"], lib, hr_img)
-
-    def _vif_scratch_for(self, lib, hr_img):
-        return self._scratch_for(_TERM["vif"], lib, hr_img)
-
-    @staticmethod
-    def _store_or_add(first: bool) -> int:
-        """The accumulate flag of every m2t_*_loss call: a term's value is stored by the first micro-batch of a cycle and added to
-        by the others."""
-        return 0 if first else 1
-
-    def _term_call(self, term: LossTerm, lib, plan, hr_img, first: bool, ws, st):
-        """m2t_<n>_loss of one (micro-)batch, behind the immediate pixel loss and the terms in front of it: adds into the
-        materialised seed.  The divisor is the GLOBAL count of what the term's mean runs over."""
-        n = term.name
-        B, _, Hs, Ws = hr_img.shape
-        divisor = global_divisor(term.count(B, Hs, Ws), self.world_size, self.accum_steps)
-        entry = f"m2t_{n}_loss"
-        _lib.check(getattr(lib, entry)(plan.handle, _lib.ptr(hr_img), getattr(self, f"lambda_{n}"), divisor, float(self.model.rgb_range),
-                                       *term.extra(self), _lib.ptr(getattr(self, f"{n}_loss")), self._store_or_add(first),
-                                       _lib.ptr(self._scratch_for(term, lib, hr_img)), ws, st), entry)
-
-    # -- the LR-consistency term: the same slot in the order and in the total; its target is lr_img, its scratch is sized by the LR ---
     def set_lambda_consistency(self, value, eps=None):
         """Weight of the LR-consistency term (0 = off) and, when given, its eps (0 = L1, > 0 = Charbonnier): ``lambda_consistency *
         mean rho((D(clamp(sr)) - lr) / rgb_range)`` over the LR elements, D the bicubic down-sampler of the model's scale
@@ -639,35 +593,45 @@ class TrainStep:
         lam = resolve_lambda("consistency", value)      # (a refused weight leaves eps as it was)
         if eps is not None:
             self.consistency_eps = resolve_consistency_eps(eps)
-        self.lambda_consistency = lam
-        if lam > 0.0:
-            if self.consistency_loss is None:
-                self.consistency_loss = torch.zeros(1, dtype=torch.float32, device=self.model.flat_params.device)
-        else:
-            self.consistency_loss = None
-            self._consistency_scratch = {}
+        self._set_lambda(_TERM["consistency"], lam)
 
-    def _consistency_scratch_for(self, lib, lr_img, hr_img=None):
-        """The term's scratch for this (micro-)batch shape, allocated once per shape."""
-        B, _, H0, W0 = lr_img.shape
-        if self._consistency_scratch is None:
-            self._consistency_scratch = {}
-        key = (B, H0, W0)
-        if key not in self._consistency_scratch:
-            nbytes = int(lib.m2t_consistency_scratch_bytes(B, 3, H0, W0, int(self.model.scale)))
+    def _scratch_for(self, term: LossTerm, lib, img):
+        """The scratch of one term for this (micro-)batch shape, allocated once; img is the term's target (hr_img, or lr_img for the
+        consistency term).  A size the term does not take is refused here, on the host, before anything is launched."""
+        n = term.name
+        B, _, Hs, Ws = img.shape
+        cache = getattr(self, f"_{n}_scratch")
+        if cache is None:
+            cache = {}
+            setattr(self, f"_{n}_scratch", cache)
+        more = term.shape_args(self)
+        key = (B, Hs, Ws) + more
+        if key not in cache:
+            if not term.size_ok(Hs, Ws, *more):
+                raise _lib.M2TError(f"lambda_{n} > 0: " + term.too_small.format(B=B, Hs=Hs, Ws=Ws))
+            tail = term.scratch_tail(self)
+            nbytes = int(getattr(lib, term.scratch_entry or f"m2t_{n}_loss_scratch_bytes")(B, 3, Hs, Ws, *more, *tail))
             if nbytes == 0:
-                raise _lib.M2TError(f"lambda_consistency > 0: no scratch size for a batch of {B} LR images {H0}x{W0} at scale "
-                                    f"{self.model.scale} (B * 3 <= 65535, SR sides at most 16384)")
-            self._consistency_scratch[key] = torch.empty(nbytes, dtype=torch.uint8, device=lr_img.device)
-        return self._consistency_scratch[key]
+                raise _lib.M2TError(f"lambda_{n} > 0: " + term.no_scratch.format(*tail, B=B, Hs=Hs, Ws=Ws))
+            cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
+        return cache[key]
 
-    def _consistency_loss_call(self, lib, lr_img, plan, hr_img, first: bool, ws, st):
-        """m2t_consistency_loss of one (micro-)batch, behind the immediate pixel loss and the table's terms: adds into the materialised
-        seed.  The divisor is the GLOBAL number of LR elements."""
-        divisor = global_divisor(lr_img.numel(), self.world_size, self.accum_steps)
-        _lib.check(lib.m2t_consistency_loss(plan.handle, _lib.ptr(lr_img), self.lambda_consistency, divisor, float(self.model.rgb_range),
-                                            float(self.consistency_eps), _lib.ptr(self.consistency_loss), self._store_or_add(first),
-                                            _lib.ptr(self._consistency_scratch_for(lib, lr_img)), ws, st), "m2t_consistency_loss")
+    @staticmethod
+    def _store_or_add(first: bool) -> int:
+        """The accumulate flag of every m2t_*_loss call: a term's value is stored by the first micro-batch of a cycle and added to
+        by the others."""
+        return 0 if first else 1
+
+    def _term_call(self, term: LossTerm, lib, img, plan, first: bool, ws, st):
+        """m2t_<n>_loss of one (micro-)batch against the term's target img, behind the immediate pixel loss and the terms in front of
+        it: adds into the materialised seed.  The divisor is the GLOBAL count of what the term's mean runs over."""
+        n = term.name
+        B, _, Hs, Ws = img.shape
+        divisor = global_divisor(term.count(B, Hs, Ws), self.world_size, self.accum_steps)
+        entry = f"m2t_{n}_loss"
+        _lib.check(getattr(lib, entry)(plan.handle, _lib.ptr(img), getattr(self, f"lambda_{n}"), divisor, float(self.model.rgb_range),
+                                       *term.extra(self), _lib.ptr(getattr(self, f"{n}_loss")), self._store_or_add(first),
+                                       _lib.ptr(self._scratch_for(term, lib, img)), ws, st), entry)
 
     # -- the perceptual term: the same slot in the order and in the total, its own preconditions, workspace and call ---------------
     def set_lambda_perceptual(self, value):
@@ -701,7 +665,7 @@ class TrainStep:
                                 "pools before relu5_1)")
         return self.perceptual_loss.workspace(B, Hs, Ws, True)
 
-    def _perceptual_loss_call(self, lib, plan, hr_img, first: bool, ws, st):
+    def _perceptual_loss_call(self, lib, hr_img, plan, first: bool, ws, st):
         """m2t_vgg_loss of one (micro-)batch, behind the immediate pixel loss and the other terms: adds into the materialised seed."""
         p = self.perceptual_loss
         divisor = global_divisor(hr_img.shape[0], self.world_size, self.accum_steps)     # global number of images
@@ -710,18 +674,18 @@ class TrainStep:
                                     _lib.ptr(self._perceptual_workspace_for(hr_img)), ws, st), "m2t_vgg_loss")
 
     # -- what forward_backward iterates ------------------------------------------------------------------------------------
-    def _terms_on(self, lib, lr_img=None) -> list:
-        """The optional terms that are on, in call order -- the rows of ALL_LOSS_TERMS, then consistency, then the perceptual term --
-        each as (value, prepare, call): the term's device [1] tensor; prepare(hr_img), which refuses an SR size the term does not
-        take and makes sure of its scratch before anything is launched; call(plan, hr_img, first, ws, st), its m2t_*_loss call.
-        lr_img: the (micro-)batch's LR tensor, the target of the consistency term."""
-        on = [(getattr(self, f"{t.name}_loss"), functools.partial(self._scratch_for, t, lib), functools.partial(self._term_call, t, lib))
-              for t in ALL_LOSS_TERMS if getattr(self, f"lambda_{t.name}") > 0.0]
-        if self.lambda_consistency > 0.0:
-            on.append((self.consistency_loss, functools.partial(self._consistency_scratch_for, lib, lr_img),
-                       functools.partial(self._consistency_loss_call, lib, lr_img)))
+    def _terms_on(self, lib, lr_img, hr_img) -> list:
+        """The optional terms that are on, in call order -- the rows of LOSS_TERMS, then the perceptual term -- each as (value,
+        prepare, call) bound to its target image of this (micro-)batch: the term's device [1] tensor; prepare(), which refuses a size
+        the term does not take and makes sure of its scratch before anything is launched; call(plan, first, ws, st), its m2t_*_loss
+        call."""
+        images = {"lr_img": lr_img, "hr_img": hr_img}
+        on = [(getattr(self, f"{t.name}_loss"), functools.partial(self._scratch_for, t, lib, images[t.target]),
+               functools.partial(self._term_call, t, lib, images[t.target]))
+              for t in LOSS_TERMS if getattr(self, f"lambda_{t.name}") > 0.0]
         if self.lambda_perceptual > 0.0:
-            on.append((self.perceptual_loss_value, self._perceptual_workspace_for, functools.partial(self._perceptual_loss_call, lib)))
+            on.append((self.perceptual_loss_value, functools.partial(self._perceptual_workspace_for, hr_img),
+                       functools.partial(self._perceptual_loss_call, lib, hr_img)))
         return on
 
     def _total_loss(self, on: list, with_clip: bool):
@@ -788,9 +752,9 @@ class TrainStep:
         B = lr_img.shape[0]
         if tuple(hr_img.shape) != (B, 3, lr_img.shape[2] * m.scale, lr_img.shape[3] * m.scale):
             raise _lib.M2TError("hr shape must be [B,3,H*scale,W*scale]")
-        on = self._terms_on(lib, lr_img)
+        on = self._terms_on(lib, lr_img, hr_img)
         for _, prepare, _ in on:
-            prepare(hr_img)                         # (refuses an SR size the term does not take before any launch)
+            prepare()                               # (refuses an SR size the term does not take before any launch)
         divisor = global_divisor(hr_img.numel(), self.world_size, self.accum_steps)      # global mean (equal shards, equal micro-batches)
         use_clip = self.semantic_loss is not None and self.lambda_clip > 0 and captions is not None
         # (micro-batches 2..k of a cycle: a second gradient buffer and a second loss slot, added to the first ones below)
@@ -813,7 +777,7 @@ class TrainStep:
             #  of _terms_on)
             self._pixel_loss_call(lib, not on, plan, hr_img, divisor, l1_loss, ws, st)
             for _, _, call in on:
-                call(plan, hr_img, first, ws, st)
+                call(plan, first, ws, st)
             fwd_done = torch.cuda.current_stream(lr_img.device).record_event() if (use_clip and self.overlap_semantic) else None
             self._backward_call(lib, plan, lr_img, grads, ws, st)
             self._accumulate_micro(lib, first, st)
@@ -872,7 +836,7 @@ class TrainStep:
             tot, g, origins = sl._value_and_grad(sr, hr_img, captions)
             self._pixel_loss_call(lib, False, plan, hr_img, divisor, l1_loss, ws, st)
             for _, _, call in on:
-                call(plan, hr_img, first, ws, st)
+                call(plan, first, ws, st)
             g = g.contiguous()
             arr = None
             if origins is not None:

@@ -31,8 +31,8 @@ def test_interface_reaches_from_the_constructor_to_the_exported_symbol():
         assert isinstance(global_divisor(n, w, k), float)
     par = inspect.signature(TrainStep.__init__).parameters
     assert "accum_steps" in par and par["accum_steps"].default == 1
-    assert "m2t_grad_accumulate" in _lib.SIGNATURES
-    res, args = _lib.SIGNATURES["m2t_grad_accumulate"]
+    assert "m2t_grad_accumulate" in _lib.ABI["m2t.h"]
+    res, args = _lib.ABI["m2t.h"]["m2t_grad_accumulate"]
     assert res is C.c_int and args == [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
     hdr = open(os.path.join(ROOT, "include", "m2t.h")).read()
     assert re.search(r"\bint\s+m2t_grad_accumulate\s*\(\s*float\*\s*acc,\s*const float\*\s*g,\s*long long n,\s*float\*\s*loss_acc,"

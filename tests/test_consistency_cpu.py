@@ -24,38 +24,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ------------------------------------------------------------------------------------------------------------- C ABI
-def _clean(header):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-
-
-def test_header_table_and_library_agree():
-    from m2trans_amd import _lib, build as B
-    vp, i, f, d, ll = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_longlong
-    src = _clean("m2t_consistency.h")
-    names = ["m2t_consistency_scratch_bytes", "m2t_imresize_adjoint_f32", "m2t_consistency_loss_tensor", "m2t_consistency_loss",
-             "m2t_back_project_f32"]
-    assert re.findall(r"\b(m2t_[a-z0-9_]+)\s*\(", src) == list(_lib.CONSISTENCY_SIGNATURES) == names
-    ctype = {"int": i, "float": f, "double": d, "long long": ll, "size_t": C.c_size_t}
-    for name, (res, args) in _lib.CONSISTENCY_SIGNATURES.items():
-        m = re.search(r"([a-z_0-9]+)\s+" + name + r"\s*\(([^)]*)\)\s*;", src)
-        types_ = [" ".join(a.split()[:-1]) for a in m.group(2).split(",")]
-        assert ctype[m.group(1)] == res, name
-        assert [vp if t.endswith("*") else ctype[t] for t in types_] == args, (name, types_)
-    assert len(_lib.CONSISTENCY_SIGNATURES["m2t_consistency_loss_tensor"][1]) == 19
-    assert len(_lib.CONSISTENCY_SIGNATURES["m2t_back_project_f32"][1]) == 13
-    older = [_lib.SIGNATURES, _lib.SPECTRAL_SIGNATURES, _lib.RESIZE_SIGNATURES, _lib.MSSSIM_SIGNATURES, _lib.VIF_SIGNATURES,
-             _lib.GROUPS_SIGNATURES, _lib.PERCEPTUAL_SIGNATURES, _lib.RLUTRANS_SIGNATURES, _lib.INFER_SIGNATURES, _lib.TRAIN_SIGNATURES,
-             _lib.TILES_SIGNATURES, _lib.GMSD_SIGNATURES, _lib.DEGRADE_SIGNATURES, _lib.JPEG_SIGNATURES, _lib.WAVELET_SIGNATURES,
-             _lib.TEXT_SIGNATURES, _lib.SWIN_SIGNATURES]
-    every = [n for t in older + [_lib.CONSISTENCY_SIGNATURES] for n in t]
-    assert len(every) == len(set(every)) and not any("consistency" in n or "back_project" in n for t in older for n in t)
-    assert "k_consistency.hip" in B.SOURCES and "m2t_consistency_tile.h" in B.HEADERS and any(h.endswith("m2t_consistency.h") for h in B.HEADERS)
-    lib = _lib.load()
-    for name in names:
-        assert hasattr(lib, name)
-    assert lib.m2t_back_project_f32.argtypes == _lib.CONSISTENCY_SIGNATURES["m2t_back_project_f32"][1]
-
-
 def test_entry_points_decide_sizes_and_bad_arguments_on_the_host():
     from m2trans_amd import _lib
     lib = _lib.load()
@@ -216,8 +184,20 @@ def test_lambda_consistency_default_resolver_and_setter():
             T.resolve_consistency_eps(bad)
     with pytest.raises(M2TError, match="lambda_consistency"):
         T.TrainStep(None, lambda_consistency=-1.0)
-    # the table and its three pinned tuples are as they were: the term has a path of its own
-    assert "consistency" not in [t.name for t in T.ALL_LOSS_TERMS] and T.ALL_LOSS_TERMS == T.LOSS_TERMS + T.MORE_LOSS_TERMS + T.LATER_LOSS_TERMS
+    # the last row of the one table: held against the LR image, which sizes its count and its scratch; the scratch entry has a name of
+    # its own and takes the scale behind the shape
+    row = T._TERM["consistency"]
+    assert isinstance(row, T.LossTerm) and T.LOSS_TERMS[-1] is row and row.target == "lr_img"
+    assert [t.target for t in T.LOSS_TERMS[:-1]] == ["hr_img"] * 6 and all(t.scratch_entry is None for t in T.LOSS_TERMS[:-1])
+    assert row.count(2, 96, 96) == 2 * 3 * 96 * 96 and row.size_ok(1, 1) and row.shape_args(None) == ()
+    assert row.scratch_entry == "m2t_consistency_scratch_bytes"
+    stand_in = types.SimpleNamespace(model=types.SimpleNamespace(scale=3), consistency_eps=1e-3)
+    assert row.scratch_tail(stand_in) == (3,) and row.extra(stand_in) == (1e-3,)
+    none = T.TrainStep.__new__(T.TrainStep)
+    none.model = stand_in.model
+    with pytest.raises(M2TError, match=r"lambda_consistency > 0: no scratch size for a batch of 2 LR images 8x9 at scale 3 \(B \* 3 <= 65535, "
+                                       r"SR sides at most 16384\)"):
+        none._scratch_for(row, types.SimpleNamespace(m2t_consistency_scratch_bytes=lambda *a: 0), torch.zeros(2, 3, 8, 9))
     ts = T.TrainStep.__new__(T.TrainStep)
     ts.accum_steps, ts.micro_count = 2, 1
     with pytest.raises(M2TError, match="accumulation cycle"):

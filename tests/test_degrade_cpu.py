@@ -25,44 +25,10 @@ def _strip(header):
     return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
 
 
-def _declared(header):
-    return re.findall(r"\b(m2t_[a-z0-9_]+)\s*\(", _strip(header))
-
-
-def _prototype(header, name):
-    m = re.search(r"([a-z_0-9]+)\s+" + name + r"\s*\(([^)]*)\)\s*;", _strip(header))
-    return m.group(1), [" ".join(a.split()[:-1]) for a in m.group(2).split(",")]
-
-
-def test_header_table_and_library_agree_and_the_older_tables_keep_their_sizes():
+def test_descriptor_width_is_the_headers_and_a_tap_keeps_its_two_roundings():
     from m2trans_amd import _lib, build as B
-    vp, i, d, ull = C.c_void_p, C.c_int, C.c_double, C.c_ulonglong
-    assert _declared("m2t_degrade.h") == list(_lib.DEGRADE_SIGNATURES) == ["m2t_degrade_patches", "m2t_degrade_image_u8"]
-    assert _lib.DEGRADE_SIGNATURES["m2t_degrade_patches"] == (i, [vp, vp, i, i, vp, i, i, i, i, ull, vp, vp, vp])
-    assert _lib.DEGRADE_SIGNATURES["m2t_degrade_image_u8"] == (i, [vp, i, i, i, vp, i, i, i, i, ull, ull, d, d, i, vp, vp])
-    ctype = {"int": i, "double": d, "unsigned long long": ull}
-    for name, (res, args) in _lib.DEGRADE_SIGNATURES.items():
-        ret, types_ = _prototype("m2t_degrade.h", name)
-        assert ctype[ret] == res, name
-        assert [vp if t.endswith("*") else ctype[t] for t in types_] == args, (name, types_)
-    assert _prototype("m2t_degrade.h", "m2t_degrade_patches")[1] == [
-        "const unsigned char*", "const double*", "int", "int", "const long long*", "int", "int", "int", "int", "unsigned long long", "float*",
-        "float*", "void*"]
-    assert _prototype("m2t_degrade.h", "m2t_degrade_image_u8")[1] == [
-        "const unsigned char*", "int", "int", "int", "const double*", "int", "int", "int", "int", "unsigned long long", "unsigned long long",
-        "double", "double", "int", "unsigned char*", "void*"]
     assert int(re.search(r"#define M2T_DEGRADE_DESC_COLS (\d+)", _strip("m2t_degrade.h")).group(1)) == _lib.DEGRADE_DESC_COLS
-    older = [_lib.SIGNATURES, _lib.SPECTRAL_SIGNATURES, _lib.RESIZE_SIGNATURES, _lib.MSSSIM_SIGNATURES, _lib.VIF_SIGNATURES,
-             _lib.GROUPS_SIGNATURES, _lib.PERCEPTUAL_SIGNATURES, _lib.RLUTRANS_SIGNATURES, _lib.INFER_SIGNATURES, _lib.TRAIN_SIGNATURES,
-             _lib.TILES_SIGNATURES, _lib.GMSD_SIGNATURES]
-    assert [len(t) for t in older] == [68, 4, 2, 4, 4, 4, 13, 4, 3, 3, 3, 3]
-    names = [n for t in older + [_lib.DEGRADE_SIGNATURES] for n in t]
-    assert len(names) == len(set(names)) and not any("degrade" in n for t in older for n in t)
-    assert "k_degrade.hip" in B.SOURCES and "m2t_degrade_tile.h" in B.HEADERS and any(h.endswith("m2t_degrade.h") for h in B.HEADERS)
     assert "-ffp-contract=off" in B.FLAGS                      # the multiply and the add of a tap are two roundings
-    lib = _lib.load()
-    for name, (res, args) in _lib.DEGRADE_SIGNATURES.items():
-        assert getattr(lib, name).argtypes == args and getattr(lib, name).restype == res
 
 
 # ------------------------------------------------------------------------------------------------------------- the restatement

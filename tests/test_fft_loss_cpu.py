@@ -86,32 +86,6 @@ def test_the_listed_inputs_stay_off_the_kink(shape, seed):
 
 
 # ------------------------------------------------------------------------------------------------------------- C ABI
-def _declared(header):
-    return set(re.findall(r"\b(m2t_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "include", header)).read()))
-
-
-def test_spectral_header_table_and_library_agree():
-    """include/m2t_spectral.h <-> _lib.SPECTRAL_SIGNATURES <-> the symbols of libm2t.so: the three-way check test_host_cpu.py makes
-    for include/m2t.h, which together with its table stays as it was."""
-    from m2trans_amd import _lib
-    declared = _declared("m2t_spectral.h")
-    assert declared == {"m2t_fft_loss_scratch_bytes", "m2t_rfft2", "m2t_fft_loss_tensor", "m2t_fft_loss"}
-    assert declared == set(_lib.SPECTRAL_SIGNATURES), declared ^ set(_lib.SPECTRAL_SIGNATURES)
-    lib = _lib.load()
-    for name, (res, args) in _lib.SPECTRAL_SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == args, name
-    vp, i, f, d, ll = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_longlong
-    assert _lib.SPECTRAL_SIGNATURES["m2t_fft_loss_scratch_bytes"] == (C.c_size_t, [i, i, i, i])
-    assert _lib.SPECTRAL_SIGNATURES["m2t_rfft2"] == (i, [vp, vp, i, i, i, i, vp])
-    assert _lib.SPECTRAL_SIGNATURES["m2t_fft_loss_tensor"] == (i, [vp, vp, i, i, i, i, ll, i, f, i, i, d, vp, vp, i, vp, vp])
-    assert _lib.SPECTRAL_SIGNATURES["m2t_fft_loss"] == (i, [vp, vp, f, d, f, i, vp, i, vp, vp, vp])
-    # the first header and its table are untouched: no spectral name in either, and the two tables are disjoint
-    assert len(_lib.SIGNATURES) == 68 and not (set(_lib.SIGNATURES) & declared)
-    assert _declared("m2t.h") == set(_lib.SIGNATURES)
-    assert "fft" not in open(os.path.join(ROOT, "include", "m2t.h")).read().lower()
-
-
 def _supported(n):
     if n < 8 or n > 2048 or n % 2:
         return False

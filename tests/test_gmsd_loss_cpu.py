@@ -85,49 +85,6 @@ def test_identical_images_and_one_cell_images_give_zero_and_no_gradient():
 
 
 # ------------------------------------------------------------------------------------------------------------- C ABI
-def _declared(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return re.findall(r"\b(m2t_[a-z0-9_]+)\s*\(", src)
-
-
-def _prototype(header, name):
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    m = re.search(r"([a-z_0-9]+)\s+" + name + r"\s*\(([^)]*)\)\s*;", src)
-    return m.group(1), [" ".join(a.split()[:-1]) for a in m.group(2).split(",")]
-
-
-def test_header_table_and_library_agree_and_the_older_tables_keep_their_sizes():
-    from m2trans_amd import _lib, build as B
-    vp, i, f, d, ll = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_longlong
-    assert _declared("m2t_gmsd.h") == list(_lib.GMSD_SIGNATURES) == ["m2t_gmsd_loss_scratch_bytes", "m2t_gmsd_loss_tensor", "m2t_gmsd_loss"]
-    assert _lib.GMSD_SIGNATURES["m2t_gmsd_loss_scratch_bytes"] == (C.c_size_t, [i, i, i, i])
-    assert _lib.GMSD_SIGNATURES["m2t_gmsd_loss_tensor"] == (i, [vp, vp, i, i, i, i, ll, i, f, i, d, vp, vp, vp, i, vp, vp])
-    assert _lib.GMSD_SIGNATURES["m2t_gmsd_loss"] == (i, [vp, vp, f, d, f, vp, i, vp, vp, vp])
-    # the exact prototypes of the header, type by type
-    ctype = {"int": i, "float": f, "double": d, "long long": ll, "size_t": C.c_size_t}
-    for name, (res, args) in _lib.GMSD_SIGNATURES.items():
-        ret, types_ = _prototype("m2t_gmsd.h", name)
-        assert ctype[ret] == res, name
-        assert [vp if t.endswith("*") else ctype[t] for t in types_] == args, (name, types_)
-    assert _prototype("m2t_gmsd.h", "m2t_gmsd_loss_tensor")[1] == [
-        "const float*", "const float*", "int", "int", "int", "int", "long long", "int", "float", "int", "double", "float*", "float*",
-        "double*", "int", "void*", "void*"]
-    assert _prototype("m2t_gmsd.h", "m2t_gmsd_loss")[1] == ["m2t_plan*", "const float*", "float", "double", "float", "float*", "int", "void*",
-                                                           "void*", "void*"]
-    older = [_lib.SIGNATURES, _lib.SPECTRAL_SIGNATURES, _lib.RESIZE_SIGNATURES, _lib.MSSSIM_SIGNATURES, _lib.VIF_SIGNATURES,
-             _lib.GROUPS_SIGNATURES, _lib.PERCEPTUAL_SIGNATURES, _lib.RLUTRANS_SIGNATURES, _lib.INFER_SIGNATURES, _lib.TRAIN_SIGNATURES,
-             _lib.TILES_SIGNATURES]
-    assert [len(t) for t in older] == [68, 4, 2, 4, 4, 4, 13, 4, 3, 3, 3]
-    names = [n for t in older + [_lib.GMSD_SIGNATURES] for n in t]
-    assert len(names) == len(set(names)) and not any("gmsd_loss" in n for t in older for n in t)
-    assert "k_gmsd_loss.hip" in B.SOURCES and "m2t_gmsd_tile.h" in B.HEADERS and any(h.endswith("m2t_gmsd.h") for h in B.HEADERS)
-    lib = _lib.load()
-    for name in _lib.GMSD_SIGNATURES:
-        assert hasattr(lib, name)
-    assert lib.m2t_gmsd_loss_tensor.argtypes == _lib.GMSD_SIGNATURES["m2t_gmsd_loss_tensor"][1]
-
-
 def test_entry_points_decide_sizes_and_bad_arguments_on_the_host():
     from m2trans_amd import _lib
     lib = _lib.load()
@@ -191,10 +148,9 @@ def test_lambda_gmsd_default_resolver_setter_and_table():
             T.resolve_lambda_gmsd(bad)
     with pytest.raises(M2TError, match="lambda_gmsd"):
         T.TrainStep(None, lambda_gmsd=-1.0)
-    # the row: a second tuple of the same type, behind the four pinned names
-    assert [t.name for t in T.LOSS_TERMS] == ["ssim", "msssim", "fft", "vif"] and [t.name for t in T.MORE_LOSS_TERMS] == ["gmsd"]
-    row = T.MORE_LOSS_TERMS[0]
-    assert isinstance(row, T.LossTerm) and T._TERM["gmsd"] is row
+    # the row of the one table (its order: tests/test_loss_terms_cpu.py)
+    row = T._TERM["gmsd"]
+    assert isinstance(row, T.LossTerm) and row in T.LOSS_TERMS
     assert row.size_ok(2, 2) and row.size_ok(2, 500) and not row.size_ok(1, 500) and not row.size_ok(500, 1)
     assert row.count(7, 100, 200) == 7 and row.extra(None) == ()
     ts = T.TrainStep.__new__(T.TrainStep)

@@ -29,26 +29,8 @@ def test_library_exports_every_declared_symbol():
     lib = _lib.load()
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in include/m2t.h but not exported"
-    assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
+    assert declared == set(_lib.ABI["m2t.h"]), declared ^ set(_lib.ABI["m2t.h"])
     assert lib.m2t_version() >= 100
-
-
-def test_swin_observation_header_table_and_library_agree():
-    """include/m2t_swin.h <-> _lib.SWIN_SIGNATURES <-> libm2t.so: the image tower's encode / backward with every stage as an
-    extra output (tests/test_gpu_swin_stages.py) are the plain entries' arguments + one pointer; include/m2t.h keeps its entries"""
-    from m2trans_amd import _lib
-    from m2trans_amd import build as B
-    hdr = open(os.path.join(ROOT, "include", "m2t_swin.h")).read()
-    declared = set(re.findall(r"\b(m2t_[a-z0-9_]+)\s*\(", hdr)) - set(_lib.SIGNATURES)     # (the comments name entries of m2t.h)
-    assert declared == {"m2t_swin_encode_ex", "m2t_swin_backward_ex"} == set(_lib.SWIN_SIGNATURES)
-    assert not set(_lib.SWIN_SIGNATURES) & set(_lib.SIGNATURES)
-    assert any(h.endswith("m2t_swin.h") for h in B.HEADERS)
-    lib = _lib.load()
-    for name, (res, args) in _lib.SWIN_SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == args
-    assert _lib.SWIN_SIGNATURES["m2t_swin_encode_ex"][1] == _lib.SIGNATURES["m2t_swin_encode_pair"][1] + [C.c_void_p]
-    assert _lib.SWIN_SIGNATURES["m2t_swin_backward_ex"][1] == _lib.SIGNATURES["m2t_swin_backward"][1] + [C.c_void_p]
 
 
 def test_plan_layout_matches_module_and_oracle_inventory():
@@ -677,7 +659,6 @@ def test_every_plan_option_is_documented_in_the_header_and_readable():
     documented = dict(re.findall(r'^ \*   "([a-z0-9_]+)"\s+\[(-?\d+)\]', hdr, re.M))
     assert listed == documented and set(keys) == set(documented), (set(listed) ^ set(documented), set(keys) ^ set(documented))
     assert f"The {len(documented)} plan options" in integ
-
 
 
 def test_no_kernel_outside_the_fp32_whitelist_uses_scratch(monkeypatch, tmp_path):

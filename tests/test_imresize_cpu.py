@@ -117,34 +117,6 @@ def test_filter_taps_equal_the_reference_table_row_of_an_interior_output(s, up):
         Z.filter_taps(5, up)
 
 
-# ------------------------------------------------------------------------------------------------------------- C ABI
-def _declared(header):
-    return set(re.findall(r"\b(m2t_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "include", header)).read()))
-
-
-def test_resize_header_table_and_library_agree():
-    """include/m2t_resize.h <-> _lib.RESIZE_SIGNATURES <-> the symbols of libm2t.so; the two older headers and tables stay as they
-    were: disjoint from the new one and of unchanged size."""
-    from m2trans_amd import _lib
-    declared = _declared("m2t_resize.h")
-    assert declared == {"m2t_imresize_u8", "m2t_imresize_f32"}
-    assert declared == set(_lib.RESIZE_SIGNATURES), declared ^ set(_lib.RESIZE_SIGNATURES)
-    lib = _lib.load()
-    for name, (res, args) in _lib.RESIZE_SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == args, name
-    vp, i, f = C.c_void_p, C.c_int, C.c_float
-    assert _lib.RESIZE_SIGNATURES["m2t_imresize_u8"] == (i, [vp, i, i, i, vp, i, i, vp])
-    assert _lib.RESIZE_SIGNATURES["m2t_imresize_f32"] == (i, [vp, i, i, i, vp, i, i, f, vp])
-    assert len(_lib.SIGNATURES) == 68 and len(_lib.SPECTRAL_SIGNATURES) == 4
-    assert not (set(_lib.SIGNATURES) & declared) and not (set(_lib.SPECTRAL_SIGNATURES) & declared)
-    assert _declared("m2t.h") == set(_lib.SIGNATURES) and _declared("m2t_spectral.h") == set(_lib.SPECTRAL_SIGNATURES)
-    for older in ("m2t.h", "m2t_spectral.h"):
-        assert "imresize" not in open(os.path.join(ROOT, "include", older)).read().lower()
-    from m2trans_amd import build as B
-    assert "k_resize.hip" in B.SOURCES and any(h.endswith("m2t_resize.h") for h in B.HEADERS)
-
-
 # ------------------------------------------------------------------------------------------------------------- tie margin
 @pytest.mark.parametrize("up", [False, True])
 def test_the_x3_inputs_stay_off_the_rounding_ties(up):

@@ -12,48 +12,9 @@ import torch
 from tests import infer_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OLDER = {"m2t.h": ("SIGNATURES", 68), "m2t_spectral.h": ("SPECTRAL_SIGNATURES", 4), "m2t_resize.h": ("RESIZE_SIGNATURES", 2),
-         "m2t_msssim.h": ("MSSSIM_SIGNATURES", 4), "m2t_vif.h": ("VIF_SIGNATURES", 4), "m2t_groups.h": ("GROUPS_SIGNATURES", 4),
-         "m2t_perceptual.h": ("PERCEPTUAL_SIGNATURES", 13), "m2t_rlutrans.h": ("RLUTRANS_SIGNATURES", 4)}
-
-
-def _declared(header):
-    return set(re.findall(r"\b(m2t_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "include", header)).read()))
 
 
 # ------------------------------------------------------------------------------------------------------------- C ABI
-def test_infer_header_table_and_library_agree():
-    """include/m2t_infer.h <-> _lib.INFER_SIGNATURES <-> the symbols of libm2t.so, with the exact signatures; the eight older headers
-    and tables stay as they were: disjoint from the new one and of unchanged size."""
-    from m2trans_amd import _lib
-    declared = _declared("m2t_infer.h")
-    assert declared == {"m2t_dihedral_pack", "m2t_dihedral_merge", "m2t_tensor_to_image_u8"}
-    assert declared == set(_lib.INFER_SIGNATURES), declared ^ set(_lib.INFER_SIGNATURES)
-    lib = _lib.load()
-    for name, (res, args) in _lib.INFER_SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == args, name
-    vp, i, f = C.c_void_p, C.c_int, C.c_float
-    assert _lib.INFER_SIGNATURES["m2t_dihedral_pack"] == (i, [vp, i, i, i, vp, vp, vp])
-    assert _lib.INFER_SIGNATURES["m2t_dihedral_merge"] == (i, [vp, vp, i, i, i, vp, vp, vp])
-    assert _lib.INFER_SIGNATURES["m2t_tensor_to_image_u8"] == (i, [vp, i, i, i, f, vp, vp])
-    text = open(os.path.join(ROOT, "include", "m2t_infer.h")).read()
-    for proto in ("int m2t_dihedral_pack(const float* src, int planes, int H, int W, float* dst_a, float* dst_b, void* stream);",
-                  "int m2t_dihedral_merge(const float* sr_a, const float* sr_b, int planes, int Hs, int Ws, float* mean, float* spread, "
-                  "void* stream);",
-                  "int m2t_tensor_to_image_u8(const float* src, int channels, int H, int W, float rgb_range, unsigned char* dst, "
-                  "void* stream);"):
-        assert proto in text, proto
-    for header, (table, size) in OLDER.items():
-        older = getattr(_lib, table)
-        assert len(older) == size, (table, len(older))
-        assert not (set(older) & declared), table
-        assert set(older) <= _declared(header), header           # (a header's comments may name entries of other headers)
-        assert "dihedral" not in open(os.path.join(ROOT, "include", header)).read().lower()
-    from m2trans_amd import build as B
-    assert "k_infer.hip" in B.SOURCES and any(h.endswith("m2t_infer.h") for h in B.HEADERS)
-
-
 def test_argument_errors_need_no_device():
     """Every M2T_ERR_ARG of the header is decided on the host before any launch, so it is reported without a device too."""
     from m2trans_amd import _lib

@@ -24,7 +24,7 @@ def _model(scale=4, nb=2):
 def test_backward_ex_is_declared_exported_and_bound():
     from m2trans_amd import _lib
     assert "m2t_backward_ex" in open(os.path.join(ROOT, "include", "m2t.h")).read()
-    assert "m2t_backward_ex" in _lib.SIGNATURES
+    assert "m2t_backward_ex" in _lib.ABI["m2t.h"]
     lib = _lib.load()
     assert hasattr(lib, "m2t_backward_ex")
     assert lib.m2t_backward_ex.restype is C.c_int

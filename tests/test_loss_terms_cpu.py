@@ -143,14 +143,15 @@ def test_a_size_a_term_does_not_take_is_refused_before_any_launch(monkeypatch):
 
 
 def test_class_defaults_are_off_for_every_term_and_scratch_caches_are_per_object():
-    from m2trans_amd.train_step import LOSS_TERMS, TrainStep
-    assert [t.name for t in LOSS_TERMS] == list(TERMS[:4])
+    from m2trans_amd.train_step import _TERM, LOSS_TERMS, TrainStep
+    # the single table, in call order
+    assert [t.name for t in LOSS_TERMS] == ["ssim", "msssim", "fft", "vif", "gmsd", "wavelet", "consistency"]
     a, b = TrainStep.__new__(TrainStep), TrainStep.__new__(TrainStep)
     for t in TERMS[:4]:
         assert getattr(a, f"lambda_{t}") == 0.0 and getattr(a, f"{t}_loss") is None and getattr(a, f"_{t}_scratch") is None
     assert a.lambda_perceptual == 0.0 and a.perceptual_loss is None and a.perceptual_loss_value is None and a.fft_norm == "backward"
     lib = types.SimpleNamespace(m2t_vif_loss_scratch_bytes=lambda *s: 64)
-    a._vif_scratch_for(lib, torch.zeros(1, 3, 48, 48))
+    a._scratch_for(_TERM["vif"], lib, torch.zeros(1, 3, 48, 48))
     assert list(a._vif_scratch) == [(1, 48, 48)] and b._vif_scratch is None and TrainStep._vif_scratch is None
 
 

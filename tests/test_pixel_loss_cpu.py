@@ -69,17 +69,6 @@ def test_fp64_restatement_default_parameters_and_padding():
         assert int(torch.count_nonzero(s1[..., 8:, :])) == 0 and int(torch.count_nonzero(s1[..., :, 12:])) == 0
 
 
-def test_abi_table_lists_the_pixel_loss_entry_points():
-    from m2trans_amd import _lib
-    want = (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_float, C.c_double, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p])
-    for name in ("m2t_pixel_loss", "m2t_pixel_loss_deferred"):
-        assert _lib.SIGNATURES[name] == want, name
-    lib = _lib.load()
-    assert hasattr(lib, "m2t_pixel_loss") and hasattr(lib, "m2t_pixel_loss_deferred")
-    # the two L1 entry points stay
-    assert "m2t_l1_loss" in _lib.SIGNATURES and "m2t_l1_loss_deferred" in _lib.SIGNATURES
-
-
 def test_entry_points_refuse_bad_arguments_without_a_device():
     """Argument checks are decided on the host before anything touches a device."""
     from m2trans_amd import _lib

@@ -50,7 +50,7 @@ def load_library(path):
     from m2trans_amd import _lib
     import torch  # noqa: F401  (its HIP runtime first, as _lib.load does)
     lib = C.CDLL(path)
-    for name, (res, args) in _lib.SIGNATURES.items():
+    for name, (res, args) in _lib.ABI["m2t.h"].items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     return lib

@@ -60,28 +60,6 @@ def test_forcing_the_own_mask_changes_no_bit(shape):
 
 
 # ------------------------------------------------------------------------------------------------------------- C ABI
-def _declared(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return re.findall(r"\b(m2t_[a-z0-9_]+)\s*\(", src)
-
-
-def test_header_table_and_library_agree():
-    from m2trans_amd import _lib
-    vp, i = C.c_void_p, C.c_int
-    assert _declared("m2t_rlutrans.h") == list(_lib.RLUTRANS_SIGNATURES) and len(_lib.RLUTRANS_SIGNATURES) == 4
-    assert _lib.RLUTRANS_SIGNATURES["m2t_transblock_train_workspace_bytes"] == (C.c_size_t, [i, i, i])
-    assert _lib.RLUTRANS_SIGNATURES["m2t_transblock_train_workspace_offset"] == (C.c_size_t, [i, i, i, i])
-    assert _lib.RLUTRANS_SIGNATURES["m2t_transblock_forward_train"] == (i, [vp, vp, vp, i, i, i, vp, vp])
-    assert _lib.RLUTRANS_SIGNATURES["m2t_transblock_backward"] == (i, [vp, vp, vp, vp, i, i, i, vp, vp])
-    assert len(_lib.SIGNATURES) == 68 and sorted(set(_declared("m2t.h"))) == sorted(_lib.SIGNATURES)
-    assert not any(n in _lib.SIGNATURES for n in _lib.RLUTRANS_SIGNATURES)
-    lib = _lib.load()
-    for name in _lib.RLUTRANS_SIGNATURES:
-        assert hasattr(lib, name)
-        assert getattr(lib, name).argtypes == _lib.RLUTRANS_SIGNATURES[name][1]
-
-
 def test_entry_points_refuse_bad_arguments_before_any_launch():
     from m2trans_amd import _lib
     lib = _lib.load()

@@ -106,18 +106,6 @@ def test_kernel_source_holds_exactly_these_taps():
 
 
 # ------------------------------------------------------------------------------------------------------------- C ABI
-def test_abi_table_lists_the_three_ssim_entry_points():
-    from m2trans_amd import _lib
-    vp, i, f, d, ll = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_longlong
-    assert _lib.SIGNATURES["m2t_ssim_loss_scratch_bytes"] == (C.c_size_t, [i, i, i, i])
-    assert _lib.SIGNATURES["m2t_ssim_loss_tensor"] == (i, [vp, vp, i, i, i, i, ll, i, f, i, d, vp, vp, i, vp, vp])
-    assert _lib.SIGNATURES["m2t_ssim_loss"] == (i, [vp, vp, f, d, f, vp, i, vp, vp, vp])
-    assert len(_lib.SIGNATURES) == 68
-    lib = _lib.load()
-    for name in ("m2t_ssim_loss_scratch_bytes", "m2t_ssim_loss_tensor", "m2t_ssim_loss"):
-        assert hasattr(lib, name)
-
-
 def test_entry_points_decide_sizes_and_bad_arguments_on_the_host():
     from m2trans_amd import _lib
     lib = _lib.load()

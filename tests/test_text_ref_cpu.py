@@ -119,23 +119,12 @@ def test_bf16_emulation_rounds_at_the_stores(params, clean):
     assert R.row_err(R.attn(q, mask, bugs=("last_key",)), ref) > 5 * R.MARGIN * R.row_err(R.attn(q, mask, emu=True), ref)
 
 
-def test_text_header_table_and_library_agree():
-    """include/m2t_text.h <-> _lib.TEXT_SIGNATURES <-> the symbols of libm2t.so; include/m2t.h keeps its entries; the text handle
-    answers ws: / wsn: for every region the gate reads, and the null-argument error of the new entry needs no device."""
+def test_text_handle_answers_the_region_queries_and_the_null_argument_error_needs_no_device():
+    """the text handle answers ws: / wsn: for every region the gate reads, and the null-argument error of m2t_text_encode_ex needs no
+    device."""
     import ctypes as C
-    import os
-    import re
     from m2trans_amd import _lib
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    declared = lambda h: set(re.findall(r"\b(m2t_[a-z0-9_]+)\s*\(", open(os.path.join(root, "include", h)).read()))
-    assert declared("m2t_text.h") == {"m2t_text_encode_ex"} == set(_lib.TEXT_SIGNATURES)
-    assert not set(_lib.TEXT_SIGNATURES) & set(_lib.SIGNATURES) and set(_lib.SIGNATURES) <= declared("m2t.h")
     lib = _lib.load()
-    fn = lib.m2t_text_encode_ex
-    assert fn.restype is C.c_int and list(fn.argtypes) == _lib.TEXT_SIGNATURES["m2t_text_encode_ex"][1]
-    assert list(fn.argtypes) == list(lib.m2t_text_encode.argtypes) + [C.c_void_p]
-    from m2trans_amd import build as B
-    assert any(h.endswith("m2t_text.h") for h in B.HEADERS)
     h = C.c_void_p()
     assert lib.m2t_text_create(C.byref(h), 4, 128, 0) == 0
     q = lambda k: lib.m2t_text_query(h, k.encode())

@@ -12,56 +12,12 @@ import torch
 from tests import tiles_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OLDER = {"m2t.h": ("SIGNATURES", 68), "m2t_spectral.h": ("SPECTRAL_SIGNATURES", 4), "m2t_resize.h": ("RESIZE_SIGNATURES", 2),
-         "m2t_msssim.h": ("MSSSIM_SIGNATURES", 4), "m2t_vif.h": ("VIF_SIGNATURES", 4), "m2t_groups.h": ("GROUPS_SIGNATURES", 4),
-         "m2t_perceptual.h": ("PERCEPTUAL_SIGNATURES", 13), "m2t_rlutrans.h": ("RLUTRANS_SIGNATURES", 4),
-         "m2t_infer.h": ("INFER_SIGNATURES", 3), "m2t_train.h": ("TRAIN_SIGNATURES", 3)}
 ARG = -2
 BRUTE_T = (1, 2, 8, 32, 33)                                  # every legal overlap, every L up to 4 T + 6
 GPU_SHAPES = [(20, 70, 32, 8, 4), (56, 56, 32, 8, 2), (33, 75, 32, 8, 3), (50, 50, 32, 16, 4), (64, 70, 32, 0, 2), (40, 56, 32, 16, 1)]
 
 
-def _declared(header):
-    return set(re.findall(r"\b(m2t_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "include", header)).read()))
-
-
 # ------------------------------------------------------------------------------------------------------------- C ABI
-def test_tiles_header_table_and_library_agree():
-    """include/m2t_tiles.h <-> _lib.TILES_SIGNATURES <-> the symbols of libm2t.so, with the exact prototypes; the ten older headers
-    and tables stay as they were: disjoint from the new one and of unchanged size."""
-    from m2trans_amd import _lib
-    declared = _declared("m2t_tiles.h")
-    assert declared == {"m2t_tile_grid", "m2t_tile_gather", "m2t_tile_blend"}
-    assert declared == set(_lib.TILES_SIGNATURES), declared ^ set(_lib.TILES_SIGNATURES)
-    lib = _lib.load()
-    for name, (res, args) in _lib.TILES_SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == args, name
-    vp, i, ip = C.c_void_p, C.c_int, C.POINTER(C.c_int)
-    assert _lib.TILES_SIGNATURES["m2t_tile_grid"] == (i, [i, i, i, ip, ip, ip])
-    assert _lib.TILES_SIGNATURES["m2t_tile_gather"] == (i, [vp, i, i, i, i, i, i, i, i, vp, vp])
-    assert _lib.TILES_SIGNATURES["m2t_tile_blend"] == (i, [vp, i, i, i, i, i, i, i, vp, vp, vp])
-    text = open(os.path.join(ROOT, "include", "m2t_tiles.h")).read()
-    for proto in ("int m2t_tile_grid(int L, int T, int overlap, int* n_out, int* tile_len_out, int* origins_out /* n ints, may be NULL */);",
-                  "int m2t_tile_gather(const float* src, int B, int C, int H, int W, int T, int overlap, int first, int count, float* dst, "
-                  "void* stream);",
-                  "int m2t_tile_blend(const float* tiles, int B, int C, int H, int W, int T, int overlap, int scale, float* dst, "
-                  "float* seam /* may be NULL */, void* stream);"):
-        assert proto in text, proto
-    for word in ("dihedral", "m2t_meter", "preview"):
-        assert word not in text.lower(), word
-    assert len(OLDER) == 10
-    for header, (table, size) in OLDER.items():
-        older = getattr(_lib, table)
-        assert len(older) == size, (table, len(older))
-        assert not (set(older) & declared), table
-        assert set(older) <= _declared(header), header
-        assert "m2t_tile" not in open(os.path.join(ROOT, "include", header)).read().lower(), header
-    from m2trans_amd import build as B
-    assert "k_tiles.hip" in B.SOURCES and any(h.endswith("m2t_tiles.h") for h in B.HEADERS)
-    assert os.path.exists(os.path.join(ROOT, "m2trans_amd", "csrc", "k_tiles.hip"))
-
-
 def test_every_argument_error_needs_no_device():
     """Every M2T_ERR_ARG of the three entries is decided on the host before any launch, so it is reported without a device too."""
     from m2trans_amd import _lib

@@ -87,35 +87,6 @@ def test_special_values():
 
 
 # ------------------------------------------------------------------------------------------------------------- C ABI
-def _declared(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return re.findall(r"\b(m2t_[a-z0-9_]+)\s*\(", src)
-
-
-def test_header_table_and_library_agree_and_the_older_tables_are_unchanged():
-    from m2trans_amd import _lib
-    vp, i, f, d, ll = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_longlong
-    assert sorted(_declared("m2t_vif.h")) == sorted(_lib.VIF_SIGNATURES) and len(_lib.VIF_SIGNATURES) == 4
-    assert _lib.VIF_SIGNATURES["m2t_vif_loss_scratch_bytes"] == (C.c_size_t, [i, i, i, i])
-    assert _lib.VIF_SIGNATURES["m2t_vif_loss_scratch_offset"] == (C.c_size_t, [i, i, i, i, i, i])
-    assert _lib.VIF_SIGNATURES["m2t_vif_loss_tensor"] == (i, [vp, vp, i, i, i, i, ll, i, f, d, i, d, vp, vp, vp, i, vp, vp])
-    assert _lib.VIF_SIGNATURES["m2t_vif_loss"] == (i, [vp, vp, f, d, f, d, vp, i, vp, vp, vp])
-    assert (len(_lib.SIGNATURES), len(_lib.SPECTRAL_SIGNATURES), len(_lib.RESIZE_SIGNATURES)) == (68, 4, 2)
-    assert list(_lib.MSSSIM_SIGNATURES) == ["m2t_msssim_loss_scratch_bytes", "m2t_msssim_loss_scratch_offset", "m2t_msssim_loss_tensor",
-                                            "m2t_msssim_loss"]
-    tables = [_lib.SIGNATURES, _lib.SPECTRAL_SIGNATURES, _lib.RESIZE_SIGNATURES, _lib.MSSSIM_SIGNATURES, _lib.VIF_SIGNATURES]
-    names = [n for t in tables for n in t]
-    assert len(names) == len(set(names))
-    assert not any("vif" in n for t in tables[:4] for n in t)
-    for header, table in (("m2t.h", _lib.SIGNATURES), ("m2t_spectral.h", _lib.SPECTRAL_SIGNATURES), ("m2t_resize.h", _lib.RESIZE_SIGNATURES),
-                          ("m2t_msssim.h", _lib.MSSSIM_SIGNATURES)):
-        assert sorted(set(_declared(header))) == sorted(table), header
-    lib = _lib.load()
-    for name in _lib.VIF_SIGNATURES:
-        assert hasattr(lib, name)
-
-
 def test_entry_points_decide_sizes_and_bad_arguments_on_the_host():
     from m2trans_amd import _lib
     lib = _lib.load()
@@ -199,13 +170,13 @@ def test_set_lambda_vif_refuses_a_change_inside_an_accumulation_cycle():
 
 
 def test_size_is_refused_before_any_launch():
-    """_vif_scratch_for refuses a small SR image on the host: no library call is made (lib = None would raise otherwise)."""
+    """_scratch_for refuses a small SR image on the host: no library call is made (lib = None would raise otherwise)."""
     from m2trans_amd._lib import M2TError
-    from m2trans_amd.train_step import TrainStep
+    from m2trans_amd.train_step import _TERM, TrainStep
     ts = TrainStep.__new__(TrainStep)
     ts._vif_scratch = {}
     with pytest.raises(M2TError, match="at least 41"):
-        ts._vif_scratch_for(None, torch.zeros(2, 3, 40, 64))
+        ts._scratch_for(_TERM["vif"], None, torch.zeros(2, 3, 40, 64))
 
 
 class _Calls:

@@ -133,53 +133,6 @@ def test_the_sector_has_exactly_zero_coefficients_and_gradient_and_a_zero_weight
 
 
 # ------------------------------------------------------------------------------------------------------------- C ABI
-def _declared(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return re.findall(r"\b(m2t_[a-z0-9_]+)\s*\(", src)
-
-
-def _prototype(header, name):
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    m = re.search(r"([a-z_0-9]+)\s+" + name + r"\s*\(([^)]*)\)\s*;", src)
-    return m.group(1), [" ".join(a.split()[:-1]) for a in m.group(2).split(",")]
-
-
-def test_header_table_and_library_agree_and_the_older_tables_keep_their_sizes():
-    from m2trans_amd import _lib, build as B
-    vp, i, f, d, ll, dp = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_longlong, C.POINTER(C.c_double)
-    names = ["m2t_wavelet_loss_scratch_bytes", "m2t_swt2", "m2t_wavelet_loss_tensor", "m2t_wavelet_loss"]
-    assert _declared("m2t_wavelet.h") == list(_lib.WAVELET_SIGNATURES) == names
-    assert _lib.WAVELET_SIGNATURES["m2t_wavelet_loss_scratch_bytes"] == (C.c_size_t, [i, i, i, i, i, i])
-    assert _lib.WAVELET_SIGNATURES["m2t_swt2"] == (i, [vp, i, i, i, i, ll, i, dp, dp, i, i, vp, vp, vp])
-    assert _lib.WAVELET_SIGNATURES["m2t_wavelet_loss_tensor"] == (i, [vp, vp, i, i, i, i, ll, i, f, i, d, dp, dp, i, i, dp, d, vp, vp, vp, i,
-                                                                     vp, vp])
-    assert _lib.WAVELET_SIGNATURES["m2t_wavelet_loss"] == (i, [vp, vp, f, d, f, dp, dp, i, i, dp, d, vp, i, vp, vp, vp])
-    # the exact prototypes of the header, type by type: the host arrays are const double*, every other pointer a device pointer
-    ctype = {"int": i, "float": f, "double": d, "long long": ll, "size_t": C.c_size_t}
-    for name, (res, args) in _lib.WAVELET_SIGNATURES.items():
-        ret, types_ = _prototype("m2t_wavelet.h", name)
-        assert ctype[ret] == res, name
-        assert [dp if t == "const double*" else vp if t.endswith("*") else ctype[t] for t in types_] == args, (name, types_)
-    assert _prototype("m2t_wavelet.h", "m2t_wavelet_loss_tensor")[1] == [
-        "const float*", "const float*", "int", "int", "int", "int", "long long", "int", "float", "int", "double", "const double*",
-        "const double*", "int", "int", "const double*", "double", "float*", "float*", "double*", "int", "void*", "void*"]
-    assert _prototype("m2t_wavelet.h", "m2t_wavelet_loss")[1] == [
-        "m2t_plan*", "const float*", "float", "double", "float", "const double*", "const double*", "int", "int", "const double*", "double",
-        "float*", "int", "void*", "void*", "void*"]
-    older = [_lib.SIGNATURES, _lib.SPECTRAL_SIGNATURES, _lib.RESIZE_SIGNATURES, _lib.MSSSIM_SIGNATURES, _lib.VIF_SIGNATURES,
-             _lib.GROUPS_SIGNATURES, _lib.PERCEPTUAL_SIGNATURES, _lib.RLUTRANS_SIGNATURES, _lib.INFER_SIGNATURES, _lib.TRAIN_SIGNATURES,
-             _lib.TILES_SIGNATURES, _lib.GMSD_SIGNATURES, _lib.DEGRADE_SIGNATURES, _lib.JPEG_SIGNATURES]
-    assert [len(t) for t in older] == [68, 4, 2, 4, 4, 4, 13, 4, 3, 3, 3, 3, 2, 4]
-    every = [n for t in older + [_lib.WAVELET_SIGNATURES] for n in t]
-    assert len(every) == len(set(every)) and not any("wavelet" in n or "swt" in n for t in older for n in t)
-    assert "k_wavelet_loss.hip" in B.SOURCES and "m2t_wavelet_tile.h" in B.HEADERS and any(h.endswith("m2t_wavelet.h") for h in B.HEADERS)
-    lib = _lib.load()
-    for name in names:
-        assert hasattr(lib, name)
-    assert lib.m2t_wavelet_loss_tensor.argtypes == _lib.WAVELET_SIGNATURES["m2t_wavelet_loss_tensor"][1]
-
-
 def _arr(v):
     return (C.c_double * len(v))(*v)
 
@@ -308,14 +261,12 @@ def test_lambda_wavelet_defaults_setter_and_table():
             T.resolve_lambda_wavelet(bad)
     with pytest.raises(M2TError, match="lambda_wavelet"):
         T.TrainStep(None, lambda_wavelet=-1.0)
-    # the row: a third tuple of the same type, behind the pinned ones
-    assert [t.name for t in T.LOSS_TERMS] == ["ssim", "msssim", "fft", "vif"] and [t.name for t in T.MORE_LOSS_TERMS] == ["gmsd"]
-    assert [t.name for t in T.LATER_LOSS_TERMS] == ["wavelet"] and T.ALL_LOSS_TERMS == T.LOSS_TERMS + T.MORE_LOSS_TERMS + T.LATER_LOSS_TERMS
-    row = T.LATER_LOSS_TERMS[0]
-    assert isinstance(row, T.LossTerm) and T._TERM["wavelet"] is row
+    # the row of the one table (its order: tests/test_loss_terms_cpu.py)
+    row = T._TERM["wavelet"]
+    assert isinstance(row, T.LossTerm) and row in T.LOSS_TERMS
     assert row.size_ok(13, 500, 3, 4) and not row.size_ok(12, 500, 3, 4) and not row.size_ok(500, 12, 3, 4) and row.size_ok(2, 2, 1, 2)
     assert row.count(7, 100, 200) == 7 * 3 * 100 * 200
-    assert all(t.shape_args(None) == () for t in T.LOSS_TERMS + T.MORE_LOSS_TERMS)
+    assert all(t.shape_args(None) == () for t in T.LOSS_TERMS if t is not row)
     ts = T.TrainStep.__new__(T.TrainStep)
     ts.accum_steps, ts.micro_count = 2, 1
     with pytest.raises(M2TError, match="accumulation cycle"):
