@@ -123,7 +123,17 @@ long long m2t_plan_query(const m2t_plan* p, const char* key);
  *                           window; 2 = the same and q | k | v of that branch are NOT stored: the backward kernel recomputes them from
  *                           the branch input (identical bits; needs "attn_bwd" >= 1; m2t_plan_query("stores_qkv1") tells whether
  *                           ws:b*.qkv1 is written); 0 = three kernels
- *   "debug_skip_side"   [0] timing experiments only: skips every parameter-gradient kernel (results are WRONG) */
+ *   "debug_skip_side"   [0] timing experiments only: skips every parameter-gradient kernel (results are WRONG)
+ *   "inference"         [0] 1 = an INFERENCE PLAN: m2t_forward alone, on a forward-only workspace.  "workspace_bytes", "ws:<name>" and
+ *                           "wsn:<name>" then describe a layout resolved from the options in force when they are asked: the persistent regions
+ *                           and X0 as before, X1 .. X<n_blocks> alternating between two buffers, ONE set of per-block regions that every
+ *                           "b<k>." name resolves to, and no region the forward never reads -- q | k | v on the fused attention paths, the tail's
+ *                           gelu' tensors, every backward region and the reduction arena answer -1 and the kernels get a null pointer for
+ *                           them.  The same kernels in the same order as a training plan's forward: sr is BIT-IDENTICAL.  May be set or
+ *                           cleared only before the first m2t_plan_init_workspace; on an initialised inference plan every other
+ *                           m2t_set_option is M2T_ERR_STATE (the layout is frozen), as are m2t_forward with keep_activations != 0, every
+ *                           plan-taking loss entry, m2t_set_output_grad / m2t_add_output_grad, m2t_backward / m2t_backward_ex and
+ *                           m2t_stream_wait_bucket: an inference forward leaves neither activations nor a seed */
 int m2t_set_option(m2t_plan* p, const char* key, long long value);
 /* Gradient buckets for communication overlap (replaces the reduce-to-GPU-0 of nn.DataParallel, train.py:73):
  * m2t_backward completes the flat gradient buffer in "grad_buckets" contiguous ranges, in this order: tail, block
@@ -137,14 +147,16 @@ int m2t_stream_wait_bucket(m2t_plan* p, int bucket, void* stream);
  * "pack_blocks" (the weight-packing tables), all three written here, and "red_descs" (the table of the deferred gradient
  * reductions), written by the first all-stages m2t_backward after this call.  Every other region is scratch WITHIN one step: each
  * m2t_forward / m2t_backward writes whatever it reads before it reads it, so the contents left by an earlier step (or by the
- * allocator) never reach a result -- tests/test_gpu_schedule.py fills them with NaN between steps.
+ * allocator) never reach a result -- tests/test_gpu_schedule.py fills them with NaN between steps.  (An inference plan has the first
+ * three persistent regions and no "red_descs"; the same contract holds for its aliased layout: tests/test_gpu_lean_inference.py.)
  * Calling this again on a live plan is legal (with the same or another buffer, once the plan's earlier work on `stream` is
  * enqueued): it returns the plan to "no activations, no seed", and the next all-stages backward publishes "red_descs" again. */
 int m2t_plan_init_workspace(m2t_plan* p, void* workspace, void* stream);
 
 /* ---- model ----------------------------------------------------------------------------- */
 /* M2Trans.forward (models/M2Trans_network.py:58-76): x [B,3,H0,W0] -> sr [B,3,H0*s,W0*s].
- * keep_activations != 0 saves what m2t_backward needs. */
+ * keep_activations: a training plan keeps everything m2t_backward needs whatever the argument says; an inference plan (option
+ * "inference") keeps nothing, and a non-zero argument is M2T_ERR_STATE there. */
 int m2t_forward(m2t_plan* p, const float* params, const float* x, float* sr, float rgb_range,
                 int keep_activations, void* workspace, void* stream);
 /* L1Loss()(sr, hr) * lambda_l1 (train.py:76,199) on the forward's output + the backward seed.

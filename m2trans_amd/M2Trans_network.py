@@ -49,9 +49,13 @@ class _Holder(nn.Module):
 
 
 class Plan:
-    """m2t_plan + its workspace (one per (B, H0, W0, dtype))."""
+    """m2t_plan + its workspace (one per (B, H0, W0, dtype)).  ``inference=True``: an inference plan (option "inference" of
+    include/m2t.h) -- m2t_forward alone, on a forward-only workspace; every entry that needs activations or a seed refuses it.
+    ``options``: {key: value} for m2t_set_option, set before the workspace is sized and initialised (an initialised inference plan
+    takes no option any more)."""
 
-    def __init__(self, B: int, H0: int, W0: int, scale: int, n_blocks: int, dtype: int, device):
+    def __init__(self, B: int, H0: int, W0: int, scale: int, n_blocks: int, dtype: int, device, inference: bool = False,
+                 options=None):
         lib = _lib.load()
         h = C.c_void_p()
         self.handle = None
@@ -59,6 +63,11 @@ class Plan:
         with torch.cuda.device(device):
             _lib.check(lib.m2t_plan_create(C.byref(h), B, H0, W0, scale, n_blocks, dtype), "m2t_plan_create")
             self.handle = h
+            self.inference = bool(inference)
+            if self.inference:           # before the size query: the option decides the layout
+                _lib.check(lib.m2t_set_option(h, b"inference", 1), "m2t_set_option(inference)")
+            for k, v in (options or {}).items():
+                _lib.check(lib.m2t_set_option(h, str(k).encode(), int(v)), f"m2t_set_option({k})")
             self.B, self.H0, self.W0, self.scale, self.n_blocks, self.dtype = B, H0, W0, scale, n_blocks, dtype
             self.device = device
             self.gen = 0
@@ -175,6 +184,10 @@ _DP_WARNED = False
 
 
 class M2Trans(nn.Module):
+    # lean_inference(): forwards that take no autograd edge run on inference plans.  A plain attribute (class default: off), so
+    # copy.deepcopy, pickle and the replicas of nn.DataParallel carry it
+    lean_inference_enabled = False
+
     def __init__(self, args):
         super().__init__()
         n_feats = int(args.n_feats)
@@ -188,6 +201,8 @@ class M2Trans(nn.Module):
         self.n_blocks = int(args.n_blocks)
         cd = getattr(args, "compute_dtype", None) or os.environ.get("M2T_COMPUTE_DTYPE", "fp32")
         self.compute_dtype = str(cd)
+        if getattr(args, "lean_inference", False):           # optional yaml key (train.py: validation on inference plans)
+            self.lean_inference_enabled = True
         self._plans: "OrderedDict[Tuple, Plan]" = OrderedDict()
         self._dp_master = None                       # set on the replicas nn.DataParallel makes of this module
         self._dp_params = None
@@ -459,15 +474,26 @@ class M2Trans(nn.Module):
             if plan.query("param:" + n) != o or plan.query("numel:" + n) != k:
                 raise M2TError(f"parameter layout mismatch for {n}")
 
-    def _plan_for(self, x: torch.Tensor) -> Plan:
+    def lean_inference(self, enabled: bool = True) -> "M2Trans":
+        """Forwards without an autograd edge (``torch.no_grad()``, or nothing that requires grad) use INFERENCE plans from now
+        on: the same kernels and the same bits on a forward-only workspace (a fraction of the training workspace, independent of
+        ``n_blocks`` but for the packed weights).  Forwards with an edge and ``TrainStep`` keep their training plans; both kinds
+        live in the same LRU under different keys.  Returns self."""
+        self.lean_inference_enabled = bool(enabled)
+        return self
+
+    def _plan_for(self, x: torch.Tensor, inference: bool = False) -> Plan:
         if x.dim() != 4 or x.shape[1] != 3:
             raise M2TError("expected input of shape [B,3,H,W]")
         self._device_ok(x)
         B, _, H0, W0 = x.shape
         key = (B, H0, W0, self._dtype_code(), x.device.index)
+        if inference:
+            key = key + ("inference",)
         plan = self._plans.get(key)
         if plan is None:
-            plan = Plan(B, H0, W0, self.scale, self.n_blocks, key[3], x.device)
+            kind = {"inference": True} if inference else {}
+            plan = Plan(B, H0, W0, self.scale, self.n_blocks, key[3], x.device, **kind)
             self._check_plan(plan)
             self._plans[key] = plan
             # least-recently-used plans go first; a plan whose backward is still pending is kept alive by its autograd node
@@ -486,6 +512,9 @@ class M2Trans(nn.Module):
 
     def _run_forward(self, plan: Plan, x: torch.Tensor, keep: bool, want_sr: bool = True):
         lib = _lib.load()
+        if keep and getattr(plan, "inference", False):
+            raise M2TError("M2Trans._run_forward: keep=True on an inference plan (it keeps no activations); "
+                           "use a training plan for a forward that a backward pass follows")
         x = x.contiguous().float()
         B, _, H0, W0 = x.shape
         sr = torch.empty(B, 3, H0 * self.scale, W0 * self.scale, dtype=torch.float32, device=x.device) if want_sr else None
@@ -503,7 +532,7 @@ class M2Trans(nn.Module):
             params = self._dp_params if self._dp_master is not None else [p for _, p in self._trainable()]
             if x.requires_grad or any(p.requires_grad for p in params):
                 return _M2TransFunction.apply(x, self, *params)
-        sr = self._run_forward(self._plan_for(x), x, keep=False)
+        sr = self._run_forward(self._plan_for(x, inference=self.lean_inference_enabled), x, keep=False)
         if self._dp_master is not None:
             self._dp_release()
         return sr

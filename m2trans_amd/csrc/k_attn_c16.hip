@@ -406,7 +406,10 @@ __global__ void __launch_bounds__(256, 4) window_attn_fwd_c16_kernel(const bf16_
 // IS the operand layout the attention part reads from HBM in the unfused kernel.  d1 (= the residual) and qkv of the
 // window's own pixels are still written: the backward pass reads them.  Out-of-image halo keys are the zero padding of
 // the normalised map (x^ = 0 -> k = v = 0, key = rel-pos alone).
+// KEEP_D = false (d == nullptr at the launcher: an inference plan, nothing reads d1): d is not written.  An instantiation of its
+// own, so that the code of the training step's kernel (KEEP_D = true) is what it was before the switch existed.
 // ---------------------------------------------------------------------------------------
+template <bool KEEP_D>
 __global__ void __launch_bounds__(256, 4) window_attn_fused_c16_fwd_kernel(const bf16_t* __restrict__ x, const float* __restrict__ mean,
                                                                            const float* __restrict__ rstd, const bf16_t* __restrict__ wqkv,
                                                                            const float* __restrict__ rel_h, const float* __restrict__ rel_w,
@@ -467,7 +470,7 @@ __global__ void __launch_bounds__(256, 4) window_attn_fused_c16_fwd_kernel(const
     const int q = 16 * qt + lr;
     const long long qpix = img + (long long)(8 * wy + (q >> 3)) * w + 8 * wx + (q & 7);
     const bf16x4 xn = normalise(xq[qt]);
-    st4(d + qpix * C16 + 4 * g, xn);
+    if constexpr (KEEP_D) st4(d + qpix * C16 + 4 * g, xn);
     st4(&Xr[q][4 * g], xn);
     f32x4 a = (f32x4){0.f, 0.f, 0.f, 0.f};
     mma4(a, wA[0], xn);
@@ -735,15 +738,20 @@ int launch_window_attn_fwd_c16(const void* qkv, const float* rel_h, const float*
 }
 
 // x: the P64 plane of chunk 0 of the block input [B*h*w][16]; mean / rstd [B][64]; wqkv [48][16] bf16 (M2T_PACK_COPY);
-// d [B*h*w][16] and qkv [B*h*w][48] are written for the backward pass; out: chunk plane of the concat buffer.
+// d [B*h*w][16] and qkv [B*h*w][48] are written for the backward pass (either may be null: not written); out: chunk plane of the concat buffer.
 int launch_window_attn_fused_c16_fwd(const void* x, const float* mean, const float* rstd, const void* wqkv, const float* rel_h,
                                      const float* rel_w, void* d, void* qkv, void* out, int ldo, int oc0, int B, int h, int w,
                                      hipStream_t st) {
   if (h % 8 || w % 8) return m2t_set_error(-2, "window_attn_fused_c16_fwd: h, w must be multiples of 8");
   const int nwin = B * (h / 8) * (w / 8);
   M2TProfScope ps(M2T_PROF_ATTN_FUSED_16, st);
-  M2T_LAUNCH_TIMED(window_attn_fused_c16_fwd_kernel, dim3((nwin + 3) / 4), dim3(256), 0, st, (const bf16_t*)x, mean, rstd,
-                   (const bf16_t*)wqkv, rel_h, rel_w, (bf16_t*)d, (bf16_t*)qkv, (bf16_t*)out, ldo, oc0, h, w, nwin);
+  if (d) {
+    M2T_LAUNCH_TIMED(window_attn_fused_c16_fwd_kernel<true>, dim3((nwin + 3) / 4), dim3(256), 0, st, (const bf16_t*)x, mean, rstd,
+                     (const bf16_t*)wqkv, rel_h, rel_w, (bf16_t*)d, (bf16_t*)qkv, (bf16_t*)out, ldo, oc0, h, w, nwin);
+  } else {
+    M2T_LAUNCH_TIMED(window_attn_fused_c16_fwd_kernel<false>, dim3((nwin + 3) / 4), dim3(256), 0, st, (const bf16_t*)x, mean, rstd,
+                     (const bf16_t*)wqkv, rel_h, rel_w, (bf16_t*)d, (bf16_t*)qkv, (bf16_t*)out, ldo, oc0, h, w, nwin);
+  }
   M2T_LAUNCH_CHECK();
   return 0;
 }

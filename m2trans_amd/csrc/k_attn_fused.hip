@@ -118,10 +118,12 @@ struct FusedPrepArgs {
   const float* mean;       // [B][64] / [B][64] statistics of X
   const float* rstd;
   bf16_t* xin;             // [B][H][W][16] (written: own pixels)
-  bf16_t* d;               // [B][h][w][C]  (written: own pixels)
+  bf16_t* d;               // [B][h][w][C]  (written: own pixels; null with KEEP_D = false)
   int k;
 };
-template <int C, int L, int NW, bool PREP = false>
+// KEEP_D = false (PREP, C = 64 only; an inference plan): the d rows are not written.  An instantiation of its own, so that the code of the
+// training step's kernels (KEEP_D = true) is what it was before the switch existed.
+template <int C, int L, int NW, bool PREP = false, bool KEEP_D = true>
 __global__ void __launch_bounds__(NW * 64, (C == 64) ? 4 : 1) window_attn_fused_fwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wfrag,
                                                                         const float* __restrict__ rel_h, const float* __restrict__ rel_w,
                                                                         bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, int ldo, int oc0,
@@ -382,7 +384,7 @@ __global__ void __launch_bounds__(NW * 64, (C == 64) ? 4 : 1) window_attn_fused_
   };
   if constexpr (!PREP) load_residual();
   else __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  if constexpr (PREP) {
+  if constexpr (PREP && KEEP_D) {      // (KEEP_D = false: pa.d == nullptr, an inference plan -- d is read by the backward pass alone)
     // the d rows of the window's own pixels (LDS rows 0..63, intact until v overwrites them behind the next barrier) leave as whole rows
     constexpr int DIT = (64 * VEC + NTHR - 1) / NTHR;
 #pragma unroll
@@ -607,12 +609,12 @@ __global__ void __launch_bounds__(NW * 64, (C == 64) ? 4 : 1) window_attn_fused_
   M2T_FUSED_STAMP(7);
 }
 
-template <int C, int L, int NW, bool PREP = false>
+template <int C, int L, int NW, bool PREP = false, bool KEEP_D = true>
 int go_fused(const bf16_t* x, const bf16_t* wfrag, const float* rel_h, const float* rel_w, bf16_t* qkv, bf16_t* out, int ldo, int oc0,
              const bf16_t* res, int ldr, int nwin, int h, int w, hipStream_t st, FusedPrepArgs pa = FusedPrepArgs{}) {
   const size_t sh = FusedCfg<C>::total;
-  if (int rc__ = m2t_ensure_dynamic_lds((const void*)window_attn_fused_fwd_kernel<C, L, NW, PREP>, (int)sh)) return rc__;
-  M2T_LAUNCH_TIMED((window_attn_fused_fwd_kernel<C, L, NW, PREP>), dim3(nwin), dim3(NW * 64), sh, st, x, wfrag, rel_h, rel_w, qkv, out, ldo,
+  if (int rc__ = m2t_ensure_dynamic_lds((const void*)window_attn_fused_fwd_kernel<C, L, NW, PREP, KEEP_D>, (int)sh)) return rc__;
+  M2T_LAUNCH_TIMED((window_attn_fused_fwd_kernel<C, L, NW, PREP, KEEP_D>), dim3(nwin), dim3(NW * 64), sh, st, x, wfrag, rel_h, rel_w, qkv, out, ldo,
                    oc0, res, ldr, h, w, pa);
   return 0;
 }
@@ -645,12 +647,13 @@ int launch_window_attn_fused_fwd(const void* x_, const void* wfrag_, const float
 }
 
 // The same with branch_prep inside (bf16, k >= 1): xn = plane k of the block input, xprev = plane k - 1 of xc (both [B][H][W][16], H = h 2^L),
-// mean / rstd [B][64]; xin [B][H][W][16] and d [B][h][w][C] are WRITTEN (own pixels of every window = every pixel once); out = plane k of xc.
+// mean / rstd [B][64]; xin [B][H][W][16] and d [B][h][w][C] are WRITTEN (own pixels of every window = every pixel once; d may be null at C = 64: not written); out = plane k of xc.
 int launch_window_attn_fused_prep_fwd(const void* xn, const void* xprev, const float* mean, const float* rstd, int k, void* xin, void* d,
                                       const void* wfrag_, const float* rel_h, const float* rel_w, void* qkv_, void* out_, int B, int h, int w,
                                       int C, int post_levels, hipStream_t st) {
   if (h % 8 || w % 8) return m2t_set_error(-2, "window_attn_fused_prep: h,w must be multiples of 8");
-  if (!xn || !xprev || !mean || !rstd || !xin || !d || k < 1 || k > 3) return m2t_set_error(-2, "window_attn_fused_prep: null argument or k outside 1..3");
+  // (d may be null at C = 64 only: without the d stores the C = 256 kernel, at 256 VGPRs, spills 28 bytes per lane)
+  if (!xn || !xprev || !mean || !rstd || !xin || (!d && C != 64) || k < 1 || k > 3) return m2t_set_error(-2, "window_attn_fused_prep: null argument or k outside 1..3");
   if (!((C == 256 && post_levels == 2) || (C == 64 && post_levels == 1)))
     return m2t_set_error(M2T_UNSUPPORTED, "window_attn_fused_prep: unsupported (C, post_levels); built for (64, 1) and (256, 2)");
   FusedPrepArgs pa;
@@ -659,7 +662,8 @@ int launch_window_attn_fused_prep_fwd(const void* xn, const void* xprev, const f
   int rc;
   M2TProfScope ps(C == 64 ? M2T_PROF_ATTN_FUSED_64 : M2T_PROF_ATTN_FUSED_256, st);
   if (C == 256) rc = go_fused<256, 2, 8, true>(nullptr, (const bf16_t*)wfrag_, rel_h, rel_w, (bf16_t*)qkv_, (bf16_t*)out_, 16, 0, (const bf16_t*)xin, 16, nwin, h, w, st, pa);
-  else rc = go_fused<64, 1, 4, true>(nullptr, (const bf16_t*)wfrag_, rel_h, rel_w, (bf16_t*)qkv_, (bf16_t*)out_, 16, 0, (const bf16_t*)xin, 16, nwin, h, w, st, pa);
+  else if (d) rc = go_fused<64, 1, 4, true>(nullptr, (const bf16_t*)wfrag_, rel_h, rel_w, (bf16_t*)qkv_, (bf16_t*)out_, 16, 0, (const bf16_t*)xin, 16, nwin, h, w, st, pa);
+  else rc = go_fused<64, 1, 4, true, false>(nullptr, (const bf16_t*)wfrag_, rel_h, rel_w, (bf16_t*)qkv_, (bf16_t*)out_, 16, 0, (const bf16_t*)xin, 16, nwin, h, w, st, pa);
   if (rc != 0) return rc;
   M2T_LAUNCH_CHECK();
   return 0;

@@ -409,8 +409,10 @@ int launch_gemm_nt(int dt, int amode, int emode, const m2t_gemm_args& a, hipStre
 // bounds the high-resolution kernels (VALU, not HBM): so the epilogue evaluates it ONCE per element and stores
 // both the activation Y = gelu(t) and the derivative Yd = gelu'(t); the consumers (next expansion, tail conv,
 // their weight / data gradients) read those instead of re-evaluating erf on every (halo-inflated) pass.
+// DER = false (Yd == nullptr at the launcher: an inference plan): the derivative is not stored.  An instantiation of its own, so
+// that the code of the training step's kernels (DER = true) is what it was before the switch existed.
 // =======================================================================================
-template <typename T, int NSUB>
+template <typename T, int NSUB, bool DER = true>
 __global__ void __launch_bounds__(256)
 tail_expand_kernel(const T* __restrict__ X, const T* __restrict__ Wp, const float* __restrict__ bias, T* __restrict__ Y,
                    T* __restrict__ Yd, long long M, int H, int Wd, int r, int tiles_per_block, int x_p64) {
@@ -496,7 +498,7 @@ tail_expand_kernel(const T* __restrict__ X, const T* __restrict__ Wp, const floa
         }
         const long long pix = pixbase[mt] + (long long)i * Wd * r + j;
         store16f(Y + pix * 64 + 16 * g, v);
-        store16f(Yd + pix * 64 + 16 * g, dv);
+        if constexpr (DER) store16f(Yd + pix * 64 + 16 * g, dv);
       }
     }
   }
@@ -510,6 +512,7 @@ tail_expand_kernel(const T* __restrict__ X, const T* __restrict__ Wp, const floa
 // per lane and accumulator, and one wave's epilogue runs under the other wave's MFMAs.  GELU and its derivative by the same
 // gelu_erf_both as the kernel above (same values for the same pre-activation; the contraction order differs).
 // ---------------------------------------------------------------------------------------
+template <bool DER = true>
 __global__ void __launch_bounds__(512)
 tail_expand_f32_kernel(const float* __restrict__ X, const float* __restrict__ Wp, const float* __restrict__ bias, float* __restrict__ Y,
                        float* __restrict__ Yd, int M, int H, int Wd, int tiles_per_block, int x_p64) {
@@ -594,7 +597,7 @@ tail_expand_f32_kernel(const float* __restrict__ X, const float* __restrict__ Wp
             const int w = w0 + 32 * wm + 8 * rq + 4 * lh + e;           // D row = pixel 8 (r >> 2) + 4 h + (r & 3), col = channel li
             const long long off = (rowbase + (long long)si * 2 * Wd + 2 * w + sj) * 64 + 32 * ch + li;
             Y[off] = a4[e];
-            Yd[off] = d4[e];
+            if constexpr (DER) Yd[off] = d4[e];
           }
         }
       }
@@ -609,14 +612,14 @@ static int launch_tail_expand_t(const T* X, const T* Wp, const float* bias, T* Y
   int nblk = (int)std::min<long long>(ntiles, 1024);
   const int tpb = (int)ceil_divll(ntiles, nblk);
   nblk = (int)ceil_divll(ntiles, tpb);
-#define GO(NS_)                                                                                                        \
+#define GO(NS_, DER_)                                                                                                  \
   {                                                                                                                    \
     const size_t sh = sizeof(T) * (64 * NS_ + 128) * 72;                                                               \
-    (void)hipFuncSetAttribute((const void*)tail_expand_kernel<T, NS_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); \
-    hipLaunchKernelGGL((tail_expand_kernel<T, NS_>), dim3(nblk), dim3(256), sh, st, X, Wp, bias, Y, Yd, M, H, Wd, r, tpb, x_p64 ? 1 : 0); \
+    (void)hipFuncSetAttribute((const void*)tail_expand_kernel<T, NS_, DER_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); \
+    hipLaunchKernelGGL((tail_expand_kernel<T, NS_, DER_>), dim3(nblk), dim3(256), sh, st, X, Wp, bias, Y, Yd, M, H, Wd, r, tpb, x_p64 ? 1 : 0); \
   }
-  if (r == 2) GO(4)
-  else if (r == 3) GO(9)
+  if (r == 2) { if (Yd) GO(4, true) else GO(4, false) }
+  else if (r == 3) { if (Yd) GO(9, true) else GO(9, false) }
   else return m2t_set_error(-2, "tail_expand: r must be 2 or 3");
 #undef GO
   M2T_LAUNCH_CHECK();
@@ -625,7 +628,8 @@ static int launch_tail_expand_t(const T* X, const T* Wp, const float* bias, T* Y
 int launch_tail_expand(int dt, const void* X, const void* Wp, const float* bias, void* Y, void* Yd, long long M, int H, int Wd,
                        int r, bool x_p64, hipStream_t st) {
   if (dt == M2T_F32 && r == 3) {
-    // fp32 x3: the 576 x 64 fp32 weight matrix does not fit LDS beside the tile -> generic tiled GEMM
+    // fp32 x3: the 576 x 64 fp32 weight matrix does not fit LDS beside the tile -> generic tiled GEMM (whose epilogue always stores Yd)
+    if (!Yd) return m2t_set_error(-2, "tail_expand: the fp32 x3 path stores the derivative: Yd must not be null");
     m2t_gemm_args ga{};
     ga.A = X; ga.lda = x_p64 ? M2T_LD_P64 : 64; ga.W = Wp; ga.Y = Y; ga.ldy = 64; ga.bias = bias; ga.M = M; ga.N = 64 * r * r; ga.K = 64;
     ga.H = H; ga.Wd = Wd; ga.r = r; ga.C = 64;
@@ -638,9 +642,15 @@ int launch_tail_expand(int dt, const void* X, const void* Wp, const float* bias,
     const int tpb = ceil_div(ntiles, nblk);
     nblk = ceil_div(ntiles, tpb);
     const size_t sh = sizeof(float) * (256 + 2 * 128) * 68;
-    if (int rc__ = m2t_ensure_dynamic_lds((const void*)tail_expand_f32_kernel, (int)sh)) return rc__;
-    hipLaunchKernelGGL(tail_expand_f32_kernel, dim3(nblk), dim3(512), sh, st, (const float*)X, (const float*)Wp, bias, (float*)Y, (float*)Yd, (int)M, H, Wd,
-                       tpb, x_p64 ? 1 : 0);
+    if (Yd) {
+      if (int rc__ = m2t_ensure_dynamic_lds((const void*)tail_expand_f32_kernel<true>, (int)sh)) return rc__;
+      hipLaunchKernelGGL(tail_expand_f32_kernel<true>, dim3(nblk), dim3(512), sh, st, (const float*)X, (const float*)Wp, bias, (float*)Y, (float*)Yd, (int)M, H, Wd,
+                         tpb, x_p64 ? 1 : 0);
+    } else {
+      if (int rc__ = m2t_ensure_dynamic_lds((const void*)tail_expand_f32_kernel<false>, (int)sh)) return rc__;
+      hipLaunchKernelGGL(tail_expand_f32_kernel<false>, dim3(nblk), dim3(512), sh, st, (const float*)X, (const float*)Wp, bias, (float*)Y, (float*)Yd, (int)M, H, Wd,
+                         tpb, x_p64 ? 1 : 0);
+    }
     M2T_LAUNCH_CHECK();
     return 0;
   }

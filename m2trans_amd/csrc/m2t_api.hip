@@ -106,6 +106,12 @@ struct m2t_plan {
   int pack_nb_base = 0, pack_nb_copy = 0, pack_nb_tr = 0;   // workgroups of the three groups (round 5: the default bf16 path skips the last two:
                                              // 6.3 M of the 14.2 M packed elements, the transposes being the slowest gathers of the kernel)
   bool have_seed = false, have_acts = false;
+  // option "inference": m2t_forward alone, on a forward-only workspace.  lay.ws / the workspace offsets of hd are then those of
+  // inference_layout(), rebuilt after every change of an option; the training layout m2t_plan_create built waits in train_ws / train_hd
+  int inference = 0;
+  bool ws_initialised = false;         // m2t_plan_init_workspace has run: "inference" is frozen, and so is every option of an inference plan
+  m2t_region train_ws;
+  m2t_plan_handles train_hd;
   // m2t_l1_loss_deferred: the loss and the seed are produced inside the next m2t_backward (round 5)
   bool l1_deferred = false;
   const float* l1_hr = nullptr; float* l1_loss_out = nullptr; float l1_sc = 0.f, l1_R = 0.f;
@@ -243,6 +249,94 @@ static void resolve_schedule(m2t_plan* p) {
 
 static const int BR_C[4] = {16, 64, 256, 256};
 static const int BR_L[4] = {0, 1, 2, 2};
+
+// ---- the workspace of an inference plan (option "inference") ---------------------------------------------------------------------
+// A region the forward of the schedule in force never reads is ABSENT: its handle is M2T_NO_REGION, its name is not in the table
+// (m2t_plan_query answers -1) and the kernel that would write it gets a null pointer.
+static const size_t M2T_NO_REGION = ~(size_t)0;
+static inline char* region_ptr(char* ws, size_t off) { return off == M2T_NO_REGION ? nullptr : ws + off; }
+
+// Does m2t_forward need the region d<i + 1> / qkv<i + 1> under schedule s?  (A training plan stores both for the backward pass whatever
+// this says.)
+static bool forward_reads_d(const m2t_sched& s, int i) {
+  if (i == 0) return !s.c16_fused_fwd;                       // the fused C = 16 kernel normalises in registers: d1 is "for the backward"
+  if (!s.prep_in_fwd) return true;                           // branch_prep writes d, the projection reads it
+  // branch_prep inside the fused kernel: nothing reads d in the forward.  The C = 64 kernel has an instantiation without the store; the
+  // C = 256 kernels keep it (k_attn_fused.hip: at 256 VGPRs the kernel spills without it; k_attn_fwd2.hip takes no null), and so their region
+  return BR_C[i] == 256;
+}
+static bool forward_reads_qkv(const m2t_sched& s, int i) {
+  if (i == 0) return !s.c16_fused_fwd;
+  if (!s.c64_fused_fwd) return true;                         // projection GEMM -> attention kernel
+  return BR_C[i] == 256 && s.prep_in_fwd && s.fwd2 != 0;     // k_attn_fwd2.hip re-reads the window's own v rows from the qkv tensor
+}
+
+// The persistent regions and X0 where the training layout has them; X1 .. X<nb> alternate between two buffers (block b reads X<b> and
+// writes X<b + 1>; the last block's conv adds X0); ONE set of per-block regions under every "b<k>." name; nothing of the backward pass.
+static void inference_layout(m2t_plan* p) {
+  const m2t_sched& s = p->sc;
+  const size_t es = p->esz;
+  const int B = p->B, sc = p->scale, r0 = (sc == 4) ? 2 : sc;
+  const long long BP = (long long)B * p->P;
+  m2t_region ws;
+  m2t_plan_handles hd = p->train_hd;                         // parameter and pack offsets carry over; every workspace offset is set below
+  auto alias = [&ws](const std::string& name, const std::string& of) { ws.t[name] = ws.t.at(of); };
+  hd.zero_page = ws.add("zero_page", 256, 1);
+  hd.pack_descs = ws.add("pack_descs", p->descs.size() * sizeof(m2t_pack_desc), 1);
+  hd.pack_blocks = ws.add("pack_blocks", p->pack_blocks.size() * sizeof(int), 1);
+  hd.packed = ws.add("packed", p->lay.npacked, es);
+  hd.X[0] = ws.add("X0", BP * 64, es);
+  for (int b = 1; b <= p->nb; ++b) {
+    const std::string name = "X" + std::to_string(b);
+    if (b <= 2) hd.X[b] = ws.add(name, BP * 64, es);
+    else { alias(name, "X" + std::to_string(b - 2)); hd.X[b] = hd.X[b - 2]; }
+  }
+  m2t_block_handles b0 = hd.blk[0];
+  b0.mean = ws.add("b0.mean", B * 64, 4);
+  b0.rstd = ws.add("b0.rstd", B * 64, 4);
+  b0.xc = ws.add("b0.xc", BP * 64, es);
+  for (int i = 0; i < 4; ++i) {
+    b0.d[i] = forward_reads_d(s, i) ? ws.add("b0.d" + std::to_string(i + 1), BP * 16, es) : M2T_NO_REGION;
+    b0.qkv[i] = forward_reads_qkv(s, i) ? ws.add("b0.qkv" + std::to_string(i + 1), BP * 48, es) : M2T_NO_REGION;
+  }
+  for (int b = 0; b < p->nb; ++b) {
+    m2t_block_handles& bh = hd.blk[b];
+    bh.mean = b0.mean; bh.rstd = b0.rstd; bh.xc = b0.xc;
+    for (int i = 0; i < 4; ++i) { bh.d[i] = b0.d[i]; bh.qkv[i] = b0.qkv[i]; }
+    if (b == 0) continue;
+    const std::string k = "b" + std::to_string(b) + ".";
+    alias(k + "mean", "b0.mean"); alias(k + "rstd", "b0.rstd"); alias(k + "xc", "b0.xc");
+    for (int i = 0; i < 4; ++i) {
+      if (b0.d[i] != M2T_NO_REGION) alias(k + "d" + std::to_string(i + 1), "b0.d" + std::to_string(i + 1));
+      if (b0.qkv[i] != M2T_NO_REGION) alias(k + "qkv" + std::to_string(i + 1), "b0.qkv" + std::to_string(i + 1));
+    }
+  }
+  hd.xin = ws.add("xin", BP * 16, es);
+  hd.norm_part = ws.add("norm_part", (size_t)B * 8 * M2T_NORM_SPLIT * 64 * 3, 4);
+  hd.vring = s.fwd2 != 0 ? ws.add("vring", window_attn_fwd2_vring_elems(B, p->H / 4, p->W / 4), es) : M2T_NO_REGION;
+  hd.t1act = s.stores_t1 ? ws.add("t1act", BP * r0 * r0 * 64, es) : M2T_NO_REGION;
+  // gelu'(t1): read by the backward pass alone.  fp32 x3 keeps it: that expansion runs on the generic GEMM, whose epilogue always stores it
+  hd.t1der = (p->dt == M2T_F32 && sc == 3) ? ws.add("t1der", BP * r0 * r0 * 64, es) : M2T_NO_REGION;
+  hd.t2act = s.stores_t2 ? ws.add("t2act", BP * 16 * 64, es) : M2T_NO_REGION;
+  hd.srpre = ws.add("srpre", (size_t)B * 3 * p->Hsp * p->Wsp, 4);
+  ws.seal();
+  hd.norm_s = hd.norm_part0 = hd.t2der = hd.loss_part = hd.gpre = hd.g_t2pre = hd.g_t1pre = hd.gT = hd.gA = hd.gB = hd.gxc = hd.gn =
+      hd.gd = hd.gd2 = hd.gdwin = hd.gdwin2 = hd.head_cols = hd.arena = hd.red_descs = M2T_NO_REGION;
+  for (int set = 0; set < 2; ++set)
+    for (int i = 0; i < 4; ++i) hd.gqkv[set][i] = hd.win[set][i] = hd.relw[set][i] = M2T_NO_REGION;
+  p->lay.ws = ws;
+  p->hd = hd;
+}
+
+// the layout that goes with p->inference and the schedule in force (resolve_schedule first)
+static void resolve_layout(m2t_plan* p, bool was_inference) {
+  if (p->inference) inference_layout(p);
+  else if (was_inference) { p->lay.ws = p->train_ws; p->hd = p->train_hd; }
+}
+static int refuse_inference(const m2t_plan* p, const char* who) {
+  if (!p->inference) return 0;
+  return m2t_set_error_at(M2T_ERR_STATE, who, "this is an inference plan (option \"inference\"): it keeps no activations and no seed");
+}
 
 extern "C" int m2t_version(void) { return 100; }
 extern "C" const char* m2t_last_error_string(void) { return g_err.c_str(); }
@@ -410,6 +504,8 @@ extern "C" int m2t_plan_create(m2t_plan** out, int B, int H0, int W0, int scale,
     p->buckets.push_back({0, hi});
   }
   resolve_schedule(p);
+  p->train_ws = lay.ws;
+  p->train_hd = hd;
   *out = p;
   return 0;
 }
@@ -450,6 +546,7 @@ extern "C" long long m2t_plan_query(const m2t_plan* p, const char* key) {
     if (o == "fused_c16_fwd") return !s.c16_fused_fwd ? 0 : (s.c16_recompute ? 2 : 1);
     if (o == "fused_qkv_dgrad") return s.fused_dgrad;
     if (o == "debug_skip_side") return p->debug_skip_side;
+    if (o == "inference") return p->inference;
     return -1;
   }
   // which stored tensors the current options leave unwritten (tests read the workspace by name)
@@ -474,6 +571,7 @@ extern "C" int m2t_plan_init_workspace(m2t_plan* p, void* workspace, void* strea
   if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
   p->have_acts = p->have_seed = false;
   p->l1_deferred = false;
+  p->ws_initialised = true;
   // red_descs lives in the workspace: a workspace that was just (re)initialised -- possibly another buffer, possibly overwritten --
   // does not hold the published table, so the next all-stages backward publishes it again (the first_backward schedule)
   p->red_uploaded = false;
@@ -490,6 +588,8 @@ struct F32FastGuard {
 extern "C" int m2t_forward(m2t_plan* p, const float* params, const float* x, float* sr, float rgb_range,
                            int keep_activations, void* workspace, void* stream) {
   if (!p || !params || !x || !workspace) return m2t_set_error(M2T_ERR_ARG, "m2t_forward: null argument");
+  if (p->inference && keep_activations != 0)
+    return m2t_set_error(M2T_ERR_STATE, "m2t_forward: keep_activations != 0 on an inference plan (option \"inference\"): it keeps nothing");
   hipStream_t st = (hipStream_t)stream;
   F32FastGuard f32_fast_guard(p->use_fp32_fast);
   const m2t_sched& sc = p->sc;
@@ -498,7 +598,8 @@ extern "C" int m2t_forward(m2t_plan* p, const float* params, const float* x, flo
   auto pk = [&](long long off) { return ws + hd.packed + (size_t)off * p->esz; };      // a packed weight
   const int dt = p->dt, B = p->B, H = p->H, W = p->W, s = p->scale;
   const long long BP = (long long)B * p->P;
-  (void)keep_activations;   // v1 keeps every activation in the workspace either way
+  // a training plan keeps every activation whatever keep_activations says; on an inference plan the regions the forward never reads
+  // are absent: region_ptr() hands the kernels a null pointer for them (on a training plan every region is present)
   // (re-packing on the side stream under the head conv was measured: -0.4 %, both kernels are bound by workgroup launch rate)
   {
     // the plain / transposed copies of the C >= 64 qkv weights are read only by the unfused projection GEMMs (forward / data gradient):
@@ -526,8 +627,8 @@ extern "C" int m2t_forward(m2t_plan* p, const float* params, const float* x, flo
       const int C = BR_C[i], L = BR_L[i];
       const int h = H >> L, w = W >> L;
       const long long M = (long long)B * h * w;
-      void* d = ws + bh.d[i];
-      void* qkv = ws + bh.qkv[i];
+      void* d = region_ptr(ws, bh.d[i]);
+      void* qkv = region_ptr(ws, bh.qkv[i]);
       const float* rh = params + bh.rel_h[i];
       const float* rw = params + bh.rel_w[i];
       void* xc_i = (char*)xc + (size_t)i * BP * 16 * p->esz;       // chunk i of the P64 concat buffer: a dense plane
@@ -537,13 +638,13 @@ extern "C" int m2t_forward(m2t_plan* p, const float* params, const float* x, flo
         continue;
       }
       // C = 64: qkv is written for the backward pass unless that recomputes it
-      void* qkv_out = (C == 64 && !sc.stores_qkv2) ? nullptr : qkv;
+      void* qkv_out = (C == 64 && !sc.stores_qkv2) ? nullptr : qkv;      // (inference plan: qkv itself is null on the fused paths)
       if (sc.prep_in_fwd && C >= 64) {
         // branch_prep (norm apply + mix + DWT^L), the qkv projection, the window attention and IWT^L / residual in one kernel
         const void* xn_i = (const char*)X + (size_t)i * BP * 16 * p->esz;
         const void* xprev = (const char*)xc + (size_t)(i - 1) * BP * 16 * p->esz;
         if (C == 256 && sc.fwd2 != 0)      // more windows than CUs: the kernels that put two windows on a CU (k_attn_fwd2.hip)
-          CK(launch_window_attn_fused_prep_fwd2(xn_i, xprev, mean, rstd, i, ws + hd.xin, d, pk(bh.wF[i]), rh, rw, qkv, xc_i, ws + hd.vring, B, h, w, sc.fwd2, st));
+          CK(launch_window_attn_fused_prep_fwd2(xn_i, xprev, mean, rstd, i, ws + hd.xin, d, pk(bh.wF[i]), rh, rw, qkv, xc_i, region_ptr(ws, hd.vring), B, h, w, sc.fwd2, st));
         else
           CK(launch_window_attn_fused_prep_fwd(xn_i, xprev, mean, rstd, i, ws + hd.xin, d, pk(bh.wF[i]), rh, rw, qkv_out, xc_i, B, h, w, C, L, st));
         continue;
@@ -581,7 +682,7 @@ extern "C" int m2t_forward(m2t_plan* p, const float* params, const float* x, flo
     CK(launch_tail_fwd_stream(Y, 1, pk(hd.t0), params + hd.tail0_b, wlast, srpre, B, H, W, r0, 0, st));
   } else {
     { M2TProfScope ps(M2T_PROF_TAIL_GEMM, st);
-      CK(launch_tail_expand(dt, Y, pk(hd.t0), params + hd.tail0_b, ws + hd.t1act, ws + hd.t1der, BP, H, W, r0, true, st)); }
+      CK(launch_tail_expand(dt, Y, pk(hd.t0), params + hd.tail0_b, ws + hd.t1act, region_ptr(ws, hd.t1der), BP, H, W, r0, true, st)); }
     if (sc.tail_fwd == TAIL_FWD_STREAM) {
       M2TProfScope ps(M2T_PROF_TAIL_FWD_FUSED, st);
       CK(launch_tail_fwd_stream(ws + hd.t1act, 0, pk(hd.t3), params + hd.tail3_b, wlast, srpre, B, 2 * H, 2 * W, 2, 0, st));
@@ -591,14 +692,14 @@ extern "C" int m2t_forward(m2t_plan* p, const float* params, const float* x, flo
     } else {
       if (s == 4) {
         M2TProfScope ps(M2T_PROF_TAIL_GEMM, st);
-        CK(launch_tail_expand(dt, ws + hd.t1act, pk(hd.t3), params + hd.tail3_b, ws + hd.t2act, ws + hd.t2der, BP * 4, 2 * H, 2 * W, 2, false, st));
+        CK(launch_tail_expand(dt, ws + hd.t1act, pk(hd.t3), params + hd.tail3_b, ws + hd.t2act, region_ptr(ws, hd.t2der), BP * 4, 2 * H, 2 * W, 2, false, st));
       }
       M2TProfScope ps(M2T_PROF_FINAL_FWD, st);
       CK(launch_final_conv_fwd(dt, ws + (s == 4 ? hd.t2act : hd.t1act), wlast, srpre, B, p->Hsp, p->Wsp, st));
     }
   }
   if (sr) CK(launch_clamp_l1(srpre, nullptr, sr, nullptr, nullptr, nullptr, B, p->Hsp, p->Wsp, p->Hs, p->Ws, rgb_range, 0.f, 0.f, st));
-  p->have_acts = true;
+  p->have_acts = !p->inference;      // an inference forward leaves neither activations nor a seed
   p->have_seed = false;
   p->l1_deferred = false;
   return 0;
@@ -622,6 +723,7 @@ extern "C" int m2t_pixel_loss(m2t_plan* p, int kind, float param, const float* h
   if (!p || !hr || !workspace) return m2t_set_error(M2T_ERR_ARG, "m2t_pixel_loss: null argument");
   M2TPixelLoss pl;
   CK(pixel_loss_request("m2t_pixel_loss", kind, param, weight, divisor, &pl));
+  CK(refuse_inference(p, "m2t_pixel_loss"));
   if (!p->have_acts) return m2t_set_error(M2T_ERR_STATE, "m2t_pixel_loss: call m2t_forward first");
   char* const ws = (char*)workspace;
   CK(launch_clamp_l1((const float*)(ws + p->hd.srpre), hr, nullptr, (float*)(ws + p->hd.gpre), (float*)(ws + p->hd.loss_part), loss_out,
@@ -644,6 +746,7 @@ extern "C" int m2t_pixel_loss_deferred(m2t_plan* p, int kind, float param, const
   if (!p || !hr || !workspace || !loss_out) return m2t_set_error(M2T_ERR_ARG, "m2t_pixel_loss_deferred: null argument");
   M2TPixelLoss pl;
   CK(pixel_loss_request("m2t_pixel_loss_deferred", kind, param, weight, divisor, &pl));
+  CK(refuse_inference(p, "m2t_pixel_loss_deferred"));
   if (!p->have_acts) return m2t_set_error(M2T_ERR_STATE, "m2t_pixel_loss_deferred: call m2t_forward first");
   p->l1_hr = hr; p->l1_loss_out = loss_out; p->l1_sc = pl.loss_scale; p->l1_R = rgb_range; p->l1_pl = pl;
   p->l1_deferred = true;
@@ -674,6 +777,7 @@ __global__ void __launch_bounds__(256) seed_from_grad_kernel(const float* __rest
 }
 extern "C" int m2t_set_output_grad(m2t_plan* p, const float* g_sr, float rgb_range, void* workspace, void* stream) {
   if (!p || !g_sr || !workspace) return m2t_set_error(M2T_ERR_ARG, "m2t_set_output_grad: null argument");
+  CK(refuse_inference(p, "m2t_set_output_grad"));
   if (!p->have_acts) return m2t_set_error(M2T_ERR_STATE, "m2t_set_output_grad: call m2t_forward first");
   char* const ws = (char*)workspace;
   const long long total = (long long)p->B * 3 * p->Hsp * p->Wsp;
@@ -691,6 +795,7 @@ extern "C" int m2t_set_output_grad(m2t_plan* p, const float* g_sr, float rgb_ran
 extern "C" int m2t_add_output_grad(m2t_plan* p, const float* g, int gh, int gw, const int* crops_host, float scale, float rgb_range,
                                    void* workspace, void* stream) {
   if (!p || !g || !workspace || gh < 1 || gw < 1) return m2t_set_error(M2T_ERR_ARG, "m2t_add_output_grad: null / bad argument");
+  CK(refuse_inference(p, "m2t_add_output_grad"));
   if (!p->have_acts || !p->have_seed || p->l1_deferred)
     return m2t_set_error(M2T_ERR_STATE, "m2t_add_output_grad: needs a materialised seed (m2t_l1_loss / m2t_pixel_loss or m2t_set_output_grad)");
   for (int b = 0; b < p->B; ++b) {
@@ -732,6 +837,7 @@ static int loss_entry_args(const char* who, bool any_null, float rgb_range, doub
 static int loss_entry_seed(const char* who, const m2t_plan* p, bool batch_ok, const char* batch_cap, void* workspace, LossSeed* s,
                            const char* term_state_refusal = nullptr) {
   if (!batch_ok) return m2t_set_error_at(M2T_ERR_ARG, who, batch_cap);
+  CK(refuse_inference(p, who));
   if (term_state_refusal) return m2t_set_error_at(M2T_ERR_STATE, who, term_state_refusal);
   if (!p->have_acts || !p->have_seed || p->l1_deferred)
     return m2t_set_error_at(M2T_ERR_STATE, who, "needs a materialised seed (m2t_l1_loss / m2t_pixel_loss or m2t_set_output_grad)");
@@ -1339,6 +1445,7 @@ static int backward_impl(m2t_plan* p, const float* params, const float* x, float
 extern "C" int m2t_backward(m2t_plan* p, const float* params, const float* x, float* grads, void* workspace,
                             void* stream) {
   if (!p || !params || !x || !grads || !workspace) return m2t_set_error(M2T_ERR_ARG, "m2t_backward: null argument");
+  CK(refuse_inference(p, "m2t_backward"));
   if (!p->have_acts || !p->have_seed)
     return m2t_set_error(M2T_ERR_STATE, "m2t_backward: needs m2t_forward and a seed (m2t_l1_loss / m2t_set_output_grad)");
   return backward_impl(p, params, x, grads, nullptr, nullptr, workspace, stream);
@@ -1352,6 +1459,7 @@ extern "C" int m2t_backward_ex(m2t_plan* p, const float* params, const float* x,
   if (!any && !gx) return m2t_set_error(M2T_ERR_ARG, "m2t_backward_ex: nothing requested (no stage flag set and gx == NULL)");
   if (any && !grads) return m2t_set_error(M2T_ERR_ARG, "m2t_backward_ex: a stage flag is set but grads is NULL");
   if ((!need_stage || need_stage[0]) && !x) return m2t_set_error(M2T_ERR_ARG, "m2t_backward_ex: the head's gradient needs x");
+  CK(refuse_inference(p, "m2t_backward_ex"));
   if (!p->have_acts || !p->have_seed)
     return m2t_set_error(M2T_ERR_STATE, "m2t_backward_ex: needs m2t_forward and a seed (m2t_l1_loss / m2t_set_output_grad)");
   return backward_impl(p, params, x, grads, gx, need_stage, workspace, stream);
@@ -1359,6 +1467,7 @@ extern "C" int m2t_backward_ex(m2t_plan* p, const float* params, const float* x,
 
 extern "C" int m2t_stream_wait_bucket(m2t_plan* p, int bucket, void* stream) {
   if (!p || bucket < 0 || (size_t)bucket >= p->buckets.size()) return m2t_set_error(M2T_ERR_ARG, "m2t_stream_wait_bucket: bad bucket");
+  CK(refuse_inference(p, "m2t_stream_wait_bucket"));
   if (p->bucket_events.size() != p->buckets.size()) return m2t_set_error(M2T_ERR_STATE, "m2t_stream_wait_bucket: call m2t_backward first");
   hipError_t e = hipStreamWaitEvent((hipStream_t)stream, p->bucket_events[bucket], 0);
   if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
@@ -1367,10 +1476,21 @@ extern "C" int m2t_stream_wait_bucket(m2t_plan* p, int bucket, void* stream) {
 
 extern "C" int m2t_set_option(m2t_plan* p, const char* key, long long value) {
   if (!p || !key) return m2t_set_error(M2T_ERR_ARG, "m2t_set_option: null");
+  const std::string k(key);
+  if (k == "inference") {
+    if (p->ws_initialised)
+      return m2t_set_error(M2T_ERR_STATE, "m2t_set_option: \"inference\" makes or unmakes an inference plan only before the first m2t_plan_init_workspace");
+    const bool was = p->inference != 0;
+    p->inference = value != 0;
+    p->have_acts = p->have_seed = p->l1_deferred = false;
+    resolve_layout(p, was);
+    return 0;
+  }
+  if (p->inference && p->ws_initialised)
+    return m2t_set_error(M2T_ERR_STATE, "m2t_set_option: the layout of an initialised inference plan is frozen (set options before m2t_plan_init_workspace)");
   p->red_uploaded = false;     // the deferred-reduction table depends on the schedule: rebuild it on the next backward
   for (auto& kv : p->mask_tables) kv.second.uploaded = false;
-  struct Resolve { m2t_plan* p; ~Resolve() { resolve_schedule(p); } } resolve_on_return{p};     // whichever raw value changes below
-  const std::string k(key);
+  struct Resolve { m2t_plan* p; ~Resolve() { resolve_schedule(p); resolve_layout(p, false); } } resolve_on_return{p};     // whichever raw value changes below
   if (k == "side_stream") { p->use_side = (value != 0); return 0; }
   if (k == "fork_on_kernel") { p->fork_on_kernel = value != 0; return 0; }
   if (k == "fused_prep_fwd") { p->use_fused_prep_fwd = value != 0; return 0; }

@@ -136,7 +136,7 @@ int launch_gemm_nt(int dt, int amode, int emode, const m2t_gemm_args& a, hipStre
 // 0 = the 16x16x4 kernels of rounds 1-4 (option fp32_fast of the plan being run; set by m2t_api.hip on entry)
 extern thread_local int g_m2t_f32_fast;
 // upsampler 1x1 conv + bias + pixel-shuffle scatter + GELU, K = 64, N = 64 r^2; X rows over [B][H][Wd];
-// Y = gelu(t), Yd = gelu'(t) (both [B][H r][Wd r][64])
+// Y = gelu(t), Yd = gelu'(t) (both [B][H r][Wd r][64]); Yd == nullptr: the derivative is not stored (inference plans)
 int launch_tail_expand(int dt, const void* X, const void* Wp, const float* bias, void* Y, void* Yd, long long M, int H, int Wd,
                        int r, bool x_p64, hipStream_t st);   // x_p64: X is a P64 feature map (else rows of 64)
 // dW[N][K] (fp32 slabs) = sum_m G[m][N]^T X[m][K];  G/X side variants as above

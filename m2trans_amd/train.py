@@ -383,7 +383,7 @@ def _dump_yaml(obj, path):
 
 # ------------------------------------------------------------------------------------------------------------------------- CLI
 # the reference's yaml keys (configs/M2Trans_x*.yml) ...
-MODEL_KEYS = ("model", "scale", "rgb_range", "colors", "n_feats", "n_blocks", "compute_dtype")
+MODEL_KEYS = ("model", "scale", "rgb_range", "colors", "n_feats", "n_blocks", "compute_dtype", "lean_inference")
 REFERENCE_KEYS = MODEL_KEYS + ("pretrain", "patch_size", "batch_size", "data_repeat", "data_augment", "data_add_noise", "cutout", "cutmix",
                                "epochs", "lr", "eta_min", "gamma", "log_every", "test_every", "log_path", "log_name", "lambda_l1",
                                "lambda_clip", "save_image", "data_path", "training_dataset", "eval_sets")
@@ -450,6 +450,9 @@ def resolve_config(cfg: dict, compute_dtype=None) -> dict:
     model.setdefault("colors", 3)
     if compute_dtype is not None:
         model["compute_dtype"] = compute_dtype
+    if "lean_inference" in model:            # validation forwards on inference plans (M2Trans.lean_inference); training plans stay cached
+        if not isinstance(model["lean_inference"], bool):
+            raise M2TError(f"lean_inference must be true or false, got {model['lean_inference']!r}")
     ts = {"lr": float(cfg["lr"]), "lambda_l1": float(cfg.get("lambda_l1", 1.0)), "lambda_clip": 0.0, "world_size": 1}
     ts.update({k: cfg[k] for k in TRAINSTEP_KEYS if k in cfg})
     if "track_grad_norm" in cfg:
