@@ -1,7 +1,8 @@
 """CPU only: the backward stage gate of tests/bwd_stage_ref.py checked against itself before it judges a device run.
 
   1. consistency   the stage references chained from the oracle's own seed, and the explicit chain without the kernels' rounding points,
-                   reproduce plain torch.autograd.grad of the oracle to 1e-12 for every tap and lr.grad;
+                   reproduce plain torch.autograd.grad of the oracle to 1e-12 for every tap, lr.grad and every trainable parameter
+                   (param_refs on the chained tap references; the parameter half's faults: tests/test_wgrad_stage_reference_cpu.py);
   2. faults        one-line faults injected into the emulated taps (which play the device) fail the gate at the expected (tap, class),
                    and only downstream of the faulted stage; the unfaulted emulation passes with every ratio <= 1;
   3. the gap       the three ring faults pass today's criteria (GRAD_REL / GRAD_OF_TOTAL per parameter tensor, lr.grad rel-rms 2e-2).
@@ -34,13 +35,19 @@ def _cell(scale, nb, B, H0, W0, dtype, leaf_params=False):
 @pytest.mark.parametrize("scale", [4, 2, 3])
 @pytest.mark.parametrize("dtype", ["bf16", "fp32"])
 def test_chained_stage_references_reproduce_autograd(dtype, scale, nb, shape):
-    g, g_sr, gpre = _cell(scale, nb, *shape, dtype)
+    g, g_sr, gpre = _cell(scale, nb, *shape, dtype, True)
     want = R.autograd_taps(g, g_sr)
     chained = R.stage_refs(g, {"gpre": gpre}, chain=True)
     assert set(chained) == set(want)
-    for what, got in (("stage references, chained", chained), ("explicit chain, no rounding points", R.emulate(g, gpre, points=False))):
+    # the parameter gradients: param_refs with the chained tap references as cotangents, and the explicit chain's own
+    want_p = R.autograd_param_grads(g, g_sr)
+    chained_p = R.param_refs(g, dict(chained, gpre=gpre))
+    assert set(chained_p) == set(want_p) == set(O.trainable_names(g.p))
+    want = dict(want, **want_p)
+    for what, got in (("stage references, chained", dict(chained, **chained_p)),
+                      ("explicit chain, no rounding points", R.emulate(g, gpre, points=False))):
         err = R.errors(g, got, want)
-        assert len(err) >= 20
+        assert len(err) >= 20 and set(want_p) <= {k[0] for k in err}
         bad = {k: e for k, e in err.items() if not e <= 1e-12}
         assert not bad, (what, bad)
 
