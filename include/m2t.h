@@ -133,7 +133,27 @@ long long m2t_plan_query(const m2t_plan* p, const char* key);
  *                           cleared only before the first m2t_plan_init_workspace; on an initialised inference plan every other
  *                           m2t_set_option is M2T_ERR_STATE (the layout is frozen), as are m2t_forward with keep_activations != 0, every
  *                           plan-taking loss entry, m2t_set_output_grad / m2t_add_output_grad, m2t_backward / m2t_backward_ex and
- *                           m2t_stream_wait_bucket: an inference forward leaves neither activations nor a seed */
+ *                           m2t_stream_wait_bucket: an inference forward leaves neither activations nor a seed
+ *   "local_norm"        [0] 0 = off; 8 .. 16384 = T: LOCAL-WINDOW InstanceNorm statistics (the Test-time Local Converter of Chu et al.,
+ *                           ECCV 2022): every CFTM block normalises each pixel with the statistics of a T x T window around it instead
+ *                           of the whole plane's.  Anything else is M2T_ERR_ARG.  Legal only on a plan whose "inference" is already 1 and
+ *                           only before the first m2t_plan_init_workspace (else M2T_ERR_STATE, the text says which rule); clearing
+ *                           "inference" while "local_norm" > 0 is M2T_ERR_STATE.  Definition, for a block input X on the padded plane
+ *                           H x W (multiples of 32) and per axis k = min(T, side):
+ *                             - the window of output row y is rows [i, i + k_h), i = clamp(y - (k_h - 1) / 2, 0, H - k_h), integer
+ *                               division; columns likewise.  This is TLC's integral-image average: a left pad of (k - 1) / 2, a right pad
+ *                               of k / 2, replicated edges.  Every window is full: the count is n = k_h k_w everywhere.
+ *                             - per image, channel and pixel: S1 = sum x and S2 = sum x^2 over the window, in fp64 from the stored X
+ *                               (plan dtype); m = S1 / n; v = max(S2 / n - m^2, 0); r = 1 / sqrt(v + 1e-5) (biased variance,
+ *                               InstanceNorm2d's eps), all in fp64.
+ *                             - mean32 = fl32(m), rstd32 = fl32(r); xn = round_to_plan_dtype((fl32(x) - mean32) * rstd32), the
+ *                               subtraction and the product as separate fp32 operations.
+ *                           T >= max(H, W) is the global InstanceNorm over the plane, in this arithmetic.  (Parity with the TLC code
+ *                           itself is unpinned.)  Per block: statistics + apply -> "ws:xn" (through the fp64 sums "ws:lnsum"), then the
+ *                           forward's launches in their order on xn with the identity record "ws:norm_id" (mean = 0 then rstd = 1, [B][64]
+ *                           floats each); the 3 x 3 conv keeps the un-normalised X as its residual and emits no statistics partials.
+ *                           The three regions answer -1 while the option is 0, and then every plan is laid out and launched as before.
+ *                           The last block's input stays in place: "ws:X<n_blocks - 1>" */
 int m2t_set_option(m2t_plan* p, const char* key, long long value);
 /* Gradient buckets for communication overlap (replaces the reduce-to-GPU-0 of nn.DataParallel, train.py:73):
  * m2t_backward completes the flat gradient buffer in "grad_buckets" contiguous ranges, in this order: tail, block
@@ -148,7 +168,8 @@ int m2t_stream_wait_bucket(m2t_plan* p, int bucket, void* stream);
  * reductions), written by the first all-stages m2t_backward after this call.  Every other region is scratch WITHIN one step: each
  * m2t_forward / m2t_backward writes whatever it reads before it reads it, so the contents left by an earlier step (or by the
  * allocator) never reach a result -- tests/test_gpu_schedule.py fills them with NaN between steps.  (An inference plan has the first
- * three persistent regions and no "red_descs"; the same contract holds for its aliased layout: tests/test_gpu_lean_inference.py.)
+ * three persistent regions and no "red_descs"; the same contract holds for its aliased layout: tests/test_gpu_lean_inference.py.
+ * With option "local_norm" > 0 it has a fourth, "norm_id", written here: tests/test_gpu_local_norm.py.)
  * Calling this again on a live plan is legal (with the same or another buffer, once the plan's earlier work on `stream` is
  * enqueued): it returns the plan to "no activations, no seed", and the next all-stages backward publishes "red_descs" again. */
 int m2t_plan_init_workspace(m2t_plan* p, void* workspace, void* stream);

@@ -52,10 +52,11 @@ class Plan:
     """m2t_plan + its workspace (one per (B, H0, W0, dtype)).  ``inference=True``: an inference plan (option "inference" of
     include/m2t.h) -- m2t_forward alone, on a forward-only workspace; every entry that needs activations or a seed refuses it.
     ``options``: {key: value} for m2t_set_option, set before the workspace is sized and initialised (an initialised inference plan
-    takes no option any more)."""
+    takes no option any more).  ``local_norm=T`` (8 .. 16384, inference plans only): option "local_norm", every block normalises each
+    pixel with the statistics of the T x T window around it (the Test-time Local Converter; include/m2t.h has the definition)."""
 
     def __init__(self, B: int, H0: int, W0: int, scale: int, n_blocks: int, dtype: int, device, inference: bool = False,
-                 options=None):
+                 options=None, local_norm: int = 0):
         lib = _lib.load()
         h = C.c_void_p()
         self.handle = None
@@ -66,6 +67,9 @@ class Plan:
             self.inference = bool(inference)
             if self.inference:           # before the size query: the option decides the layout
                 _lib.check(lib.m2t_set_option(h, b"inference", 1), "m2t_set_option(inference)")
+            self.local_norm = int(local_norm or 0)
+            if self.local_norm:          # (on a training plan the library refuses it: M2T_ERR_STATE)
+                _lib.check(lib.m2t_set_option(h, b"local_norm", self.local_norm), "m2t_set_option(local_norm)")
             for k, v in (options or {}).items():
                 _lib.check(lib.m2t_set_option(h, str(k).encode(), int(v)), f"m2t_set_option({k})")
             self.B, self.H0, self.W0, self.scale, self.n_blocks, self.dtype = B, H0, W0, scale, n_blocks, dtype
@@ -187,6 +191,8 @@ class M2Trans(nn.Module):
     # lean_inference(): forwards that take no autograd edge run on inference plans.  A plain attribute (class default: off), so
     # copy.deepcopy, pickle and the replicas of nn.DataParallel carry it
     lean_inference_enabled = False
+    # local_norm(T): those forwards use local-window InstanceNorm statistics (option "local_norm"); 0 = off.  A plain attribute as well
+    local_norm_window = 0
 
     def __init__(self, args):
         super().__init__()
@@ -203,6 +209,8 @@ class M2Trans(nn.Module):
         self.compute_dtype = str(cd)
         if getattr(args, "lean_inference", False):           # optional yaml key (train.py: validation on inference plans)
             self.lean_inference_enabled = True
+        if getattr(args, "local_norm", None):                # optional yaml key: validation with local-window statistics
+            self.local_norm(args.local_norm)
         self._plans: "OrderedDict[Tuple, Plan]" = OrderedDict()
         self._dp_master = None                       # set on the replicas nn.DataParallel makes of this module
         self._dp_params = None
@@ -482,17 +490,38 @@ class M2Trans(nn.Module):
         self.lean_inference_enabled = bool(enabled)
         return self
 
-    def _plan_for(self, x: torch.Tensor, inference: bool = False) -> Plan:
+    def local_norm(self, T=96) -> "M2Trans":
+        """Local-window InstanceNorm statistics at test time (the Test-time Local Converter of Chu et al., ECCV 2022): forwards
+        without an autograd edge normalise every pixel of every block with the statistics of the ``T x T`` window around it
+        (``T`` = 8 .. 16384, clamped at the borders; include/m2t.h, option "local_norm", has the definition) instead of the whole
+        plane's -- the statistics a model trained on ``T x T`` patches saw, on a whole frame, in one pass without tiles or seams.
+        Implies ``lean_inference()``: such forwards run on inference plans, cached under a key of their own.  ``0`` / ``None``
+        turns it off (``lean_inference`` stays as it is).  A forward under autograd, and ``TrainStep``, keep the ordinary training
+        plan with GLOBAL statistics: that is TLC's contract -- train global, test local.  Returns self."""
+        T = int(T or 0)
+        if T != 0 and not 8 <= T <= 16384:
+            raise M2TError(f"local_norm: the window side must be 0 (off) or 8 .. 16384, got {T}")
+        self.local_norm_window = T
+        if T:
+            self.lean_inference_enabled = True
+        return self
+
+    def _plan_for(self, x: torch.Tensor, inference: bool = False, local_norm: int = 0) -> Plan:
         if x.dim() != 4 or x.shape[1] != 3:
             raise M2TError("expected input of shape [B,3,H,W]")
         self._device_ok(x)
         B, _, H0, W0 = x.shape
         key = (B, H0, W0, self._dtype_code(), x.device.index)
-        if inference:
+        if local_norm:                   # an inference plan of its own kind: one per window side
+            inference = True
+            key = key + ("local_norm", int(local_norm))
+        elif inference:
             key = key + ("inference",)
         plan = self._plans.get(key)
         if plan is None:
             kind = {"inference": True} if inference else {}
+            if local_norm:
+                kind["local_norm"] = int(local_norm)
             plan = Plan(B, H0, W0, self.scale, self.n_blocks, key[3], x.device, **kind)
             self._check_plan(plan)
             self._plans[key] = plan
@@ -532,7 +561,11 @@ class M2Trans(nn.Module):
             params = self._dp_params if self._dp_master is not None else [p for _, p in self._trainable()]
             if x.requires_grad or any(p.requires_grad for p in params):
                 return _M2TransFunction.apply(x, self, *params)
-        sr = self._run_forward(self._plan_for(x, inference=self.lean_inference_enabled), x, keep=False)
+        if self.local_norm_window:
+            plan = self._plan_for(x, inference=True, local_norm=self.local_norm_window)
+        else:
+            plan = self._plan_for(x, inference=self.lean_inference_enabled)
+        sr = self._run_forward(plan, x, keep=False)
         if self._dp_master is not None:
             self._dp_release()
         return sr

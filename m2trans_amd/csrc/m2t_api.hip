@@ -86,6 +86,7 @@ struct m2t_plan_handles {
   size_t zero_page, pack_descs, pack_blocks, packed, xin, norm_part, norm_s, vring, norm_part0, t1act, t1der, t2act, t2der, srpre,
       loss_part, gpre, g_t2pre, g_t1pre, gT, gA, gB, gxc, gn, gd, gd2, gdwin, gdwin2, head_cols, gqkv[2][4], win[2][4], relw[2][4],
       arena, red_descs;
+  size_t xn, lnsum, norm_id;                                                // option "local_norm": absent on every other plan
   long long head_w, head_b, tail0_w, tail0_b, tail3_w, tail3_b, wlast;      // parameters (wlast: the tail conv; tail3_*: x4 only)
   long long t0, t0T, t3, t3T;                                               // packs (t3 / t3T: x4 only)
 };
@@ -109,6 +110,9 @@ struct m2t_plan {
   // option "inference": m2t_forward alone, on a forward-only workspace.  lay.ws / the workspace offsets of hd are then those of
   // inference_layout(), rebuilt after every change of an option; the training layout m2t_plan_create built waits in train_ws / train_hd
   int inference = 0;
+  // option "local_norm" (inference plans only): T > 0 = every block normalises with the statistics of a T x T window around each pixel
+  // (k_local_norm.hip -> region "xn") and its unchanged consumers get xn with the identity record "norm_id" (mean 0, rstd 1)
+  int local_norm = 0;
   bool ws_initialised = false;         // m2t_plan_init_workspace has run: "inference" is frozen, and so is every option of an inference plan
   m2t_region train_ws;
   m2t_plan_handles train_hd;
@@ -319,6 +323,11 @@ static void inference_layout(m2t_plan* p) {
   hd.t1der = (p->dt == M2T_F32 && sc == 3) ? ws.add("t1der", BP * r0 * r0 * 64, es) : M2T_NO_REGION;
   hd.t2act = s.stores_t2 ? ws.add("t2act", BP * 16 * 64, es) : M2T_NO_REGION;
   hd.srpre = ws.add("srpre", (size_t)B * 3 * p->Hsp * p->Wsp, 4);
+  // local_norm: the normalised block input (one buffer for every block: a block's consumers are done with it before the next block's
+  // statistics run), the fp64 {sum x, sum x^2} pairs between its two passes, and the identity record [mean = 0 | rstd = 1], [B][64] each
+  hd.xn = p->local_norm > 0 ? ws.add("xn", BP * 64, es) : M2T_NO_REGION;
+  hd.lnsum = p->local_norm > 0 ? ws.add("lnsum", BP * 64 * 2, 8) : M2T_NO_REGION;
+  hd.norm_id = p->local_norm > 0 ? ws.add("norm_id", (size_t)B * 64 * 2, 4) : M2T_NO_REGION;
   ws.seal();
   hd.norm_s = hd.norm_part0 = hd.t2der = hd.loss_part = hd.gpre = hd.g_t2pre = hd.g_t1pre = hd.gT = hd.gA = hd.gB = hd.gxc = hd.gn =
       hd.gd = hd.gd2 = hd.gdwin = hd.gdwin2 = hd.head_cols = hd.arena = hd.red_descs = M2T_NO_REGION;
@@ -357,6 +366,7 @@ extern "C" int m2t_plan_create(m2t_plan** out, int B, int H0, int W0, int scale,
   m2t_layout& lay = p->lay;
   m2t_plan_handles& hd = p->hd;
   hd = m2t_plan_handles{};
+  hd.xn = hd.lnsum = hd.norm_id = M2T_NO_REGION;
   hd.X.resize(n_blocks + 1);
   hd.blk.assign(n_blocks, m2t_block_handles{});
   auto param = [&](const std::string& n, long long cnt) { lay.add_param(n, cnt); return lay.poff[n]; };
@@ -547,6 +557,7 @@ extern "C" long long m2t_plan_query(const m2t_plan* p, const char* key) {
     if (o == "fused_qkv_dgrad") return s.fused_dgrad;
     if (o == "debug_skip_side") return p->debug_skip_side;
     if (o == "inference") return p->inference;
+    if (o == "local_norm") return p->local_norm;
     return -1;
   }
   // which stored tensors the current options leave unwritten (tests read the workspace by name)
@@ -567,6 +578,13 @@ extern "C" int m2t_plan_init_workspace(m2t_plan* p, void* workspace, void* strea
   if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
   e = hipMemsetAsync(ws + p->hd.zero_page, 0, 256, (hipStream_t)stream);
   if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
+  std::vector<float> norm_id;                        // (alive until the synchronisation below)
+  if (p->hd.norm_id != M2T_NO_REGION) {
+    norm_id.assign((size_t)p->B * 64 * 2, 0.f);
+    std::fill(norm_id.begin() + (size_t)p->B * 64, norm_id.end(), 1.f);
+    e = hipMemcpyAsync(ws + p->hd.norm_id, norm_id.data(), norm_id.size() * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
+  }
   e = hipStreamSynchronize((hipStream_t)stream);   // the host table may be freed/moved afterwards
   if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
   p->have_acts = p->have_seed = false;
@@ -616,13 +634,23 @@ extern "C" int m2t_forward(m2t_plan* p, const float* params, const float* x, flo
   int stat_partials = 0;
   for (int b = 0; b < p->nb; ++b) {
     const m2t_block_handles& bh = hd.blk[b];
-    void* X = ws + hd.X[b];
+    void* const Xres = ws + hd.X[b];                          // the block input: the residual of the block's conv
+    void* X = Xres;                                           // ... and what the branches normalise
     float* mean = (float*)(ws + bh.mean);
     float* rstd = (float*)(ws + bh.rstd);
     void* xc = ws + bh.xc;
-    // statistics of the block input: left as per-segment partials by the previous block's conv (bf16, row-streaming), else two stages
-    if (stat_partials > 0) CK(launch_instnorm_finalize((const float*)(ws + hd.norm_part), mean, rstd, B, stat_partials, st));
-    else CK(launch_instnorm_stats(dt, X, mean, rstd, (float*)(ws + hd.norm_part), B, (int)p->P, st));
+    if (p->local_norm > 0) {
+      // local statistics + apply -> xn; the launches below are today's, on xn with the identity record: (xn - 0) * 1 is xn on every bit
+      CK(launch_local_norm(dt, Xres, ws + hd.lnsum, ws + hd.xn, B, H, W, p->local_norm, st));
+      X = ws + hd.xn;
+      mean = (float*)(ws + hd.norm_id);
+      rstd = mean + (size_t)B * 64;
+    } else if (stat_partials > 0) {
+      // statistics of the block input: left as per-segment partials by the previous block's conv (bf16, row-streaming), else two stages
+      CK(launch_instnorm_finalize((const float*)(ws + hd.norm_part), mean, rstd, B, stat_partials, st));
+    } else {
+      CK(launch_instnorm_stats(dt, X, mean, rstd, (float*)(ws + hd.norm_part), B, (int)p->P, st));
+    }
     for (int i = 0; i < 4; ++i) {
       const int C = BR_C[i], L = BR_L[i];
       const int h = H >> L, w = W >> L;
@@ -669,8 +697,9 @@ extern "C" int m2t_forward(m2t_plan* p, const float* params, const float* x, flo
     }
     // x = feed_forward(xc) + x (:164); the last block also folds in `res + x` (:70)
     { M2TProfScope ps(M2T_PROF_CONV3_FWD, st);
-      stat_partials = (b < p->nb - 1) ? conv3x3_c64_stat_partials(dt, B, H, W, sc.conv_variant) : 0;
-      CK(launch_conv3x3_c64(dt, xc, pk(bh.wf), params + bh.ffb, X, (b == p->nb - 1) ? ws + hd.X[0] : nullptr, ws + hd.X[b + 1], B, H, W, st,
+      // (local_norm: the next block takes no global statistics, so the conv leaves no partials)
+      stat_partials = (b < p->nb - 1 && p->local_norm == 0) ? conv3x3_c64_stat_partials(dt, B, H, W, sc.conv_variant) : 0;
+      CK(launch_conv3x3_c64(dt, xc, pk(bh.wf), params + bh.ffb, Xres, (b == p->nb - 1) ? ws + hd.X[0] : nullptr, ws + hd.X[b + 1], B, H, W, st,
                             pk(bh.wfR), ws + hd.zero_page, sc.conv_variant, stat_partials > 0 ? (float*)(ws + hd.norm_part) : nullptr)); }
   }
   void* Y = ws + hd.X[p->nb];
@@ -1480,10 +1509,22 @@ extern "C" int m2t_set_option(m2t_plan* p, const char* key, long long value) {
   if (k == "inference") {
     if (p->ws_initialised)
       return m2t_set_error(M2T_ERR_STATE, "m2t_set_option: \"inference\" makes or unmakes an inference plan only before the first m2t_plan_init_workspace");
+    if (value == 0 && p->local_norm > 0)
+      return m2t_set_error(M2T_ERR_STATE, "m2t_set_option: \"inference\" cannot be cleared while \"local_norm\" > 0 (local statistics exist on inference plans only: clear \"local_norm\" first)");
     const bool was = p->inference != 0;
     p->inference = value != 0;
     p->have_acts = p->have_seed = p->l1_deferred = false;
     resolve_layout(p, was);
+    return 0;
+  }
+  if (k == "local_norm") {
+    if (value != 0 && (value < 8 || value > 16384)) return m2t_set_error(M2T_ERR_ARG, "local_norm: 0 (off) or 8 .. 16384 (the window side T)");
+    if (p->ws_initialised)
+      return m2t_set_error(M2T_ERR_STATE, "m2t_set_option: \"local_norm\" decides the workspace layout: it is set only before the first m2t_plan_init_workspace");
+    if (!p->inference)
+      return m2t_set_error(M2T_ERR_STATE, "m2t_set_option: \"local_norm\" needs an inference plan: set \"inference\" to 1 first (the backward pass has no local statistics)");
+    p->local_norm = (int)value;
+    resolve_layout(p, false);
     return 0;
   }
   if (p->inference && p->ws_initialised)

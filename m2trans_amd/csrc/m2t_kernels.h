@@ -68,6 +68,9 @@ struct M2TProfScope {
   ~M2TProfScope() { m2t_prof_end(cat, st); }
 };
 
+// ---- k_local_norm.hip: local-window InstanceNorm statistics + apply (option "local_norm"): X (P64) -> Xn (P64), hs = B*H*W*64 fp64 pairs
+int launch_local_norm(int dt, const void* X, void* hs, void* Xn, int B, int H, int W, int T, hipStream_t st);
+
 // ---- k_pointwise.hip --------------------------------------------------------------------
 int launch_dwt(int dt, int L, const void* src, int lds_, int c0, void* dst, int ldd, int d0, int B, int H, int W,
                int C, bool inverse, hipStream_t st);

@@ -4,7 +4,7 @@ results table: the model runs on the eight flips and transposes of the input as 
 averaged) and the per-pixel spread of the eight outputs (test-time-augmentation uncertainty).
 
     python -m m2trans_amd.infer --config configs/M2Trans_x4_test.yml --model_path model.pt --input LR_DIR --output SR_DIR \\
-        [--self_ensemble] [--spread SPREAD_DIR] [--compute_dtype bf16|fp32] [--lean] [--tile T [--tile_overlap V] [--tile_batch N] [--seam SEAM_DIR]]
+        [--self_ensemble] [--spread SPREAD_DIR] [--compute_dtype bf16|fp32] [--lean] [--local_norm T] [--tile T [--tile_overlap V] [--tile_batch N] [--seam SEAM_DIR]]
 
 Tiled inference (include/m2t_tiles.h, k_tiles.hip; restated by tests/tiles_ref.py): the model runs on overlapping tiles of the
 training size, in batches, and the outputs are feather-blended; its InstanceNorms then see the statistics they were trained with, and
@@ -346,7 +346,7 @@ def _save_map(grey_of: torch.Tensor, path) -> float:
 
 def upscale_folder(model, in_dir, out_dir, self_ensemble: bool = False, spread_dir=None, rgb_range: float = 1.0,
                    device="cuda", tile=None, overlap: int = 16, tile_batch=None, seam_dir=None, back_project_iters: int = 0,
-                   back_project_beta: float = 1.0, lean: bool = False) -> list:
+                   back_project_beta: float = 1.0, lean: bool = False, local_norm=None) -> list:
     """Every image of `in_dir` through `model` into `out_dir` as `<name>.png`; returns the written names.  self_ensemble: through
     the eight views.  spread_dir (needs self_ensemble): the per-pixel maximum over RGB of the spread as an 8-bit grey PNG of the same
     name, scaled by the image's own maximum (grey 255 = that maximum); `spread.json` beside the files maps each name to that maximum,
@@ -355,7 +355,18 @@ def upscale_folder(model, in_dir, out_dir, self_ensemble: bool = False, spread_d
     like the spread, with `seam.json`.  back_project_iters > 0: every output goes through that many iterations of `back_project` (step
     `back_project_beta`) against its own input before it is written, and `consistency.json` beside the results holds, per image,
     the mean / max residual and the LR-PSNR before and after.  lean: the model runs on inference plans for the length of this call
-    (`M2Trans.lean_inference`: the same bits on a forward-only workspace); False leaves the model's own setting alone."""
+    (`M2Trans.lean_inference`: the same bits on a forward-only workspace); False leaves the model's own setting alone.  local_norm=T:
+    for the length of this call the model normalises with the statistics of a T x T window around every pixel (`M2Trans.local_norm`,
+    which implies lean); None leaves the model's own setting alone."""
+    if local_norm is not None:
+        was = (int(getattr(model, "local_norm_window", 0)), bool(getattr(model, "lean_inference_enabled", False)))
+        model.local_norm(local_norm)
+        try:
+            return upscale_folder(model, in_dir, out_dir, self_ensemble, spread_dir, rgb_range, device, tile, overlap, tile_batch, seam_dir,
+                                  back_project_iters, back_project_beta, lean=lean)
+        finally:
+            model.local_norm(was[0])
+            model.lean_inference(was[1])
     if lean:
         was = bool(getattr(model, "lean_inference_enabled", False))
         model.lean_inference(True)
@@ -439,6 +450,9 @@ def parse_args(argv=None):
     ap.add_argument("--compute_dtype", choices=("bf16", "fp32"), default=None, help="overrides the yaml's compute_dtype")
     ap.add_argument("--lean", action="store_true", help="run on inference plans: the same bits on a forward-only workspace (a fraction "
                     "of the training workspace; whole frames fit where they needed --tile before)")
+    ap.add_argument("--local_norm", type=int, default=None, metavar="T", help="normalise every pixel with the InstanceNorm statistics of the "
+                    "T x T window around it (8 .. 16384; the training LR patch size) instead of the whole frame's: one pass, no tiles "
+                    "(implies --lean)")
     ap.add_argument("--tile", type=int, default=None, metavar="T", help="run the model on overlapping T x T tiles (the training LR patch "
                     "size, a multiple of 32) and feather-blend the outputs")
     ap.add_argument("--tile_overlap", type=int, default=16, metavar="V", help="with --tile: LR pixels two neighbouring tiles share, 0 <= 2 V <= T")
@@ -460,6 +474,8 @@ def parse_args(argv=None):
             ap.error("--back_project_beta must lie inside (0, 2)")
     if args.spread is not None and not args.self_ensemble:
         ap.error("--spread needs --self_ensemble")
+    if args.local_norm is not None and not 8 <= args.local_norm <= 16384:
+        ap.error("--local_norm must lie in 8 .. 16384")
     if args.seam is not None and args.tile is None:
         ap.error("--seam needs --tile")
     if args.tile is not None:
@@ -506,8 +522,9 @@ def main(argv=None) -> int:
     outs = upscale_folder(model, args.input, args.output, self_ensemble=args.self_ensemble, spread_dir=args.spread,
                           rgb_range=float(getattr(ns, "rgb_range", 1.0)), tile=args.tile, overlap=args.tile_overlap,
                           tile_batch=args.tile_batch, seam_dir=args.seam, back_project_iters=args.back_project or 0,
-                          back_project_beta=args.back_project_beta or 1.0, lean=args.lean)
-    line = {"images": len(outs), "output": args.output, "self_ensemble": bool(args.self_ensemble), "spread": args.spread, "lean": bool(args.lean),
+                          back_project_beta=args.back_project_beta or 1.0, lean=args.lean, local_norm=args.local_norm)
+    line = {"images": len(outs), "output": args.output, "self_ensemble": bool(args.self_ensemble), "spread": args.spread, "lean": bool(args.lean or args.local_norm),
+            "local_norm": args.local_norm,
             "tile": args.tile, "tile_overlap": args.tile_overlap if args.tile is not None else None, "seam": args.seam}
     if args.back_project is not None:
         line.update({"back_project": args.back_project, "back_project_beta": args.back_project_beta,

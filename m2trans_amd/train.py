@@ -383,7 +383,7 @@ def _dump_yaml(obj, path):
 
 # ------------------------------------------------------------------------------------------------------------------------- CLI
 # the reference's yaml keys (configs/M2Trans_x*.yml) ...
-MODEL_KEYS = ("model", "scale", "rgb_range", "colors", "n_feats", "n_blocks", "compute_dtype", "lean_inference")
+MODEL_KEYS = ("model", "scale", "rgb_range", "colors", "n_feats", "n_blocks", "compute_dtype", "lean_inference", "local_norm")
 REFERENCE_KEYS = MODEL_KEYS + ("pretrain", "patch_size", "batch_size", "data_repeat", "data_augment", "data_add_noise", "cutout", "cutmix",
                                "epochs", "lr", "eta_min", "gamma", "log_every", "test_every", "log_path", "log_name", "lambda_l1",
                                "lambda_clip", "save_image", "data_path", "training_dataset", "eval_sets")
@@ -453,6 +453,10 @@ def resolve_config(cfg: dict, compute_dtype=None) -> dict:
     if "lean_inference" in model:            # validation forwards on inference plans (M2Trans.lean_inference); training plans stay cached
         if not isinstance(model["lean_inference"], bool):
             raise M2TError(f"lean_inference must be true or false, got {model['lean_inference']!r}")
+    if "local_norm" in model:                # ... with local-window InstanceNorm statistics (M2Trans.local_norm): train global, test local
+        T = model["local_norm"]
+        if isinstance(T, bool) or not isinstance(T, int) or not (T == 0 or 8 <= T <= 16384):
+            raise M2TError(f"local_norm must be 0 (off) or a window side of 8 .. 16384, got {T!r}")
     ts = {"lr": float(cfg["lr"]), "lambda_l1": float(cfg.get("lambda_l1", 1.0)), "lambda_clip": 0.0, "world_size": 1}
     ts.update({k: cfg[k] for k in TRAINSTEP_KEYS if k in cfg})
     if "track_grad_norm" in cfg:
