@@ -1,8 +1,8 @@
 """Teacher-forced stage gate of the backward pass: fp64 reference per stage, bf16 error budget, per-pixel-class comparator.
 
 Plain helper module (CPU only, no pytest hooks), shared by tests/test_bwd_stage_reference_cpu.py and tests/test_gpu_bwd_stages.py;
-the mirror image of the forward stage gate (tests/test_gpu_baseline_configs.py check_vs_oracle) and the model-level continuation of
-tests/attn_ref.py.
+the mirror image of the forward stage gate (tests/fwd_stage_ref.py with tests/test_gpu_fwd_stages.py; check_vs_oracle of
+tests/test_gpu_baseline_configs.py is its whole-tensor forerunner at the benchmark geometry) and the model-level continuation of tests/attn_ref.py.
 
 TAPS.  Gradient tensors that a synchronised m2t_backward_ex of a model with n_blocks <= 2 leaves in the workspace (read from the body
 loop and the head part of backward_impl in csrc/m2t_api.hip; tests/gpu_util.hip_backward_trace reads them back), under these names:

@@ -142,6 +142,8 @@ def hip_forward_trace(plan, scale, n_blocks, B, H, W):
     names the oracle's ``force`` / ``cap`` dicts use (H, W = padded LR size)."""
     t = {"X0": ws_nchw(plan, "X0", B, H, W, 64)}
     for b in range(n_blocks):
+        for nm in ("mean", "rstd"):                        # InstanceNorm statistics of the block input: [B, 64], fp32 in both compute types
+            t[f"b{b}.{nm}"] = plan.ws_tensor(f"b{b}.{nm}", dtype=torch.float32).view(B, 64).cpu().clone()
         for i in range(4):
             h, w = H >> BR_L[i], W >> BR_L[i]
             t[f"b{b}.d{i+1}"] = ws_nchw(plan, f"b{b}.d{i+1}", B, h, w, BR_C[i])

@@ -77,7 +77,9 @@ GRAD_OF_TOTAL = 1e-5     # ... or, for the near-cancelling sums (rel-pos tables,
 
 
 def check_vs_oracle(scale, lr, B, dtype, nb=8, verbose=True):
-    """leg (a).  Returns what leg (b) needs."""
+    """leg (a).  Returns what leg (b) needs.  The bf16 stage thresholds here are whole-tensor numbers at the square, unpadded benchmark
+    geometry; THE forward gate -- every stored activation against fp64 per pixel class, with a budget, at non-square, padded and tall
+    shapes -- is tests/test_gpu_fwd_stages.py with tests/fwd_stage_ref.py."""
     model, p = build_model(scale, nb, dtype)
     x = O.closed_form_image(B, 3, lr, lr)
     hr = O.closed_form_image(B, 3, lr * scale, lr * scale, phase=0.7)
