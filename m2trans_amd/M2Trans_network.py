@@ -48,12 +48,13 @@ class _Holder(nn.Module):
     """A parameter container that only exists to reproduce the reference's state_dict names."""
 
 
-class Plan:
+class Plan(_lib.Handle):
     """m2t_plan + its workspace (one per (B, H0, W0, dtype)).  ``inference=True``: an inference plan (option "inference" of
     include/m2t.h) -- m2t_forward alone, on a forward-only workspace; every entry that needs activations or a seed refuses it.
     ``options``: {key: value} for m2t_set_option, set before the workspace is sized and initialised (an initialised inference plan
     takes no option any more).  ``local_norm=T`` (8 .. 16384, inference plans only): option "local_norm", every block normalises each
     pixel with the statistics of the T x T window around it (the Test-time Local Converter; include/m2t.h has the definition)."""
+    family = "plan"
 
     def __init__(self, B: int, H0: int, W0: int, scale: int, n_blocks: int, dtype: int, device, inference: bool = False,
                  options=None, local_norm: int = 0):
@@ -81,12 +82,6 @@ class Plan:
             _lib.check(lib.m2t_plan_init_workspace(self.handle, _lib.ptr(self.workspace), _lib.stream_ptr()),
                        "m2t_plan_init_workspace")
 
-    def query(self, key: str) -> int:
-        v = _lib.load().m2t_plan_query(self.handle, key.encode())
-        if v < 0:
-            raise KeyError(key)
-        return int(v)
-
     def grad_buckets(self):
         """[(lo, hi)] float ranges of the flat gradient buffer in the order m2t_backward completes them."""
         n = self.query("grad_buckets")
@@ -100,14 +95,6 @@ class Plan:
         es = torch.empty((), dtype=dtype).element_size()
         t = self.workspace[off: off + n * es].view(dtype)
         return t.view(shape) if shape is not None else t
-
-    def __del__(self):
-        try:
-            if self.handle:
-                _lib.load().m2t_plan_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
 
 class _M2TransFunction(torch.autograd.Function):

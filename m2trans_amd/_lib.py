@@ -268,6 +268,33 @@ def check(rc: int, what: str = ""):
         raise M2TError(f"{what} failed with status {rc}: {msg.decode() if msg else ''}")
 
 
+class Handle:
+    """What every owner of a library handle of ``family`` (m2t_<family>_create: plan, swin, text, vgg) shares: ``query``, the
+    parameter inventory, and the destroy call when the owner goes.  The owner sets ``self.handle``."""
+    family = ""
+    handle = None
+
+    def query(self, key: str) -> int:
+        v = getattr(load(), f"m2t_{self.family}_query")(self.handle, key.encode())
+        if v < 0:
+            raise KeyError(key)
+        return int(v)
+
+    def inventory(self):
+        """(names in flat order, {name: (float offset, element count)}) of the flat parameter buffer, as the library lays it"""
+        name = getattr(load(), f"m2t_{self.family}_param_name")
+        names = [name(self.handle, i).decode() for i in range(self.query("num_param_tensors"))]
+        return names, {n: (self.query("param:" + n), self.query("numel:" + n)) for n in names}
+
+    def __del__(self):
+        try:
+            if self.handle:
+                getattr(load(), f"m2t_{self.family}_destroy")(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
 def ptr(t):
     """Device/host pointer of a torch tensor (or None)."""
     return None if t is None else C.c_void_p(t.data_ptr())

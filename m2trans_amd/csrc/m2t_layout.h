@@ -1,7 +1,7 @@
 // m2t_layout.h -- the layout table every plan of the C ABI holds (m2t_plan, m2t_swin, m2t_text): the flat parameter
 // inventory, the packed-weight region, the optional fp32 side region, named workspace regions, and the query keys that
-// read them.  Host code only.  Names are for m2t_*_create, m2t_*_query and the frozen encoders; the training step of
-// m2t_api.hip resolves them to plain offsets once, at m2t_plan_create.
+// read them.  Host code only.  Names are for m2t_*_create and m2t_*_query: every handle resolves them to plain offsets once, as
+// it registers them (m2t_plan_handles of m2t_api.hip, the tower handles of m2t_tower.h), and its passes look nothing up.
 #pragma once
 #include <cstdlib>
 #include <map>
@@ -9,8 +9,6 @@
 #include <vector>
 
 #define CK(call) do { int rc__ = (call); if (rc__) return rc__; } while (0)
-// a named workspace tensor of plan `p` inside the caller's buffer `workspace` (the frozen encoders look names up per call)
-#define WSP(name) (p->lay.ws.ptr(workspace, name))
 
 // named tensors of one device buffer, each aligned to 256 bytes
 struct m2t_region {
@@ -25,7 +23,6 @@ struct m2t_region {
   }
   void seal() { bytes = (bytes + 255) & ~(size_t)255; }
   void clear() { t.clear(); bytes = 0; }
-  char* ptr(void* base, const std::string& name) const { return (char*)base + t.at(name).off; }
 };
 
 struct m2t_layout {
@@ -39,16 +36,15 @@ struct m2t_layout {
   long long nfb = 0;
   m2t_region ws;
 
-  void add_param(const std::string& n, long long cnt) { pnames.push_back(n); poff[n] = nparams; pnum[n] = cnt; nparams += cnt; }
+  long long add_param(const std::string& n, long long cnt) { pnames.push_back(n); poff[n] = nparams; pnum[n] = cnt; nparams += cnt; return nparams - cnt; }
   long long add_pack(const std::string& n, long long cnt) {
     npacked = (npacked + 7) & ~7LL;
     pk[n] = npacked;
     npacked += cnt;
     return pk[n];
   }
-  void add_fb(const std::string& n, long long cnt) { fb[n] = nfb; nfb += cnt; }
+  long long add_fb(const std::string& n, long long cnt) { fb[n] = nfb; nfb += cnt; return nfb - cnt; }
   const char* param_name(int i) const { return (i < 0 || i >= (int)pnames.size()) ? nullptr : pnames[i].c_str(); }
-  char* packed_ptr(void* workspace, const std::string& n) const { return ws.ptr(workspace, "packed") + pk.at(n) * esz; }
 
   // the generic keys; `families` names the name-keyed families beyond param: / numel: this handle answers (anything else: -1)
   enum { Q_WS = 1, Q_WSN = 2, Q_PACKED = 4 };

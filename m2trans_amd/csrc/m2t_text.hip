@@ -11,7 +11,7 @@
 // small kernels here (embedding + LayerNorm, masked multi-head attention for short sequences, pooling + projection); the fp32
 // handle forms q | k | v in a fourth, with fp64 accumulation.
 #include "m2t_kernels.h"
-#include "m2t_layout.h"
+#include "m2t_tower.h"
 #include "../../include/m2t.h"
 #include "../../include/m2t_text.h"
 
@@ -170,9 +170,21 @@ __global__ void __launch_bounds__(512) text_head_kernel(const float* __restrict_
 }
 }  // namespace
 
+// ---- names resolved once, at m2t_text_create: parameter offsets in floats, workspace offsets in bytes ----
+struct text_layer {
+  m2t_tower_layer L;
+  long long ln1_w, ln1_b, ln2_w, ln2_b;      // attention.output.LayerNorm, output.LayerNorm
+};
+struct text_handles {
+  text_layer lyr[TX_LAYERS];
+  long long word, pos, type, eln_w, eln_b, head_w;
+  size_t packed, fbias, ids, mask, X, XM, Y, QKV, AO, MH, pooled;
+};
+
 struct m2t_text {
   int max_seqs, max_len, dt;
-  m2t_layout lay;
+  m2t_layout lay;                            // names -> offsets: read by m2t_text_query / m2t_text_param_name only
+  text_handles hd;
   const float* weights = nullptr;
 };
 
@@ -181,49 +193,42 @@ extern "C" int m2t_text_create(m2t_text** out, int max_seqs, int max_len, int dt
     return m2t_set_error(M2T_ERR_ARG, "m2t_text_create: bad argument (1 <= max_len <= 128)");
   m2t_text* p = new m2t_text();
   p->max_seqs = max_seqs; p->max_len = max_len; p->dt = dtype; p->lay.esz = (dtype == M2T_F32) ? 4 : 2;
+  m2t_layout& lay = p->lay;
+  text_handles& hd = p->hd;
   // parameter inventory: HF BertModel checkpoint names (transformers 4.24; `pooler.*` is not used by encode_text and is
   // not part of the buffer) + the MedCLIP text projection
-  p->lay.add_param("embeddings.word_embeddings.weight", (long long)TX_VOCAB * TX_H);
-  p->lay.add_param("embeddings.position_embeddings.weight", (long long)TX_POS * TX_H);
-  p->lay.add_param("embeddings.token_type_embeddings.weight", (long long)TX_TYPES * TX_H);
-  p->lay.add_param("embeddings.LayerNorm.weight", TX_H);
-  p->lay.add_param("embeddings.LayerNorm.bias", TX_H);
+  hd.word = lay.add_param("embeddings.word_embeddings.weight", (long long)TX_VOCAB * TX_H);
+  hd.pos = lay.add_param("embeddings.position_embeddings.weight", (long long)TX_POS * TX_H);
+  hd.type = lay.add_param("embeddings.token_type_embeddings.weight", (long long)TX_TYPES * TX_H);
+  hd.eln_w = lay.add_param("embeddings.LayerNorm.weight", TX_H);
+  hd.eln_b = lay.add_param("embeddings.LayerNorm.bias", TX_H);
   for (int l = 0; l < TX_LAYERS; ++l) {
     const std::string b = "encoder.layer." + std::to_string(l) + ".";
-    for (const char* nm : {"query", "key", "value"}) {
-      p->lay.add_param(b + "attention.self." + nm + ".weight", (long long)TX_H * TX_H);
-      p->lay.add_param(b + "attention.self." + nm + ".bias", TX_H);
-    }
-    p->lay.add_param(b + "attention.output.dense.weight", (long long)TX_H * TX_H);
-    p->lay.add_param(b + "attention.output.dense.bias", TX_H);
-    p->lay.add_param(b + "attention.output.LayerNorm.weight", TX_H);
-    p->lay.add_param(b + "attention.output.LayerNorm.bias", TX_H);
-    p->lay.add_param(b + "intermediate.dense.weight", (long long)TX_FF * TX_H);
-    p->lay.add_param(b + "intermediate.dense.bias", TX_FF);
-    p->lay.add_param(b + "output.dense.weight", (long long)TX_H * TX_FF);
-    p->lay.add_param(b + "output.dense.bias", TX_H);
-    p->lay.add_param(b + "output.LayerNorm.weight", TX_H);
-    p->lay.add_param(b + "output.LayerNorm.bias", TX_H);
-    p->lay.add_pack(b + "qkv", 3LL * TX_H * TX_H);
-    p->lay.add_pack(b + "o", (long long)TX_H * TX_H);
-    p->lay.add_pack(b + "fc1", (long long)TX_FF * TX_H);
-    p->lay.add_pack(b + "fc2", (long long)TX_H * TX_FF);
-    p->lay.add_fb(b + "qkv_bias", 3 * TX_H);
+    text_layer& ly = hd.lyr[l];
+    ly.L.C = TX_H; ly.L.FF = TX_FF;
+    tower_add_qkv(lay, b, ly.L);
+    tower_add_o(lay, b, ly.L);
+    ly.ln1_w = lay.add_param(b + "attention.output.LayerNorm.weight", TX_H);
+    ly.ln1_b = lay.add_param(b + "attention.output.LayerNorm.bias", TX_H);
+    tower_add_mlp(lay, b, ly.L);
+    ly.ln2_w = lay.add_param(b + "output.LayerNorm.weight", TX_H);
+    ly.ln2_b = lay.add_param(b + "output.LayerNorm.bias", TX_H);
+    tower_add_packs(lay, b, ly.L);
   }
-  p->lay.add_param("projection_head.weight", 512LL * TX_H);
-  const size_t rows = (size_t)max_seqs * max_len, es = p->lay.esz;
-  p->lay.ws.add("packed", (size_t)p->lay.npacked, es);
-  p->lay.ws.add("fbias", (size_t)p->lay.nfb, 4);
-  p->lay.ws.add("ids", rows, 4);
-  p->lay.ws.add("mask", rows, 4);
-  p->lay.ws.add("X", rows * TX_H, es);
-  p->lay.ws.add("XM", rows * TX_H, es);      // the attention-block LayerNorm of a layer (kept apart from X so every stage input survives)
-  p->lay.ws.add("Y", rows * TX_H, es);
-  p->lay.ws.add("QKV", rows * 3 * TX_H, es);
-  p->lay.ws.add("AO", rows * TX_H, es);
-  p->lay.ws.add("MH", rows * TX_FF, es);
-  p->lay.ws.add("pooled", (size_t)max_seqs * TX_H, 4);
-  p->lay.ws.seal();
+  hd.head_w = lay.add_param("projection_head.weight", 512LL * TX_H);
+  const size_t rows = (size_t)max_seqs * max_len, es = lay.esz;
+  hd.packed = lay.ws.add("packed", (size_t)lay.npacked, es);
+  hd.fbias = lay.ws.add("fbias", (size_t)lay.nfb, 4);
+  hd.ids = lay.ws.add("ids", rows, 4);
+  hd.mask = lay.ws.add("mask", rows, 4);
+  hd.X = lay.ws.add("X", rows * TX_H, es);
+  hd.XM = lay.ws.add("XM", rows * TX_H, es);      // the attention-block LayerNorm of a layer (kept apart from X so every stage input survives)
+  hd.Y = lay.ws.add("Y", rows * TX_H, es);
+  hd.QKV = lay.ws.add("QKV", rows * 3 * TX_H, es);
+  hd.AO = lay.ws.add("AO", rows * TX_H, es);
+  hd.MH = lay.ws.add("MH", rows * TX_FF, es);
+  hd.pooled = lay.ws.add("pooled", (size_t)max_seqs * TX_H, 4);
+  lay.ws.seal();
   *out = p;
   return 0;
 }
@@ -242,32 +247,11 @@ extern "C" const char* m2t_text_param_name(const m2t_text* p, int i) {
 // once per weight set: the frozen fp32 weights -> element type T, q | k | v fused into one [2304][768] matrix per layer
 extern "C" int m2t_text_load_weights(m2t_text* p, const float* weights, void* workspace, void* stream) {
   if (!p || !weights || !workspace) return m2t_set_error(M2T_ERR_ARG, "m2t_text_load_weights: null");
-  hipStream_t st = (hipStream_t)stream;
-  const int dt = p->dt;
   p->weights = weights;
-  float* fbias = (float*)WSP("fbias");
-  for (int l = 0; l < TX_LAYERS; ++l) {
-    const std::string b = "encoder.layer." + std::to_string(l) + ".";
-    int part = 0;
-    for (const char* nm : {"query", "key", "value"}) {
-      CK(launch_convert(dt, weights + p->lay.poff.at(b + "attention.self." + nm + ".weight"),
-                         p->lay.packed_ptr(workspace, b + "qkv") + (size_t)part * TX_H * TX_H * p->lay.esz, (long long)TX_H * TX_H, st));
-      CK(launch_convert(M2T_F32, weights + p->lay.poff.at(b + "attention.self." + nm + ".bias"), fbias + p->lay.fb.at(b + "qkv_bias") + part * TX_H, TX_H, st));
-      ++part;
-    }
-    CK(launch_convert(dt, weights + p->lay.poff.at(b + "attention.output.dense.weight"), p->lay.packed_ptr(workspace, b + "o"), (long long)TX_H * TX_H, st));
-    CK(launch_convert(dt, weights + p->lay.poff.at(b + "intermediate.dense.weight"), p->lay.packed_ptr(workspace, b + "fc1"), (long long)TX_FF * TX_H, st));
-    CK(launch_convert(dt, weights + p->lay.poff.at(b + "output.dense.weight"), p->lay.packed_ptr(workspace, b + "fc2"), (long long)TX_H * TX_FF, st));
-  }
+  for (int l = 0; l < TX_LAYERS; ++l)
+    CK(tower_pack_layer(p->dt, p->lay.esz, p->hd.lyr[l].L, weights, (char*)workspace + p->hd.packed, (float*)((char*)workspace + p->hd.fbias),
+                        (hipStream_t)stream));
   return 0;
-}
-
-static int text_gemm(int dt, int emode, const void* A, int K, const void* W, void* Y, int N, long long M, const float* bias,
-                     const void* aux, hipStream_t st) {
-  m2t_gemm_args ga{};
-  ga.A = A; ga.lda = K; ga.W = W; ga.Y = Y; ga.ldy = N; ga.bias = bias; ga.aux = aux; ga.ldaux = N;
-  ga.M = M; ga.N = N; ga.K = K; ga.H = 1; ga.Wd = 1; ga.r = 1; ga.C = 64;
-  return launch_gemm_nt(dt, M2T_A_PLAIN, emode, ga, st);
 }
 
 // medmodel.encode_text(input_ids, attention_mask) (losses.py:65,74): ids_host / mask_host int[n][len] in HOST memory
@@ -285,7 +269,9 @@ extern "C" int m2t_text_encode_ex(m2t_text* p, const int* ids_host, const int* m
   hipStream_t st = (hipStream_t)stream;
   const int dt = p->dt;
   const float* wt = p->weights;
-  const size_t hs_bytes = (size_t)rows * TX_H * p->lay.esz;
+  const text_handles& hd = p->hd;
+  const size_t es = p->lay.esz, hs_bytes = (size_t)rows * TX_H * es;
+  char* W = (char*)workspace;
 #define TX_KEEP_HIDDEN(i)                                                                                             \
   do {                                                                                                                \
     if (hidden_out) {                                                                                                 \
@@ -293,60 +279,51 @@ extern "C" int m2t_text_encode_ex(m2t_text* p, const int* ids_host, const int* m
       if (he != hipSuccess) return m2t_set_hip_error(he, __FILE__, __LINE__);                                         \
     }                                                                                                                 \
   } while (0)
-  hipError_t e = hipMemcpyAsync(WSP("ids"), ids_host, sizeof(int) * rows, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(WSP("mask"), mask_host, sizeof(int) * rows, hipMemcpyHostToDevice, st);
+  // a kernel templated on the element type T, at the handle's: the arguments may name T
+#define TX_LAUNCH(kern, grid, block, ...)                                                                             \
+  do {                                                                                                                \
+    if (dt == M2T_F32) { using T = float; hipLaunchKernelGGL(kern<T>, grid, block, 0, st, __VA_ARGS__); }             \
+    else { using T = bf16_t; hipLaunchKernelGGL(kern<T>, grid, block, 0, st, __VA_ARGS__); }                          \
+    M2T_LAUNCH_CHECK();                                                                                               \
+  } while (0)
+  hipError_t e = hipMemcpyAsync(W + hd.ids, ids_host, sizeof(int) * rows, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(W + hd.mask, mask_host, sizeof(int) * rows, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);       // the host arrays may be temporaries
   if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
-  void *X = WSP("X"), *XM = WSP("XM"), *Y = WSP("Y"), *QKV = WSP("QKV"), *AO = WSP("AO"), *MH = WSP("MH");
-  float* pooled = (float*)WSP("pooled");
-  const float* fbias = (const float*)WSP("fbias");
-  const int* ids = (const int*)WSP("ids");
-  const int* mask = (const int*)WSP("mask");
-#define TX_LAUNCH(kern, grid, block, ...)                                                                 \
-  do {                                                                                                    \
-    if (dt == M2T_F32) hipLaunchKernelGGL(kern<float>, grid, block, 0, st, __VA_ARGS__);                  \
-    else hipLaunchKernelGGL(kern<bf16_t>, grid, block, 0, st, __VA_ARGS__);                               \
-    M2T_LAUNCH_CHECK();                                                                                   \
-  } while (0)
-  if (dt == M2T_F32)
-    hipLaunchKernelGGL(text_embed_kernel<float>, dim3((rows + 3) / 4), dim3(256), 0, st, ids, wt + p->lay.poff.at("embeddings.word_embeddings.weight"),
-                       wt + p->lay.poff.at("embeddings.position_embeddings.weight"), wt + p->lay.poff.at("embeddings.token_type_embeddings.weight"),
-                       wt + p->lay.poff.at("embeddings.LayerNorm.weight"), wt + p->lay.poff.at("embeddings.LayerNorm.bias"), (float*)X, rows, len);
-  else
-    hipLaunchKernelGGL(text_embed_kernel<bf16_t>, dim3((rows + 3) / 4), dim3(256), 0, st, ids, wt + p->lay.poff.at("embeddings.word_embeddings.weight"),
-                       wt + p->lay.poff.at("embeddings.position_embeddings.weight"), wt + p->lay.poff.at("embeddings.token_type_embeddings.weight"),
-                       wt + p->lay.poff.at("embeddings.LayerNorm.weight"), wt + p->lay.poff.at("embeddings.LayerNorm.bias"), (bf16_t*)X, rows, len);
-  M2T_LAUNCH_CHECK();
+  void *X = W + hd.X, *XM = W + hd.XM, *Y = W + hd.Y, *QKV = W + hd.QKV, *AO = W + hd.AO, *MH = W + hd.MH;
+  float* pooled = (float*)(W + hd.pooled);
+  const float* fbias = (const float*)(W + hd.fbias);
+  const char* packed = W + hd.packed;
+  const int* ids = (const int*)(W + hd.ids);
+  const int* mask = (const int*)(W + hd.mask);
+  TX_LAUNCH(text_embed_kernel, dim3((rows + 3) / 4), dim3(256), ids, wt + hd.word, wt + hd.pos, wt + hd.type, wt + hd.eln_w, wt + hd.eln_b,
+            (T*)X, rows, len);
   TX_KEEP_HIDDEN(0);
   for (int l = 0; l < TX_LAYERS; ++l) {
-    const std::string b = "encoder.layer." + std::to_string(l) + ".";
+    const text_layer& ly = hd.lyr[l];
+    const m2t_tower_layer& L = ly.L;
     if (dt == M2T_F32) {      // the parity mode forms q | k | v with fp64 accumulation (see text_qkv_f64acc_kernel)
       static_assert((3 * TX_H) % 64 == 0 && TX_H % 16 == 0, "text_qkv_f64acc_kernel tiles");
       hipLaunchKernelGGL(text_qkv_f64acc_kernel, dim3(3 * TX_H / 64, (rows + 63) / 64), dim3(256), 0, st, (const float*)X,
-                         (const float*)p->lay.packed_ptr(workspace, b + "qkv"), fbias + p->lay.fb.at(b + "qkv_bias"), (float*)QKV, rows, 3 * TX_H, TX_H);
+                         (const float*)(packed + L.pk_qkv * es), fbias + L.fb_qkv, (float*)QKV, rows, 3 * TX_H, TX_H);
       M2T_LAUNCH_CHECK();
     } else {
-      CK(text_gemm(dt, M2T_E_BIAS, X, TX_H, p->lay.packed_ptr(workspace, b + "qkv"), QKV, 3 * TX_H, rows, fbias + p->lay.fb.at(b + "qkv_bias"), nullptr, st));
+      CK(tower_gemm(dt, M2T_E_BIAS, X, TX_H, packed + L.pk_qkv * es, QKV, 3 * TX_H, rows, fbias + L.fb_qkv, nullptr, st));
     }
-    if (dt == M2T_F32) hipLaunchKernelGGL(text_attn_kernel<float>, dim3(n * TX_HEADS), dim3(256), 0, st, (const float*)QKV, mask, (float*)AO, len);
-    else hipLaunchKernelGGL(text_attn_kernel<bf16_t>, dim3(n * TX_HEADS), dim3(256), 0, st, (const bf16_t*)QKV, mask, (bf16_t*)AO, len);
-    M2T_LAUNCH_CHECK();
+    TX_LAUNCH(text_attn_kernel, dim3(n * TX_HEADS), dim3(256), (const T*)QKV, mask, (T*)AO, len);
     // BertSelfOutput: LayerNorm(dense(attention) + hidden); BertOutput: LayerNorm(dense(gelu(dense(h))) + h)
-    CK(text_gemm(dt, M2T_E_BIAS_RESID, AO, TX_H, p->lay.packed_ptr(workspace, b + "o"), Y, TX_H, rows, wt + p->lay.poff.at(b + "attention.output.dense.bias"), X, st));
-    CK(launch_layernorm(dt, Y, wt + p->lay.poff.at(b + "attention.output.LayerNorm.weight"), wt + p->lay.poff.at(b + "attention.output.LayerNorm.bias"), XM, rows, TX_H, st, 1e-12f));
-    CK(text_gemm(dt, M2T_E_BIAS_GELU, XM, TX_H, p->lay.packed_ptr(workspace, b + "fc1"), MH, TX_FF, rows, wt + p->lay.poff.at(b + "intermediate.dense.bias"), nullptr, st));
-    CK(text_gemm(dt, M2T_E_BIAS_RESID, MH, TX_FF, p->lay.packed_ptr(workspace, b + "fc2"), Y, TX_H, rows, wt + p->lay.poff.at(b + "output.dense.bias"), XM, st));
-    CK(launch_layernorm(dt, Y, wt + p->lay.poff.at(b + "output.LayerNorm.weight"), wt + p->lay.poff.at(b + "output.LayerNorm.bias"), X, rows, TX_H, st, 1e-12f));
+    CK(tower_gemm(dt, M2T_E_BIAS_RESID, AO, TX_H, packed + L.pk_o * es, Y, TX_H, rows, wt + L.o_b, X, st));
+    CK(launch_layernorm(dt, Y, wt + ly.ln1_w, wt + ly.ln1_b, XM, rows, TX_H, st, 1e-12f));
+    CK(tower_gemm(dt, M2T_E_BIAS_GELU, XM, TX_H, packed + L.pk_fc1 * es, MH, TX_FF, rows, wt + L.fc1_b, nullptr, st));
+    CK(tower_gemm(dt, M2T_E_BIAS_RESID, MH, TX_FF, packed + L.pk_fc2 * es, Y, TX_H, rows, wt + L.fc2_b, XM, st));
+    CK(launch_layernorm(dt, Y, wt + ly.ln2_w, wt + ly.ln2_b, X, rows, TX_H, st, 1e-12f));
     // hidden_states[l + 1] = X: the package pools hidden states 1, 2 and -1
     TX_KEEP_HIDDEN(l + 1);
-    if (l == 0 || l == 1 || l == TX_LAYERS - 1) {
-      if (dt == M2T_F32) hipLaunchKernelGGL(text_pool_kernel<float>, dim3(n), dim3(256), 0, st, (const float*)X, pooled, len, l == 0 ? 0 : 1);
-      else hipLaunchKernelGGL(text_pool_kernel<bf16_t>, dim3(n), dim3(256), 0, st, (const bf16_t*)X, pooled, len, l == 0 ? 0 : 1);
-      M2T_LAUNCH_CHECK();
-    }
+    if (l == 0 || l == 1 || l == TX_LAYERS - 1) TX_LAUNCH(text_pool_kernel, dim3(n), dim3(256), (const T*)X, pooled, len, l == 0 ? 0 : 1);
   }
-  hipLaunchKernelGGL(text_head_kernel, dim3(n), dim3(512), 0, st, pooled, wt + p->lay.poff.at("projection_head.weight"), emb);
+  hipLaunchKernelGGL(text_head_kernel, dim3(n), dim3(512), 0, st, pooled, wt + hd.head_w, emb);
   M2T_LAUNCH_CHECK();
+#undef TX_LAUNCH
 #undef TX_KEEP_HIDDEN
   return 0;
 }

@@ -48,6 +48,7 @@ struct m2t_vgg {
   m2t_layout lay;
   const char* packed = nullptr;            // the caller's device buffer, set by load_weights
   size_t wf[NL] = {}, wb[NL] = {}, w0 = 0, bias[NL] = {}, packed_bytes = 0;     // byte offsets inside it
+  long long pw[NL] = {}, pb[NL] = {};      // each layer's weight and bias in the flat fp32 parameters (offsets in floats)
 };
 
 extern "C" int m2t_vgg_create(m2t_vgg** out, int dtype) {
@@ -59,8 +60,8 @@ extern "C" int m2t_vgg_create(m2t_vgg** out, int dtype) {
   auto add = [&off](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
   for (int l = 0; l < NL; ++l) {
     const std::string b = "features." + std::to_string(FEAT[l]) + ".";
-    v->lay.add_param(b + "weight", (long long)COUT[l] * CIN[l] * 9);
-    v->lay.add_param(b + "bias", COUT[l]);
+    v->pw[l] = v->lay.add_param(b + "weight", (long long)COUT[l] * CIN[l] * 9);
+    v->pb[l] = v->lay.add_param(b + "bias", COUT[l]);
     if (l == 0) {
       v->w0 = add(27 * 64 * 4);
     } else {
@@ -89,15 +90,14 @@ extern "C" int m2t_vgg_load_weights(m2t_vgg* v, const float* weights, void* pack
   hipStream_t st = (hipStream_t)stream;
   char* pk = (char*)packed;
   for (int l = 0; l < NL; ++l) {
-    const std::string b = "features." + std::to_string(FEAT[l]) + ".";
-    const float* w = weights + v->lay.poff.at(b + "weight");
+    const float* w = weights + v->pw[l];
     if (l == 0) {
       CK(launch_vgg_pack_first(w, (float*)(pk + v->w0), st));
     } else {
       CK(launch_vgg_pack(w, pk + v->wf[l], COUT[l], CIN[l], 0, st));
       CK(launch_vgg_pack(w, pk + v->wb[l], COUT[l], CIN[l], 1, st));
     }
-    CK(launch_convert(M2T_F32, weights + v->lay.poff.at(b + "bias"), pk + v->bias[l], COUT[l], st));
+    CK(launch_convert(M2T_F32, weights + v->pb[l], pk + v->bias[l], COUT[l], st));
   }
   v->packed = pk;
   return 0;

@@ -42,30 +42,45 @@ _V5_TO_V4 = (
 )
 
 
-class SwinEncoder:
-    """m2t_swin handle + workspace + flat weights."""
+class _Tower(_lib.Handle):
+    """A frozen tower behind ``m2t_<family>_*``: handle + parameter inventory + flat fp32 weights + workspace."""
+    what = ""          # the tower in the "missing ... weights" message
 
-    def __init__(self, max_images: int, dtype: int, device):
-        lib = _lib.load()
+    def __init__(self, dtype: int, device, *sizes: int):
         h = C.c_void_p()
-        _lib.check(lib.m2t_swin_create(C.byref(h), max_images, dtype), "m2t_swin_create")
-        self.handle, self.max_images, self.dtype, self.device = h, max_images, dtype, device
-        self.names: List[str] = []
-        self.slots: Dict[str, tuple] = {}
-        for i in range(self.query("num_param_tensors")):
-            n = lib.m2t_swin_param_name(h, i).decode()
-            self.names.append(n)
-            self.slots[n] = (self.query("param:" + n), self.query("numel:" + n))
+        _lib.check(getattr(_lib.load(), f"m2t_{self.family}_create")(C.byref(h), *sizes, dtype), f"m2t_{self.family}_create")
+        self.handle, self.dtype, self.device = h, dtype, device
+        self.names, self.slots = self.inventory()
         self.flat = torch.zeros(self.query("num_params"), dtype=torch.float32, device=device)
         self.workspace = torch.empty(self.query("workspace_bytes"), dtype=torch.uint8, device=device)
-        self.grad_workspace = None         # allocated on the first encode_grad (differentiable SemanticLoss only)
         self.loaded = False
 
-    def query(self, key: str) -> int:
-        v = _lib.load().m2t_swin_query(self.handle, key.encode())
-        if v < 0:
-            raise KeyError(key)
-        return int(v)
+    def _store(self, k: str, v: torch.Tensor, short_ok: bool = False):
+        """a state-dict tensor into its slot of ``flat`` (short_ok: one with fewer elements fills the front of the slot)"""
+        o, n = self.slots[k]
+        if v.numel() != n and not (short_ok and v.numel() < n):
+            raise M2TError(f"shape mismatch for {k}: {tuple(v.shape)}")
+        self.flat[o:o + v.numel()].copy_(v.reshape(-1).to(self.flat))
+
+    def _load_weights(self, seen):
+        """after the ``_store`` calls of a state dict: every tensor must have come, then the library packs them"""
+        missing = [n for n in self.names if n not in seen]
+        if missing:
+            raise M2TError(f"missing {self.what} weights: {missing[:5]} ... ({len(missing)})")
+        entry = f"m2t_{self.family}_load_weights"
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(_lib.load(), entry)(self.handle, _lib.ptr(self.flat), _lib.ptr(self.workspace), _lib.stream_ptr()), entry)
+        self.loaded = True
+
+
+class SwinEncoder(_Tower):
+    """m2t_swin handle + workspace + flat weights."""
+    family, what = "swin", "Swin"
+
+    def __init__(self, max_images: int, dtype: int, device):
+        super().__init__(dtype, device, max_images)
+        self.max_images = max_images
+        self.grad_workspace = None         # allocated on the first encode_grad (differentiable SemanticLoss only)
 
     def load(self, state: Dict[str, torch.Tensor]):
         seen = set()
@@ -76,18 +91,9 @@ class SwinEncoder:
                 if k.startswith(prefix) and k[len(prefix):] in self.slots:
                     k = k[len(prefix):]
             if k in self.slots:
-                o, n = self.slots[k]
-                if v.numel() != n:
-                    raise M2TError(f"shape mismatch for {k}: {tuple(v.shape)}")
-                self.flat[o:o + n].copy_(v.reshape(-1).to(self.flat))
+                self._store(k, v)
                 seen.add(k)
-        missing = [n for n in self.names if n not in seen]
-        if missing:
-            raise M2TError(f"missing Swin weights: {missing[:5]} ... ({len(missing)})")
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().m2t_swin_load_weights(self.handle, _lib.ptr(self.flat), _lib.ptr(self.workspace),
-                                                         _lib.stream_ptr()), "m2t_swin_load_weights")
-        self.loaded = True
+        self._load_weights(seen)
 
     DEPTHS = (2, 2, 6, 2)
 
@@ -216,39 +222,16 @@ class SwinEncoder:
                                                      _lib.ptr(self.grad_workspace), _lib.stream_ptr()), "m2t_swin_backward")
         return g
 
-    def __del__(self):
-        try:
-            if self.handle:
-                _lib.load().m2t_swin_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
-
-class TextEncoder:
+class TextEncoder(_Tower):
     """m2t_text handle + workspace + flat weights: ``medmodel.encode_text`` (losses.py:65,74) = BERT-base -> mean of hidden
     states 1, 2, -1 -> Linear(768, 512) -> unit norm, as hand-written kernels behind ``m2t_text_*`` (csrc/m2t_text.hip)."""
 
-    def __init__(self, max_seqs: int, max_len: int, dtype: int, device):
-        lib = _lib.load()
-        h = C.c_void_p()
-        _lib.check(lib.m2t_text_create(C.byref(h), max_seqs, max_len, dtype), "m2t_text_create")
-        self.handle, self.max_seqs, self.max_len, self.dtype, self.device = h, max_seqs, max_len, dtype, device
-        self.names: List[str] = []
-        self.slots: Dict[str, tuple] = {}
-        for i in range(self.query("num_param_tensors")):
-            n = lib.m2t_text_param_name(h, i).decode()
-            self.names.append(n)
-            self.slots[n] = (self.query("param:" + n), self.query("numel:" + n))
-        self.flat = torch.zeros(self.query("num_params"), dtype=torch.float32, device=device)
-        self.workspace = torch.empty(self.query("workspace_bytes"), dtype=torch.uint8, device=device)
-        self.loaded = False
+    family, what = "text", "text-tower"
 
-    def query(self, key: str) -> int:
-        v = _lib.load().m2t_text_query(self.handle, key.encode())
-        if v < 0:
-            raise KeyError(key)
-        return int(v)
+    def __init__(self, max_seqs: int, max_len: int, dtype: int, device):
+        super().__init__(dtype, device, max_seqs, max_len)
+        self.max_seqs, self.max_len = max_seqs, max_len
 
     def load(self, state: Dict[str, torch.Tensor]):
         """HF BertModel names (transformers 4.24), optionally behind the MedCLIP checkpoint's ``text_model.model.`` /
@@ -263,21 +246,9 @@ class TextEncoder:
                     break
             if k not in self.slots:
                 continue
-            o, n = self.slots[k]
-            if k == "embeddings.word_embeddings.weight" and v.dim() == 2 and v.shape[1] == 768 and v.numel() < n:
-                self.flat[o:o + v.numel()].copy_(v.reshape(-1).to(self.flat))
-            elif v.numel() != n:
-                raise M2TError(f"shape mismatch for {k}: {tuple(v.shape)}")
-            else:
-                self.flat[o:o + n].copy_(v.reshape(-1).to(self.flat))
+            self._store(k, v, short_ok=k == "embeddings.word_embeddings.weight" and v.dim() == 2 and v.shape[1] == 768)
             seen.add(k)
-        missing = [n for n in self.names if n not in seen]
-        if missing:
-            raise M2TError(f"missing text-tower weights: {missing[:5]} ... ({len(missing)})")
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().m2t_text_load_weights(self.handle, _lib.ptr(self.flat), _lib.ptr(self.workspace),
-                                                         _lib.stream_ptr()), "m2t_text_load_weights")
-        self.loaded = True
+        self._load_weights(seen)
 
     def encode(self, input_ids, attention_mask, hidden_states: bool = False):
         """input_ids, attention_mask: [n, len] integer arrays (host) -> [n,512] unit-norm embeddings on the device.
@@ -297,14 +268,6 @@ class TextEncoder:
                                                       _lib.stream_ptr(), _lib.ptr(hs) if hidden_states else None),
                        "m2t_text_encode")
         return (emb, hs) if hidden_states else emb
-
-    def __del__(self):
-        try:
-            if self.handle:
-                _lib.load().m2t_text_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
 
 def hash_text_feature(caption: str) -> torch.Tensor:
@@ -1011,11 +974,12 @@ def vgg_fold_state_dict(state: Dict[str, torch.Tensor]) -> Dict[str, torch.Tenso
 
 
 
-class PerceptualLoss(nn.Module):
+class PerceptualLoss(nn.Module, _lib.Handle):
     """The reference's ``PerceptualLoss(weights, resize, criterion)`` plus ``data_range``: ``sum_k weights[k] * crit(F_k(x), F_k(y))`` on
     VGG19's relu1_1, relu2_1, relu3_1, relu4_1, relu5_1 of ``((t / data_range) - mean) / std`` (one channel repeated to three; inputs
     not clamped), ``crit`` the mean L1 / smooth-L1 / L2.  ``resize=True`` takes both images to 224 x 224 first (bicubic,
     align_corners).  bf16 compute; differentiable with respect to ``x`` only.  Call ``load_vgg_state_dict`` first."""
+    family = "vgg"
 
     def __init__(self, weights=(1.0, 1.0, 1.0, 1.0, 1.0), resize: bool = False, criterion: str = "l1", data_range: float = 1.0, device=None):
         super().__init__()
@@ -1052,18 +1016,13 @@ class PerceptualLoss(nn.Module):
     def tap_weights(self):
         return (C.c_double * 5)(*self.weights)
 
-    def query(self, key: str) -> int:
-        return int(_lib.load().m2t_vgg_query(self.handle, key.encode()))
-
     def load_vgg_state_dict(self, sd: Dict[str, torch.Tensor]):
         folded = vgg_fold_state_dict(sd)
         if self.device.type != "cuda":
             raise M2TError("PerceptualLoss needs a HIP device (there is no host implementation)")
         lib = _lib.load()
         flat = torch.zeros(self.query("num_params"), dtype=torch.float32, device=self.device)
-        for i in range(self.query("num_param_tensors")):
-            n = lib.m2t_vgg_param_name(self.handle, i).decode()
-            o, cnt = self.query("param:" + n), self.query("numel:" + n)
+        for n, (o, cnt) in self.inventory()[1].items():
             if folded[n].numel() != cnt:
                 raise M2TError(f"load_vgg_state_dict: shape mismatch for {n}: {tuple(folded[n].shape)}")
             flat[o:o + cnt].copy_(folded[n].reshape(-1))
@@ -1121,11 +1080,3 @@ class PerceptualLoss(nn.Module):
     def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         self.check(x, y)
         return _EagerGradFn.apply(x, lambda want_grad: self._call(x, y, want_grad))
-
-    def __del__(self):
-        try:
-            if self.handle:
-                _lib.load().m2t_vgg_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass

@@ -432,3 +432,26 @@ def test_encoder_wrappers_are_the_plain_calls(params, encoders):
     g1 = enc.backward(g, 1)
     g2, taps = enc.backward(g, 1, taps=True)
     assert torch.equal(g1, g2) and taps["xf"].shape == (1, 49, 768) and taps["s0.out"].shape == (1, 3136, 96) and len(taps) == 29
+
+
+@pytest.mark.parametrize("dtype", ("fp32", "bf16"))
+def test_backward_after_a_relayout_of_the_grad_workspace(dtype, params):
+    """m2t_swin_grad_workspace_bytes(h, 2) between encode_grad(n_grad = 1) and backward(n_grad = 1) re-lays the cached region table;
+    backward lays it for its own n_grad again, so g_crops, emb and gws:gR are those of the undisturbed sequence, bit for bit"""
+    from m2trans_amd import _lib
+    from m2trans_amd.losses import SwinEncoder
+    lib = _lib.load()
+    enc = SwinEncoder(2, _lib.F32 if dtype == "fp32" else _lib.BF16, torch.device("cuda"))
+    enc.grad_workspace = torch.empty(int(lib.m2t_swin_grad_workspace_bytes(enc.handle, 2)), dtype=torch.uint8, device="cuda")
+    enc.load(params["closed"])
+    src = torch.rand(1, 3, 240, 256, generator=torch.Generator().manual_seed(5)).cuda()
+    crops, g_emb = [(0, 0, 0), (0, 16, 32)], torch.randn(1, 512, generator=torch.Generator().manual_seed(6)).cuda()
+    emb_a = enc.encode_grad(src, None, crops, 1)
+    g_a, gr_a = enc.backward(g_emb, 1), enc.query("gws:gR")
+    emb_b = enc.encode_grad(src, None, crops, 1)
+    assert lib.m2t_swin_grad_workspace_bytes(enc.handle, 2) == enc.grad_workspace.numel() and enc.query("gwsn:gR") == 2 * 3136 * 96
+    g_b = enc.backward(g_emb, 1)
+    assert enc.query("gws:gR") == gr_a and enc.query("gwsn:gR") == 3136 * 96
+    assert torch.isfinite(g_a).all() and float(g_a.abs().max()) > 0
+    assert torch.equal(emb_a.view(torch.int32), emb_b.view(torch.int32))
+    assert torch.equal(g_a.view(torch.int32), g_b.view(torch.int32))
