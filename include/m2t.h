@@ -153,7 +153,46 @@ long long m2t_plan_query(const m2t_plan* p, const char* key);
  *                           forward's launches in their order on xn with the identity record "ws:norm_id" (mean = 0 then rstd = 1, [B][64]
  *                           floats each); the 3 x 3 conv keeps the un-normalised X as its residual and emits no statistics partials.
  *                           The three regions answer -1 while the option is 0, and then every plan is laid out and launched as before.
- *                           The last block's input stays in place: "ws:X<n_blocks - 1>" */
+ *                           The last block's input stays in place: "ws:X<n_blocks - 1>"
+ *   "health"            [0] the STEP HEALTH RECORD of a training plan: 0 = off (the plan is laid out and launched as before: the same
+ *                           "workspace_bytes", the same launches, the same bits; "ws:health" answers -1), 1 = a record of the tensors
+ *                           m2t_forward stores, 2 = level 1 and the tensors m2t_backward / m2t_backward_ex leave.  Any other value is
+ *                           M2T_ERR_ARG.  Set only before the first m2t_plan_init_workspace (after it: M2T_ERR_STATE) and only on a
+ *                           training plan (on a plan whose "inference" is 1: M2T_ERR_STATE; setting "inference" to 1 while "health" > 0
+ *                           is M2T_ERR_STATE too); each refusal's text names its rule.  The workspace gains "ws:health", double
+ *                           [1 + rows][72], "ws:health_part" (the per-chunk partials) and two tables, all written by
+ *                           m2t_plan_init_workspace, which zeroes the record.  ROWS, fixed from the layout table and the options in
+ *                           force: "sr" (the caller's output, fp32 [B,3,Hs,Ws]; empty when sr == NULL); the regions the forward writes, in
+ *                           its order -- X0, then per block b<k>.mean, .rstd, .d1, .qkv1 .. .d4, .qkv4, .xc, X<k + 1>, then t1act, t1der,
+ *                           t2act, t2der, srpre; at level 2 the regions the backward leaves -- g_t2pre, g_t1pre, gT, gA, gB (g(X<k>) of
+ *                           the even / odd blocks k >= 1), gqkv0 .. gqkv3, gqkv0b .. gqkv3b (dq | dK | dV of the last even / odd block), gn,
+ *                           gxc (after block 0: the head's cotangent g(res)) -- and last "grads", the caller's flat gradient buffer
+ *                           (all of it behind an all-stages pass; empty behind a pass with a stage flag clear, which also leaves the
+ *                           regions it does not write as they were).  A tensor the options in force do not store has NO row: q | k | v
+ *                           of the recomputing attention paths, the GELU tensors of the fused tails, g_t1pre / g_t2pre of the fused tail
+ *                           backwards; clear that option to look inside.  On an initialised plan with "health" > 0 the options that
+ *                           decide what is stored ("fused_tail", "attn_bwd", "fused_attn_fwd", "fused_c16_fwd") are M2T_ERR_STATE.
+ *                           m2t_plan_query: "health_rows"; "health_row:<name>" = index or -1 (<name>: "sr", "grads" or a "ws:" name);
+ *                           "health_phase:<index>" = 0 forward / 1 backward; "health_name:<index>" = the length of the row's name,
+ *                           which it leaves where m2t_last_error_string() reads.
+ *                           ROW r = ws:health[1 + r][0 .. 71] over the region's stored elements (padding counts: it is stored data),
+ *                           each widened to fp32 exactly, then to fp64:
+ *                             [0] n   [1] non-finite elements (NaN, +-Inf)   [2] NaNs   [3] max |x| over finite elements (0: none)
+ *                             [4] sum and [5] sum of squares over finite elements   [6] exact zeros (+-0)
+ *                             [7] min |x| over finite non-zero elements (+Inf: none)
+ *                             [8 + k], k = 0 .. 63: exponent histogram -- bin 0 zeros; bins 1 .. 62 the finite non-zero elements with
+ *                             clamp(floor(log2 |x|), -41, 20) + 42, from the fp32 bit pattern (subnormals: bin 1); bin 63 non-finite
+ *                           HEADER ws:health[0]: [0] forward passes recorded, [1] backward passes recorded, [2] the first row, in row
+ *                           order, of the last recorded forward with [1] > 0, or -1, [3] the same for the last recorded backward among
+ *                           the backward rows, [4] rows, zeros beyond.  Counts, max, min and histogram are exact; the sums are fp64,
+ *                           folded in an order the element index alone fixes: chunks of 32768 elements, inside a chunk 256 lanes taking
+ *                           groups of 8 elements round-robin, the lanes by a halving tree, the chunks of a row in ascending order
+ *                           (csrc/m2t_health_tile.h).  Bit-reproducible, no atomics, no allocation, no host synchronisation; two
+ *                           launches behind the forward's last kernel, two on the main stream behind the backward's join of the side
+ *                           stream (both schedules); the kernels write the two regions only
+ *   "health_on"         [1] the run-time switch of the record: 0 = the passes skip its launches (the record and its pass counters
+ *                           stay as they are).  Any time on a training plan, no effect while "health" is 0; M2T_ERR_STATE on an
+ *                           inference plan, M2T_ERR_ARG beyond 0 / 1 */
 int m2t_set_option(m2t_plan* p, const char* key, long long value);
 /* Gradient buckets for communication overlap (replaces the reduce-to-GPU-0 of nn.DataParallel, train.py:73):
  * m2t_backward completes the flat gradient buffer in "grad_buckets" contiguous ranges, in this order: tail, block

@@ -180,6 +180,9 @@ class M2Trans(nn.Module):
     lean_inference_enabled = False
     # local_norm(T): those forwards use local-window InstanceNorm statistics (option "local_norm"); 0 = off.  A plain attribute as well
     local_norm_window = 0
+    # track_health(level): the training plans made from then on keep the step health record (option "health"); 0 = off
+    health_level = 0
+    _last_plan = None
 
     def __init__(self, args):
         super().__init__()
@@ -396,7 +399,7 @@ class M2Trans(nn.Module):
         return flags
 
     # ------------------------------------------------------------------ copy.deepcopy / pickle (torch.save(model))
-    _UNCOPIED = ("_dp_lock", "_dp_pool", "_plans", "_dp_master", "_dp_params", "_dp_release", "flat_params", "flat_grads")
+    _UNCOPIED = ("_dp_lock", "_dp_pool", "_plans", "_last_plan", "_dp_master", "_dp_params", "_dp_release", "flat_params", "flat_grads")
 
     def __getstate__(self):
         """A copy shares nothing that belongs to the device state of this module: no lock, no plans (a shared plan's C handle
@@ -493,6 +496,25 @@ class M2Trans(nn.Module):
             self.lean_inference_enabled = True
         return self
 
+    def track_health(self, level: int = 2) -> "M2Trans":
+        """The TRAINING plans made from now on keep the step health record (option "health" of include/m2t.h): per stored tensor
+        its element count, non-finite and NaN counts, max / min |x|, fp64 sum and sum of squares, zeros and a 64-bin exponent
+        histogram, written by two HIP launches behind the forward (``level`` 1) and two behind the backward (``level`` 2) without
+        a host synchronisation.  ``health()`` reads it.  Plans that exist already keep their layout (drop them with a new shape or
+        ``model._plans.clear()``); inference plans never carry a record.  0 turns it off.  Returns self."""
+        level = int(level or 0)
+        if level not in (0, 1, 2):
+            raise M2TError(f"track_health: the level is 0 (off), 1 (forward rows) or 2 (forward and backward rows), got {level}")
+        self.health_level = level
+        return self
+
+    def health(self):
+        """The ``HealthReport`` (m2trans_amd/health.py) of the plan this model used last.  Synchronises (one small copy)."""
+        from .health import HealthReport
+        if self._last_plan is None:
+            raise M2TError("M2Trans.health: no forward has run yet")
+        return HealthReport.from_plan(self._last_plan)
+
     def _plan_for(self, x: torch.Tensor, inference: bool = False, local_norm: int = 0) -> Plan:
         if x.dim() != 4 or x.shape[1] != 3:
             raise M2TError("expected input of shape [B,3,H,W]")
@@ -509,6 +531,8 @@ class M2Trans(nn.Module):
             kind = {"inference": True} if inference else {}
             if local_norm:
                 kind["local_norm"] = int(local_norm)
+            if not inference and self.health_level:
+                kind["options"] = {"health": self.health_level}
             plan = Plan(B, H0, W0, self.scale, self.n_blocks, key[3], x.device, **kind)
             self._check_plan(plan)
             self._plans[key] = plan
@@ -524,6 +548,7 @@ class M2Trans(nn.Module):
                 del self._plans[victim]
         else:
             self._plans.move_to_end(key)
+        self._last_plan = plan
         return plan
 
     def _run_forward(self, plan: Plan, x: torch.Tensor, keep: bool, want_sr: bool = True):

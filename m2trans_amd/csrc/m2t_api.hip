@@ -6,6 +6,7 @@
 #include <cstdio>
 #include "m2t_kernels.h"
 #include "m2t_layout.h"
+#include "m2t_health_tile.h"
 #include "../../include/m2t.h"
 #include "../../include/m2t_spectral.h"
 #include "../../include/m2t_msssim.h"
@@ -87,6 +88,7 @@ struct m2t_plan_handles {
       loss_part, gpre, g_t2pre, g_t1pre, gT, gA, gB, gxc, gn, gd, gd2, gdwin, gdwin2, head_cols, gqkv[2][4], win[2][4], relw[2][4],
       arena, red_descs;
   size_t xn, lnsum, norm_id;                                                // option "local_norm": absent on every other plan
+  size_t health, health_part, health_descs, health_work;                    // option "health": absent on every other plan
   long long head_w, head_b, tail0_w, tail0_b, tail3_w, tail3_b, wlast;      // parameters (wlast: the tail conv; tail3_*: x4 only)
   long long t0, t0T, t3, t3T;                                               // packs (t3 / t3T: x4 only)
 };
@@ -113,6 +115,15 @@ struct m2t_plan {
   // option "local_norm" (inference plans only): T > 0 = every block normalises with the statistics of a T x T window around each pixel
   // (k_local_norm.hip -> region "xn") and its unchanged consumers get xn with the identity record "norm_id" (mean 0, rstd 1)
   int local_norm = 0;
+  // option "health" (training plans only): 1 = a record of the tensors the forward stores, 2 = and of what the backward leaves
+  // (k_health.hip).  The rows are resolved by health_layout() from the layout table and the schedule in force; the passes use the
+  // descriptor table, the work list and the counts below and look nothing up
+  int health = 0, health_on = 1;
+  bool health_laid = false;            // lay.ws / hd carry the record's regions (resolve_layout takes them off again)
+  std::vector<std::string> health_names;       // row -> name ("sr", a "ws:" name, "grads")
+  std::vector<m2t_health_desc> health_descs;
+  std::vector<int> health_work;                // (row, chunk) pairs, forward rows first
+  int health_rows_fwd = 0, health_items_fwd = 0;
   bool ws_initialised = false;         // m2t_plan_init_workspace has run: "inference" is frozen, and so is every option of an inference plan
   m2t_region train_ws;
   m2t_plan_handles train_hd;
@@ -337,10 +348,84 @@ static void inference_layout(m2t_plan* p) {
   p->hd = hd;
 }
 
+// ---- the step health record (option "health"; k_health.hip) -------------------------------------------------------------------------
+// The rows, from the training layout's own table and the schedule in force, then the record's regions behind the training layout.  A
+// tensor the schedule does not store (q | k | v on the recomputing attention paths, the tail's GELU tensors on the fused tails) has no
+// row; neither has a scratch region a pass only partly writes (xin, the ring buffers, the slab arena).  Order: sr, the forward's regions
+// in the order m2t_forward writes them, then at level 2 the backward's in the order it writes them, then grads.
+static void health_layout(m2t_plan* p) {
+  const m2t_sched& s = p->sc;
+  const bool x4 = p->scale == 4;
+  p->health_names.clear(); p->health_descs.clear(); p->health_work.clear();
+  auto row = [&](const std::string& name, int phase, long long ext_n) {
+    m2t_health_desc d{};
+    d.phase = phase;
+    if (ext_n >= 0) { d.off = -1; d.n = ext_n; d.dtype = M2T_F32; }
+    else {
+      auto it = p->train_ws.t.find(name);
+      if (it == p->train_ws.t.end()) return;
+      const bool f32 = name == "srpre" || name.find(".mean") != std::string::npos || name.find(".rstd") != std::string::npos;
+      d.off = (long long)it->second.off; d.n = (long long)it->second.n; d.dtype = f32 ? M2T_F32 : p->dt;
+    }
+    d.item0 = (int)(p->health_work.size() / 2);
+    d.nitems = (int)std::max<long long>(1, ceil_divll(d.n, health_tile::CHUNK));
+    for (int c = 0; c < d.nitems; ++c) { p->health_work.push_back((int)p->health_descs.size()); p->health_work.push_back(c); }
+    p->health_names.push_back(name);
+    p->health_descs.push_back(d);
+  };
+  auto ws_row = [&](const std::string& name, int phase, bool stored = true) { if (stored) row(name, phase, -1); };
+  row("sr", 0, (long long)p->B * 3 * p->Hs * p->Ws);
+  ws_row("X0", 0);
+  for (int b = 0; b < p->nb; ++b) {
+    const std::string k = "b" + std::to_string(b) + ".";
+    ws_row(k + "mean", 0); ws_row(k + "rstd", 0);
+    for (int i = 0; i < 4; ++i) {
+      ws_row(k + "d" + std::to_string(i + 1), 0);
+      ws_row(k + "qkv" + std::to_string(i + 1), 0, i == 0 ? s.stores_qkv1 : (i == 1 ? s.stores_qkv2 : true));
+    }
+    ws_row(k + "xc", 0);
+    ws_row("X" + std::to_string(b + 1), 0);
+  }
+  ws_row("t1act", 0, s.stores_t1); ws_row("t1der", 0, s.stores_t1);
+  ws_row("t2act", 0, s.stores_t2); ws_row("t2der", 0, s.stores_t2);
+  ws_row("srpre", 0);
+  p->health_rows_fwd = (int)p->health_descs.size();
+  p->health_items_fwd = (int)(p->health_work.size() / 2);
+  if (p->health >= 2) {
+    ws_row("g_t2pre", 1, x4 && s.tail_bwd == TAIL_BWD_PLAIN);
+    ws_row("g_t1pre", 1, s.tail_bwd != TAIL_BWD_X23_STREAM);
+    ws_row("gT", 1);
+    ws_row("gA", 1, p->nb >= 3); ws_row("gB", 1, p->nb >= 2);      // g(X<b>) of the even / odd blocks b >= 1
+    for (int set = 0; set < 2; ++set)                               // dq | dK | dV of the last block that used the buffer set
+      for (int i = 0; i < 4; ++i) ws_row("gqkv" + std::to_string(i) + (set ? "b" : ""), 1, set == 0 || p->nb >= 2);
+    ws_row("gn", 1);
+    ws_row("gxc", 1);                                               // after block 0: g(res), the head's cotangent
+    row("grads", 1, p->lay.nparams);
+  }
+  m2t_region& ws = p->lay.ws;                                       // (the training layout: resolve_layout put it back)
+  m2t_plan_handles& hd = p->hd;
+  const size_t rows = p->health_descs.size(), items = p->health_work.size() / 2;
+  hd.health_descs = ws.add("health_descs", rows * sizeof(m2t_health_desc), 1);
+  hd.health_work = ws.add("health_work", items * 2 * sizeof(int), 1);
+  hd.health = ws.add("health", (1 + rows) * health_tile::SLOTS, 8);
+  hd.health_part = ws.add("health_part", items * health_tile::SLOTS, 8);
+  ws.seal();
+  p->health_laid = true;
+}
+static int health_record(m2t_plan* p, int phase, const void* ext, char* ws, hipStream_t st) {
+  const m2t_plan_handles& hd = p->hd;
+  const int row0 = phase ? p->health_rows_fwd : 0, item0 = phase ? p->health_items_fwd : 0;
+  const int nrows = phase ? (int)p->health_descs.size() - row0 : p->health_rows_fwd;
+  const int nitems = phase ? (int)(p->health_work.size() / 2) - item0 : p->health_items_fwd;
+  return launch_health_record(ws, ext, (const m2t_health_desc*)(ws + hd.health_descs), (const int*)(ws + hd.health_work),
+                              (double*)(ws + hd.health_part), (double*)(ws + hd.health), phase, row0, nrows, item0, nitems, st);
+}
+
 // the layout that goes with p->inference and the schedule in force (resolve_schedule first)
 static void resolve_layout(m2t_plan* p, bool was_inference) {
   if (p->inference) inference_layout(p);
-  else if (was_inference) { p->lay.ws = p->train_ws; p->hd = p->train_hd; }
+  else if (was_inference || p->health_laid) { p->lay.ws = p->train_ws; p->hd = p->train_hd; p->health_laid = false; }
+  if (!p->inference && p->health > 0) health_layout(p);
 }
 static int refuse_inference(const m2t_plan* p, const char* who) {
   if (!p->inference) return 0;
@@ -367,6 +452,7 @@ extern "C" int m2t_plan_create(m2t_plan** out, int B, int H0, int W0, int scale,
   m2t_plan_handles& hd = p->hd;
   hd = m2t_plan_handles{};
   hd.xn = hd.lnsum = hd.norm_id = M2T_NO_REGION;
+  hd.health = hd.health_part = hd.health_descs = hd.health_work = M2T_NO_REGION;
   hd.X.resize(n_blocks + 1);
   hd.blk.assign(n_blocks, m2t_block_handles{});
   auto param = [&](const std::string& n, long long cnt) { lay.add_param(n, cnt); return lay.poff[n]; };
@@ -558,6 +644,28 @@ extern "C" long long m2t_plan_query(const m2t_plan* p, const char* key) {
     if (o == "debug_skip_side") return p->debug_skip_side;
     if (o == "inference") return p->inference;
     if (o == "local_norm") return p->local_norm;
+    if (o == "health") return p->health;
+    if (o == "health_on") return p->health > 0 && p->health_on;
+    return -1;
+  }
+  // the health record's rows (option "health"): names are resolved here, never by a pass
+  if (k.rfind("health_", 0) == 0) {
+    const long long rows = p->health > 0 ? (long long)p->health_descs.size() : 0;
+    if (k == "health_rows") return rows;
+    if (k.rfind("health_row:", 0) == 0) {
+      const std::string name = k.substr(11);
+      for (long long r = 0; r < rows; ++r) if (p->health_names[r] == name) return r;
+      return -1;
+    }
+    if (k.rfind("health_phase:", 0) == 0 || k.rfind("health_name:", 0) == 0) {
+      const char* arg = k.c_str() + k.find(':') + 1;
+      char* end = nullptr;
+      const long long r = strtoll(arg, &end, 10);
+      if (end == arg || *end || r < 0 || r >= rows) return -1;
+      if (k[7] == 'p') return p->health_descs[r].phase;
+      g_err = p->health_names[r];                  // "health_name:<index>": the name goes where m2t_last_error_string() reads
+      return (long long)p->health_names[r].size();
+    }
     return -1;
   }
   // which stored tensors the current options leave unwritten (tests read the workspace by name)
@@ -583,6 +691,22 @@ extern "C" int m2t_plan_init_workspace(m2t_plan* p, void* workspace, void* strea
     norm_id.assign((size_t)p->B * 64 * 2, 0.f);
     std::fill(norm_id.begin() + (size_t)p->B * 64, norm_id.end(), 1.f);
     e = hipMemcpyAsync(ws + p->hd.norm_id, norm_id.data(), norm_id.size() * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
+  }
+  std::vector<double> health_head;                   // (alive until the synchronisation below)
+  if (p->health > 0 && p->hd.health != M2T_NO_REGION) {
+    // the record: descriptor table and work list next to the other tables, every row zero, the header row "nothing recorded"
+    const size_t rows = p->health_descs.size();
+    e = hipMemcpyAsync(ws + p->hd.health_descs, p->health_descs.data(), rows * sizeof(m2t_health_desc), hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
+    e = hipMemcpyAsync(ws + p->hd.health_work, p->health_work.data(), p->health_work.size() * sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
+    e = hipMemsetAsync(ws + p->hd.health, 0, (1 + rows) * health_tile::SLOTS * sizeof(double), (hipStream_t)stream);
+    if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
+    health_head.assign(health_tile::SLOTS, 0.0);
+    health_head[2] = health_head[3] = -1.0;
+    health_head[4] = (double)rows;
+    e = hipMemcpyAsync(ws + p->hd.health, health_head.data(), health_head.size() * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)stream);
     if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
   }
   e = hipStreamSynchronize((hipStream_t)stream);   // the host table may be freed/moved afterwards
@@ -728,6 +852,7 @@ extern "C" int m2t_forward(m2t_plan* p, const float* params, const float* x, flo
     }
   }
   if (sr) CK(launch_clamp_l1(srpre, nullptr, sr, nullptr, nullptr, nullptr, B, p->Hsp, p->Wsp, p->Hs, p->Ws, rgb_range, 0.f, 0.f, st));
+  if (p->health > 0 && p->health_on) CK(health_record(p, 0, sr, ws, st));      // the forward rows, behind the last kernel
   p->have_acts = !p->inference;      // an inference forward leaves neither activations nor a seed
   p->have_seed = false;
   p->l1_deferred = false;
@@ -1048,6 +1173,11 @@ static int backward_impl(m2t_plan* p, const float* params, const float* x, float
     return e;
   };
   auto main_wait = [&](hipEvent_t e) { if (e) (void)hipStreamWaitEvent(st, e, 0); };
+  // option "health" = 2: the backward rows, on the main stream behind the join of the side stream (both schedules end in it)
+  auto health_backward = [&]() -> int {
+    if (p->health < 2 || !p->health_on) return 0;
+    return health_record(p, 1, full ? grads : nullptr, (char*)workspace, st);
+  };
 
   const int dt = p->dt, B = p->B, H = p->H, W = p->W, s = p->scale;
   const long long BP = (long long)B * p->P;
@@ -1438,6 +1568,7 @@ static int backward_impl(m2t_plan* p, const float* params, const float* x, float
     }
     for (auto e : p->bucket_events) (void)hipEventRecord(e, sd);
     main_wait(side_marker());
+    CK(health_backward());         // (a partial pass: no grads row; a region it did not write keeps what it held)
     p->have_seed = false;
     p->l1_deferred = false;
     return 0;
@@ -1466,6 +1597,7 @@ static int backward_impl(m2t_plan* p, const float* params, const float* x, float
     for (auto e : p->bucket_events) (void)hipEventRecord(e, sd);
   if (bucket_i != p->buckets.size()) return m2t_set_error(M2T_ERR_STATE, "m2t_backward: gradient bucket table out of step");
   if (!(tail_on_main && !first_backward)) main_wait(side_marker());          // join: every gradient is complete in main-stream order
+  CK(health_backward());
   p->have_seed = false;
   p->l1_deferred = false;
   return 0;
@@ -1511,6 +1643,8 @@ extern "C" int m2t_set_option(m2t_plan* p, const char* key, long long value) {
       return m2t_set_error(M2T_ERR_STATE, "m2t_set_option: \"inference\" makes or unmakes an inference plan only before the first m2t_plan_init_workspace");
     if (value == 0 && p->local_norm > 0)
       return m2t_set_error(M2T_ERR_STATE, "m2t_set_option: \"inference\" cannot be cleared while \"local_norm\" > 0 (local statistics exist on inference plans only: clear \"local_norm\" first)");
+    if (value != 0 && p->health > 0)
+      return m2t_set_error(M2T_ERR_STATE, "m2t_set_option: \"inference\" cannot be set while \"health\" > 0 (the health record exists on training plans only: clear \"health\" first)");
     const bool was = p->inference != 0;
     p->inference = value != 0;
     p->have_acts = p->have_seed = p->l1_deferred = false;
@@ -1527,6 +1661,25 @@ extern "C" int m2t_set_option(m2t_plan* p, const char* key, long long value) {
     resolve_layout(p, false);
     return 0;
   }
+  if (k == "health") {
+    if (value < 0 || value > 2) return m2t_set_error(M2T_ERR_ARG, "health: 0 (off), 1 (the forward's tensors) or 2 (and what the backward leaves)");
+    if (p->ws_initialised)
+      return m2t_set_error(M2T_ERR_STATE, "m2t_set_option: \"health\" decides the workspace layout: it is set only before the first m2t_plan_init_workspace");
+    if (p->inference)
+      return m2t_set_error(M2T_ERR_STATE, "m2t_set_option: \"health\" needs a training plan: this is an inference plan (option \"inference\"), which stores no stage");
+    p->health = (int)value;
+    resolve_layout(p, false);
+    return 0;
+  }
+  if (k == "health_on") {
+    if (value < 0 || value > 1) return m2t_set_error(M2T_ERR_ARG, "health_on: 0 / 1");
+    if (p->inference)
+      return m2t_set_error(M2T_ERR_STATE, "m2t_set_option: \"health_on\" switches the health record of a training plan: this is an inference plan (option \"inference\")");
+    p->health_on = (int)value;
+    return 0;
+  }
+  if (p->health > 0 && p->ws_initialised && (k == "fused_tail" || k == "attn_bwd" || k == "fused_attn_fwd" || k == "fused_c16_fwd"))
+    return m2t_set_error(M2T_ERR_STATE, "m2t_set_option: this option decides which tensors are stored, and the rows of the health record (option \"health\") are fixed by m2t_plan_init_workspace: set it before");
   if (p->inference && p->ws_initialised)
     return m2t_set_error(M2T_ERR_STATE, "m2t_set_option: the layout of an initialised inference plan is frozen (set options before m2t_plan_init_workspace)");
   p->red_uploaded = false;     // the deferred-reduction table depends on the schedule: rebuild it on the next backward

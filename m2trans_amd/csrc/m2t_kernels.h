@@ -71,6 +71,15 @@ struct M2TProfScope {
 // ---- k_local_norm.hip: local-window InstanceNorm statistics + apply (option "local_norm"): X (P64) -> Xn (P64), hs = B*H*W*64 fp64 pairs
 int launch_local_norm(int dt, const void* X, void* hs, void* Xn, int B, int H, int W, int T, hipStream_t st);
 
+// ---- k_health.hip: the step health record (option "health"): per (row, chunk) partials, then one fold per row and the header row
+struct m2t_health_desc {   // one row: a workspace tensor, or (off < 0) the buffer the pass got from its caller (sr, grads)
+  long long off, n;        // byte offset in the workspace, element count
+  int dtype, phase;        // m2t_dtype of the stored elements; 0 = written by the forward, 1 = left by the backward
+  int item0, nitems;       // the row's chunks in the work list (and in "health_part")
+};
+int launch_health_record(const void* ws, const void* ext, const m2t_health_desc* descs, const int* work, double* parts, double* rec,
+                         int phase, int row0, int nrows, int item0, int nitems, hipStream_t st);
+
 // ---- k_pointwise.hip --------------------------------------------------------------------
 int launch_dwt(int dt, int L, const void* src, int lds_, int c0, void* dst, int ldd, int d0, int B, int H, int W,
                int C, bool inverse, hipStream_t st);

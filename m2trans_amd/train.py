@@ -309,6 +309,9 @@ def fit(model, train_step, train_set, valid_sets, *, epochs, batch_size, lr0, et
             log("Epoch:{}, {}/{}, loss: {:.4f}, L1loss: {:.4f}, CLIPloss: {:.8f} time: {:.3f}".format(
                 str(epoch).zfill(epoch_width), str((it + 1) * batch_size).zfill(fill_width), total_steps, means["loss"],
                 means["pixel"], means["clip"], duration))
+            # track_health: K: the stage where a NaN / Inf first appeared in the last recorded step, else its three largest ranges
+            if getattr(train_step, "track_health", 0) and getattr(train_step, "_last_plan", None) is not None:
+                log(train_step.health().log_line())
             if on_log is not None:
                 on_log({"epoch": epoch, "iter": it, "means": means, "record": rec, "meter": meter})
 
@@ -391,7 +394,7 @@ IGNORED_KEYS = ("gpu_ids", "threads", "num_heads")
 # ... and the project's own, each handed to TrainStep unchanged (TrainStep validates them)
 TRAINSTEP_KEYS = ("pixel_loss", "pixel_loss_param", "lambda_ssim", "lambda_msssim", "lambda_fft", "fft_norm", "lambda_vif", "lambda_gmsd", "lambda_wavelet",
                   "wavelet", "wavelet_levels", "wavelet_band_weights", "wavelet_eps", "lambda_consistency", "consistency_eps", "accum_steps",
-                  "max_grad_norm", "weight_decay", "decoupled_weight_decay", "ema_decay", "skip_nonfinite", "param_groups")
+                  "max_grad_norm", "weight_decay", "decoupled_weight_decay", "ema_decay", "skip_nonfinite", "param_groups", "track_health")
 LOOP_KEYS = ("train_hr_path", "eval_folders", "preview_every", "validate_ema", "seed", "ring_rows", "track_grad_norm")
 DATA_KEYS = ("degradation",)            # a mapping of degrade.Degradation's arguments: LR synthesis beyond bicubic
 CLI_KEYS = ("config", "resume")         # the command line's own arguments, which config.yml records as the reference's does
@@ -459,6 +462,10 @@ def resolve_config(cfg: dict, compute_dtype=None) -> dict:
             raise M2TError(f"local_norm must be 0 (off) or a window side of 8 .. 16384, got {T!r}")
     ts = {"lr": float(cfg["lr"]), "lambda_l1": float(cfg.get("lambda_l1", 1.0)), "lambda_clip": 0.0, "world_size": 1}
     ts.update({k: cfg[k] for k in TRAINSTEP_KEYS if k in cfg})
+    if "track_health" in ts:                 # the step health record every K-th step (TrainStep(track_health=K)); 0 = off
+        K = ts["track_health"]
+        if isinstance(K, bool) or not isinstance(K, int) or K < 0:
+            raise M2TError(f"track_health must be an integer >= 0 (record every K-th step; 0 = off), got {K!r}")
     if "track_grad_norm" in cfg:
         ts["track_grad_norm"] = bool(cfg["track_grad_norm"])
     fit_kw = {"epochs": int(cfg["epochs"]), "batch_size": int(cfg["batch_size"]), "lr0": float(cfg["lr"]), "eta_min": float(cfg["eta_min"]),

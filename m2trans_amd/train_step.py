@@ -371,6 +371,7 @@ class TrainStep:
     perceptual_loss = None
     groups = None
     _need_stage = None
+    track_health = 0              # record the step health every K-th step (M2Trans.track_health); 0 = off
 
     def __init__(self, model: M2Trans, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  lambda_l1: float = 1.0, process_group=None, world_size: Optional[int] = None,
@@ -383,8 +384,17 @@ class TrainStep:
                  lambda_msssim: float = 0.0, lambda_vif: float = 0.0, param_groups=None, perceptual_loss=None,
                  lambda_perceptual: float = 0.0, lambda_gmsd: float = 0.0, lambda_wavelet: float = 0.0, wavelet="haar",
                  wavelet_levels: int = 2, wavelet_band_weights=None, wavelet_eps: float = 0.0, lambda_consistency: float = 0.0,
-                 consistency_eps: float = 0.0):
+                 consistency_eps: float = 0.0, track_health: int = 0):
         self.model = model
+        # the step health record (M2Trans.track_health, level 2) on the steps with step_count % track_health == 0; 0 = off: the
+        # plans are laid out and launched as before
+        if int(track_health) != track_health or int(track_health) < 0:
+            raise _lib.M2TError(f"track_health must be an integer >= 0 (record every K-th step; 0 = off), got {track_health!r}")
+        self.track_health = int(track_health)
+        if self.track_health:
+            model.track_health(2)
+            for key in [k for k, pl in (model._plans or {}).items() if not pl.inference and pl.query("opt:health") != 2]:
+                del model._plans[key]               # (a training plan made before this object has no record: made again on first use)
         # parameter groups / frozen tensors (param_groups.py): resolved against the model's names here, on the host, fixed for the
         # life of this object.  None (the default): nothing is allocated and the step issues the calls it always issued
         self.groups = resolve_param_groups(model, param_groups)
@@ -766,6 +776,7 @@ class TrainStep:
         plan.gen += 1
         plan.trained = True              # (the plan LRU of the model keeps training plans while forward-only ones remain)
         self._last_plan = plan
+        self._health_switch(lib, plan)
         with torch.cuda.device(lr_img.device):
             st = _lib.stream_ptr()
             ws = _lib.ptr(plan.workspace)
@@ -799,6 +810,26 @@ class TrainStep:
         self.loss = self._total_loss(on, use_clip)
         return self.loss
 
+    def _health_switch(self, lib, plan):
+        """track_health = K: the record's launches run on the steps with step_count % K == 0 (with accum_steps, on the last
+        micro-batch of such a step); on every other pass option "health_on" is 0 and the pass adds no launch.  Host state only."""
+        if not self.track_health:
+            return
+        on = self.step_count % self.track_health == 0 and self.micro_count == self.accum_steps - 1
+        if getattr(plan, "health_on", True) != on:
+            _lib.check(lib.m2t_set_option(plan.handle, b"health_on", int(on)), "m2t_set_option(health_on)")
+            plan.health_on = on
+
+    def health(self):
+        """The ``HealthReport`` of the last recorded step (m2trans_amd/health.py): ``.first_nonfinite`` names the stage where a NaN
+        or Inf first appeared -- what to read after ``skipped_steps`` grows.  Synchronises."""
+        from .health import HealthReport
+        if not self.track_health:
+            raise _lib.M2TError("TrainStep.health: made with track_health = 0 (off)")
+        if self._last_plan is None:
+            raise _lib.M2TError("TrainStep.health: no step has run yet")
+        return HealthReport.from_plan(self._last_plan)
+
     def _accumulate_micro(self, lib, first: bool, st):
         """Close one micro-batch: count it and, from the second one of a cycle on, grads += micro_grads, l1_loss += micro_loss."""
         if self.accum_steps == 1:
@@ -828,6 +859,7 @@ class TrainStep:
         plan.gen += 1
         plan.trained = True
         self._last_plan = plan
+        self._health_switch(lib, plan)
         with torch.cuda.device(lr_img.device):
             st = _lib.stream_ptr()
             ws = _lib.ptr(plan.workspace)
