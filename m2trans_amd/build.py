@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libm2t.so")
 SOURCES = ["k_pointwise.hip", "k_gemm.hip", "k_conv.hip", "k_attn.hip", "k_attn_res.hip", "k_attn_c16.hip", "k_attn_fused.hip", "k_attn_fwd2.hip", "k_tail_bwd.hip", "k_tail_fwd.hip", "k_tail_stream.hip", "k_tail_bwd_stream.hip", "k_swin.hip", "k_swin_bwd.hip", "k_metrics.hip", "k_ssim_loss.hip", "k_msssim_loss.hip", "k_vif_loss.hip", "k_gmsd_loss.hip", "k_wavelet_loss.hip", "k_consistency.hip", "k_fft_loss.hip", "k_fsim.hip", "k_datas.hip", "k_resize.hip", "k_optim.hip", "k_vgg.hip", "m2t_vgg.hip", "m2t_api.hip", "m2t_prof.hip", "m2t_swin.hip", "m2t_rlutrans.hip", "k_rlutrans_bwd.hip", "m2t_text.hip", "k_infer.hip", "k_train.hip", "k_tiles.hip", "k_degrade.hip", "k_jpeg.hip", "k_local_norm.hip", "k_health.hip"]
-HEADERS = ["m2t_common.h", "m2t_kernels.h", "m2t_gemm_load.h", "m2t_haar.h", "m2t_window.h", "m2t_layout.h", "m2t_tower.h", "m2t_pixel_loss.h", "m2t_fft.h", "m2t_moment_tile.h", "m2t_ssim_tile.h", "m2t_vif_tile.h", "m2t_gmsd_tile.h", "m2t_wavelet_tile.h", "m2t_consistency_tile.h", "m2t_degrade_tile.h", "m2t_jpeg_tile.h", "m2t_rlutrans_layout.h", "m2t_instnorm.h", "m2t_local_norm_tile.h", "m2t_health_tile.h", os.path.join("..", "..", "include", "m2t.h"),
+HEADERS = ["m2t_common.h", "m2t_kernels.h", "m2t_gemm_load.h", "m2t_haar.h", "m2t_window.h", "m2t_layout.h", "m2t_plan_layout.h", "m2t_tower.h", "m2t_pixel_loss.h", "m2t_fft.h", "m2t_moment_tile.h", "m2t_ssim_tile.h", "m2t_vif_tile.h", "m2t_gmsd_tile.h", "m2t_wavelet_tile.h", "m2t_consistency_tile.h", "m2t_degrade_tile.h", "m2t_jpeg_tile.h", "m2t_rlutrans_layout.h", "m2t_instnorm.h", "m2t_local_norm_tile.h", "m2t_health_tile.h", os.path.join("..", "..", "include", "m2t.h"),
            os.path.join("..", "..", "include", "m2t_spectral.h"), os.path.join("..", "..", "include", "m2t_resize.h"),
            os.path.join("..", "..", "include", "m2t_msssim.h"), os.path.join("..", "..", "include", "m2t_vif.h"),
            os.path.join("..", "..", "include", "m2t_groups.h"), os.path.join("..", "..", "include", "m2t_perceptual.h"),

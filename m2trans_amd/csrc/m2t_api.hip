@@ -4,10 +4,7 @@
 // (models/M2Trans_network.py:58-76,132-164) and train.py:199-210.
 #include <cstring>
 #include <cstdio>
-#include "m2t_kernels.h"
-#include "m2t_layout.h"
-#include "m2t_health_tile.h"
-#include "../../include/m2t.h"
+#include "m2t_plan_layout.h"
 #include "../../include/m2t_spectral.h"
 #include "../../include/m2t_msssim.h"
 #include "../../include/m2t_vif.h"
@@ -39,68 +36,14 @@ int m2t_ensure_dynamic_lds(const void* kernel, int bytes) {
   return 0;
 }
 
-// ---- the resolved schedule ----------------------------------------------------------------------------------------------------
-// Which kernel runs where, derived in ONE place (resolve_schedule) from the raw option values m2t_set_option writes, the element
-// type, the scale and the shape.  m2t_forward, the backward pass and m2t_plan_query read these fields and never combine raw options
-// themselves: a new option is resolved here and nowhere else.  Per-pass conditions (stage masks, debug_skip_side, stream capture,
-// red_uploaded, l1_deferred) stay with the pass and combine with these fields.
-enum m2t_tail_fwd { TAIL_FWD_PLAIN, TAIL_FWD_TILE, TAIL_FWD_STREAM, TAIL_FWD_X23_STREAM };
-enum m2t_tail_bwd { TAIL_BWD_PLAIN, TAIL_BWD_STORED, TAIL_BWD_RC16, TAIL_BWD_RC32, TAIL_BWD_STREAM, TAIL_BWD_X23_STREAM };
-struct m2t_sched {
-  // forward attention (bf16 only)
-  bool c16_fused_fwd;      // C = 16: norm apply + qkv projection + attention + residual in one kernel (k_attn_c16.hip)
-  bool c16_recompute;      // ... and qkv1 is not stored: the wave-per-window backward recomputes it from d1
-  bool c64_fused_fwd;      // C >= 64: qkv projection + attention + epilogue in one kernel (k_attn_fused.hip)
-  bool prep_in_fwd;        // ... with branch_prep inside
-  bool c64_recompute;      // qkv2 (C = 64) is not stored: the resident backward recomputes it from d2
-  int fwd2;                // C = 256 with branch_prep inside: variant of the two-windows-per-CU kernels (k_attn_fwd2.hip), 0 = not used
-  // backward attention (bf16 only)
-  bool resident_bwd;       // whole-window-resident attention backward (k_attn_res.hip)
-  bool fused_dgrad;        // C >= 64: projection data gradient inside that kernel
-  bool c16_prep;           // C = 16: overlap-add + projection data gradient + branch_prep_bwd in one kernel
-  bool prep_in_bwd;        // branch 4's branch_prep_bwd inside branch 3's attention backward
-  bool norm_red_in_prep;   // first stage of the InstanceNorm backward reduction inside the C = 16 prep launch
-  // tail
-  m2t_tail_fwd tail_fwd;
-  m2t_tail_bwd tail_bwd;
-  bool l1_in_tail;         // a deferred L1 loss is taken inside the fused tail backward (else by m2t_l1_loss's kernel)
-  // feed-forward conv
-  bool conv_rows;          // bf16: the row-streaming LDS-DMA kernel
-  int conv_variant;        // the launchers' variant argument: 0 = row-streaming where the element type has it, 1 = tile
-  bool fused_conv_bwd;     // bf16: data + weight / bias gradient in one row-streaming pass
-  // weight packs of the C >= 64 qkv weights the forward must refresh: plain copies (unfused forward GEMM), transposes (unfused dgrad GEMM)
-  bool need_copy, need_tr;
-  // what the forward leaves in the workspace
-  bool stores_qkv1, stores_qkv2, stores_t1, stores_t2;
-  bool fork_on_kernel;     // fork events ride on the dispatch they follow (needs the side stream; not under stream capture)
-};
-
-// ---- names resolved once, at m2t_plan_create: workspace offsets in bytes, parameter offsets in floats, pack offsets in elements ----
-struct m2t_block_handles {
-  size_t mean, rstd, xc, d[4], qkv[4];
-  long long rel_h[4], rel_w[4], wqkv[4], ffw, ffb;                          // parameters
-  long long w[4], wT[4], wF[4], wTF[4], wf, wfT, wfR, wfTR;                 // packs (wF / wTF: C >= 64 only)
-};
-struct m2t_plan_handles {
-  std::vector<size_t> X;                                                    // nb + 1 feature maps: block b reads X[b], writes X[b + 1]
-  std::vector<m2t_block_handles> blk;
-  size_t zero_page, pack_descs, pack_blocks, packed, xin, norm_part, norm_s, vring, norm_part0, t1act, t1der, t2act, t2der, srpre,
-      loss_part, gpre, g_t2pre, g_t1pre, gT, gA, gB, gxc, gn, gd, gd2, gdwin, gdwin2, head_cols, gqkv[2][4], win[2][4], relw[2][4],
-      arena, red_descs;
-  size_t xn, lnsum, norm_id;                                                // option "local_norm": absent on every other plan
-  size_t health, health_part, health_descs, health_work;                    // option "health": absent on every other plan
-  long long head_w, head_b, tail0_w, tail0_b, tail3_w, tail3_b, wlast;      // parameters (wlast: the tail conv; tail3_*: x4 only)
-  long long t0, t0T, t3, t3T;                                               // packs (t3 / t3T: x4 only)
-};
-
-struct m2t_plan {
-  int B, H0, W0, H, W, scale, nb, dt;
-  size_t esz;
-  long long P;                       // padded LR pixels per image
-  int Hs, Ws, Hsp, Wsp;              // SR size (cropped) and padded SR size
+// The plan: its shape and the options that decide the layout (m2t_plan_geom, m2t_plan_layout.h), then everything else.
+// hd's parameter and pack offsets are set once by m2t_plan_create; lay.ws, hd's workspace offsets and the health rows are rebuilt
+// by resolve_layout() from the one region table, for the mode in force, after every change of an option: nothing is kept aside
+struct m2t_plan : m2t_plan_geom {
   m2t_layout lay;                    // names -> offsets: read at creation and by m2t_plan_query only
   m2t_plan_handles hd;
   m2t_sched sc;                      // resolve_schedule() after every change of an option
+  m2t_health_table ht;               // option "health": the rows of the record, empty on every other plan
   std::vector<m2t_pack_desc> descs;
   std::vector<char> desc_is_qkv;             // per descriptor: a packed form of a qkv_conv.weight
   std::vector<int> pack_blocks;              // (descriptor, chunk) pairs: one workgroup of the packing kernel each.  Order: every
@@ -109,24 +52,8 @@ struct m2t_plan {
   int pack_nb_base = 0, pack_nb_copy = 0, pack_nb_tr = 0;   // workgroups of the three groups (round 5: the default bf16 path skips the last two:
                                              // 6.3 M of the 14.2 M packed elements, the transposes being the slowest gathers of the kernel)
   bool have_seed = false, have_acts = false;
-  // option "inference": m2t_forward alone, on a forward-only workspace.  lay.ws / the workspace offsets of hd are then those of
-  // inference_layout(), rebuilt after every change of an option; the training layout m2t_plan_create built waits in train_ws / train_hd
-  int inference = 0;
-  // option "local_norm" (inference plans only): T > 0 = every block normalises with the statistics of a T x T window around each pixel
-  // (k_local_norm.hip -> region "xn") and its unchanged consumers get xn with the identity record "norm_id" (mean 0, rstd 1)
-  int local_norm = 0;
-  // option "health" (training plans only): 1 = a record of the tensors the forward stores, 2 = and of what the backward leaves
-  // (k_health.hip).  The rows are resolved by health_layout() from the layout table and the schedule in force; the passes use the
-  // descriptor table, the work list and the counts below and look nothing up
-  int health = 0, health_on = 1;
-  bool health_laid = false;            // lay.ws / hd carry the record's regions (resolve_layout takes them off again)
-  std::vector<std::string> health_names;       // row -> name ("sr", a "ws:" name, "grads")
-  std::vector<m2t_health_desc> health_descs;
-  std::vector<int> health_work;                // (row, chunk) pairs, forward rows first
-  int health_rows_fwd = 0, health_items_fwd = 0;
+  int health_on = 1;                   // option "health_on": the record of a plan with "health" > 0 is taken (1) or skipped (0)
   bool ws_initialised = false;         // m2t_plan_init_workspace has run: "inference" is frozen, and so is every option of an inference plan
-  m2t_region train_ws;
-  m2t_plan_handles train_hd;
   // m2t_l1_loss_deferred: the loss and the seed are produced inside the next m2t_backward (round 5)
   bool l1_deferred = false;
   const float* l1_hr = nullptr; float* l1_loss_out = nullptr; float l1_sc = 0.f, l1_R = 0.f;
@@ -179,7 +106,6 @@ struct m2t_plan {
   // its end through a table of its own stage mask, uploaded on the first pass with that mask into a plan-owned device buffer
   struct MaskTable { std::vector<m2t_red_desc> descs; void* dev = nullptr; bool uploaded = false; };
   std::map<std::vector<unsigned char>, MaskTable> mask_tables;
-  size_t arena_floats = 0;
   hipStream_t side = nullptr;
   // gradient buckets: [lo, hi) float ranges of the flat gradient buffer in the order m2t_backward completes them
   // (tail, block pairs from the last to the first, head); one event each, recorded behind the bucket's reduction
@@ -262,171 +188,17 @@ static void resolve_schedule(m2t_plan* p) {
   s.fork_on_kernel = p->use_side && p->fork_on_kernel;
 }
 
-static const int BR_C[4] = {16, 64, 256, 256};
-static const int BR_L[4] = {0, 1, 2, 2};
-
-// ---- the workspace of an inference plan (option "inference") ---------------------------------------------------------------------
-// A region the forward of the schedule in force never reads is ABSENT: its handle is M2T_NO_REGION, its name is not in the table
-// (m2t_plan_query answers -1) and the kernel that would write it gets a null pointer.
-static const size_t M2T_NO_REGION = ~(size_t)0;
-static inline char* region_ptr(char* ws, size_t off) { return off == M2T_NO_REGION ? nullptr : ws + off; }
-
-// Does m2t_forward need the region d<i + 1> / qkv<i + 1> under schedule s?  (A training plan stores both for the backward pass whatever
-// this says.)
-static bool forward_reads_d(const m2t_sched& s, int i) {
-  if (i == 0) return !s.c16_fused_fwd;                       // the fused C = 16 kernel normalises in registers: d1 is "for the backward"
-  if (!s.prep_in_fwd) return true;                           // branch_prep writes d, the projection reads it
-  // branch_prep inside the fused kernel: nothing reads d in the forward.  The C = 64 kernel has an instantiation without the store; the
-  // C = 256 kernels keep it (k_attn_fused.hip: at 256 VGPRs the kernel spills without it; k_attn_fwd2.hip takes no null), and so their region
-  return BR_C[i] == 256;
-}
-static bool forward_reads_qkv(const m2t_sched& s, int i) {
-  if (i == 0) return !s.c16_fused_fwd;
-  if (!s.c64_fused_fwd) return true;                         // projection GEMM -> attention kernel
-  return BR_C[i] == 256 && s.prep_in_fwd && s.fwd2 != 0;     // k_attn_fwd2.hip re-reads the window's own v rows from the qkv tensor
-}
-
-// The persistent regions and X0 where the training layout has them; X1 .. X<nb> alternate between two buffers (block b reads X<b> and
-// writes X<b + 1>; the last block's conv adds X0); ONE set of per-block regions under every "b<k>." name; nothing of the backward pass.
-static void inference_layout(m2t_plan* p) {
-  const m2t_sched& s = p->sc;
-  const size_t es = p->esz;
-  const int B = p->B, sc = p->scale, r0 = (sc == 4) ? 2 : sc;
-  const long long BP = (long long)B * p->P;
-  m2t_region ws;
-  m2t_plan_handles hd = p->train_hd;                         // parameter and pack offsets carry over; every workspace offset is set below
-  auto alias = [&ws](const std::string& name, const std::string& of) { ws.t[name] = ws.t.at(of); };
-  hd.zero_page = ws.add("zero_page", 256, 1);
-  hd.pack_descs = ws.add("pack_descs", p->descs.size() * sizeof(m2t_pack_desc), 1);
-  hd.pack_blocks = ws.add("pack_blocks", p->pack_blocks.size() * sizeof(int), 1);
-  hd.packed = ws.add("packed", p->lay.npacked, es);
-  hd.X[0] = ws.add("X0", BP * 64, es);
-  for (int b = 1; b <= p->nb; ++b) {
-    const std::string name = "X" + std::to_string(b);
-    if (b <= 2) hd.X[b] = ws.add(name, BP * 64, es);
-    else { alias(name, "X" + std::to_string(b - 2)); hd.X[b] = hd.X[b - 2]; }
-  }
-  m2t_block_handles b0 = hd.blk[0];
-  b0.mean = ws.add("b0.mean", B * 64, 4);
-  b0.rstd = ws.add("b0.rstd", B * 64, 4);
-  b0.xc = ws.add("b0.xc", BP * 64, es);
-  for (int i = 0; i < 4; ++i) {
-    b0.d[i] = forward_reads_d(s, i) ? ws.add("b0.d" + std::to_string(i + 1), BP * 16, es) : M2T_NO_REGION;
-    b0.qkv[i] = forward_reads_qkv(s, i) ? ws.add("b0.qkv" + std::to_string(i + 1), BP * 48, es) : M2T_NO_REGION;
-  }
-  for (int b = 0; b < p->nb; ++b) {
-    m2t_block_handles& bh = hd.blk[b];
-    bh.mean = b0.mean; bh.rstd = b0.rstd; bh.xc = b0.xc;
-    for (int i = 0; i < 4; ++i) { bh.d[i] = b0.d[i]; bh.qkv[i] = b0.qkv[i]; }
-    if (b == 0) continue;
-    const std::string k = "b" + std::to_string(b) + ".";
-    alias(k + "mean", "b0.mean"); alias(k + "rstd", "b0.rstd"); alias(k + "xc", "b0.xc");
-    for (int i = 0; i < 4; ++i) {
-      if (b0.d[i] != M2T_NO_REGION) alias(k + "d" + std::to_string(i + 1), "b0.d" + std::to_string(i + 1));
-      if (b0.qkv[i] != M2T_NO_REGION) alias(k + "qkv" + std::to_string(i + 1), "b0.qkv" + std::to_string(i + 1));
-    }
-  }
-  hd.xin = ws.add("xin", BP * 16, es);
-  hd.norm_part = ws.add("norm_part", (size_t)B * 8 * M2T_NORM_SPLIT * 64 * 3, 4);
-  hd.vring = s.fwd2 != 0 ? ws.add("vring", window_attn_fwd2_vring_elems(B, p->H / 4, p->W / 4), es) : M2T_NO_REGION;
-  hd.t1act = s.stores_t1 ? ws.add("t1act", BP * r0 * r0 * 64, es) : M2T_NO_REGION;
-  // gelu'(t1): read by the backward pass alone.  fp32 x3 keeps it: that expansion runs on the generic GEMM, whose epilogue always stores it
-  hd.t1der = (p->dt == M2T_F32 && sc == 3) ? ws.add("t1der", BP * r0 * r0 * 64, es) : M2T_NO_REGION;
-  hd.t2act = s.stores_t2 ? ws.add("t2act", BP * 16 * 64, es) : M2T_NO_REGION;
-  hd.srpre = ws.add("srpre", (size_t)B * 3 * p->Hsp * p->Wsp, 4);
-  // local_norm: the normalised block input (one buffer for every block: a block's consumers are done with it before the next block's
-  // statistics run), the fp64 {sum x, sum x^2} pairs between its two passes, and the identity record [mean = 0 | rstd = 1], [B][64] each
-  hd.xn = p->local_norm > 0 ? ws.add("xn", BP * 64, es) : M2T_NO_REGION;
-  hd.lnsum = p->local_norm > 0 ? ws.add("lnsum", BP * 64 * 2, 8) : M2T_NO_REGION;
-  hd.norm_id = p->local_norm > 0 ? ws.add("norm_id", (size_t)B * 64 * 2, 4) : M2T_NO_REGION;
-  ws.seal();
-  hd.norm_s = hd.norm_part0 = hd.t2der = hd.loss_part = hd.gpre = hd.g_t2pre = hd.g_t1pre = hd.gT = hd.gA = hd.gB = hd.gxc = hd.gn =
-      hd.gd = hd.gd2 = hd.gdwin = hd.gdwin2 = hd.head_cols = hd.arena = hd.red_descs = M2T_NO_REGION;
-  for (int set = 0; set < 2; ++set)
-    for (int i = 0; i < 4; ++i) hd.gqkv[set][i] = hd.win[set][i] = hd.relw[set][i] = M2T_NO_REGION;
-  p->lay.ws = ws;
-  p->hd = hd;
-}
-
-// ---- the step health record (option "health"; k_health.hip) -------------------------------------------------------------------------
-// The rows, from the training layout's own table and the schedule in force, then the record's regions behind the training layout.  A
-// tensor the schedule does not store (q | k | v on the recomputing attention paths, the tail's GELU tensors on the fused tails) has no
-// row; neither has a scratch region a pass only partly writes (xin, the ring buffers, the slab arena).  Order: sr, the forward's regions
-// in the order m2t_forward writes them, then at level 2 the backward's in the order it writes them, then grads.
-static void health_layout(m2t_plan* p) {
-  const m2t_sched& s = p->sc;
-  const bool x4 = p->scale == 4;
-  p->health_names.clear(); p->health_descs.clear(); p->health_work.clear();
-  auto row = [&](const std::string& name, int phase, long long ext_n) {
-    m2t_health_desc d{};
-    d.phase = phase;
-    if (ext_n >= 0) { d.off = -1; d.n = ext_n; d.dtype = M2T_F32; }
-    else {
-      auto it = p->train_ws.t.find(name);
-      if (it == p->train_ws.t.end()) return;
-      const bool f32 = name == "srpre" || name.find(".mean") != std::string::npos || name.find(".rstd") != std::string::npos;
-      d.off = (long long)it->second.off; d.n = (long long)it->second.n; d.dtype = f32 ? M2T_F32 : p->dt;
-    }
-    d.item0 = (int)(p->health_work.size() / 2);
-    d.nitems = (int)std::max<long long>(1, ceil_divll(d.n, health_tile::CHUNK));
-    for (int c = 0; c < d.nitems; ++c) { p->health_work.push_back((int)p->health_descs.size()); p->health_work.push_back(c); }
-    p->health_names.push_back(name);
-    p->health_descs.push_back(d);
-  };
-  auto ws_row = [&](const std::string& name, int phase, bool stored = true) { if (stored) row(name, phase, -1); };
-  row("sr", 0, (long long)p->B * 3 * p->Hs * p->Ws);
-  ws_row("X0", 0);
-  for (int b = 0; b < p->nb; ++b) {
-    const std::string k = "b" + std::to_string(b) + ".";
-    ws_row(k + "mean", 0); ws_row(k + "rstd", 0);
-    for (int i = 0; i < 4; ++i) {
-      ws_row(k + "d" + std::to_string(i + 1), 0);
-      ws_row(k + "qkv" + std::to_string(i + 1), 0, i == 0 ? s.stores_qkv1 : (i == 1 ? s.stores_qkv2 : true));
-    }
-    ws_row(k + "xc", 0);
-    ws_row("X" + std::to_string(b + 1), 0);
-  }
-  ws_row("t1act", 0, s.stores_t1); ws_row("t1der", 0, s.stores_t1);
-  ws_row("t2act", 0, s.stores_t2); ws_row("t2der", 0, s.stores_t2);
-  ws_row("srpre", 0);
-  p->health_rows_fwd = (int)p->health_descs.size();
-  p->health_items_fwd = (int)(p->health_work.size() / 2);
-  if (p->health >= 2) {
-    ws_row("g_t2pre", 1, x4 && s.tail_bwd == TAIL_BWD_PLAIN);
-    ws_row("g_t1pre", 1, s.tail_bwd != TAIL_BWD_X23_STREAM);
-    ws_row("gT", 1);
-    ws_row("gA", 1, p->nb >= 3); ws_row("gB", 1, p->nb >= 2);      // g(X<b>) of the even / odd blocks b >= 1
-    for (int set = 0; set < 2; ++set)                               // dq | dK | dV of the last block that used the buffer set
-      for (int i = 0; i < 4; ++i) ws_row("gqkv" + std::to_string(i) + (set ? "b" : ""), 1, set == 0 || p->nb >= 2);
-    ws_row("gn", 1);
-    ws_row("gxc", 1);                                               // after block 0: g(res), the head's cotangent
-    row("grads", 1, p->lay.nparams);
-  }
-  m2t_region& ws = p->lay.ws;                                       // (the training layout: resolve_layout put it back)
-  m2t_plan_handles& hd = p->hd;
-  const size_t rows = p->health_descs.size(), items = p->health_work.size() / 2;
-  hd.health_descs = ws.add("health_descs", rows * sizeof(m2t_health_desc), 1);
-  hd.health_work = ws.add("health_work", items * 2 * sizeof(int), 1);
-  hd.health = ws.add("health", (1 + rows) * health_tile::SLOTS, 8);
-  hd.health_part = ws.add("health_part", items * health_tile::SLOTS, 8);
-  ws.seal();
-  p->health_laid = true;
-}
 static int health_record(m2t_plan* p, int phase, const void* ext, char* ws, hipStream_t st) {
   const m2t_plan_handles& hd = p->hd;
-  const int row0 = phase ? p->health_rows_fwd : 0, item0 = phase ? p->health_items_fwd : 0;
-  const int nrows = phase ? (int)p->health_descs.size() - row0 : p->health_rows_fwd;
-  const int nitems = phase ? (int)(p->health_work.size() / 2) - item0 : p->health_items_fwd;
+  const int row0 = phase ? p->ht.rows_fwd : 0, item0 = phase ? p->ht.items_fwd : 0;
+  const int nrows = phase ? (int)p->ht.descs.size() - row0 : p->ht.rows_fwd;
+  const int nitems = phase ? (int)(p->ht.work.size() / 2) - item0 : p->ht.items_fwd;
   return launch_health_record(ws, ext, (const m2t_health_desc*)(ws + hd.health_descs), (const int*)(ws + hd.health_work),
                               (double*)(ws + hd.health_part), (double*)(ws + hd.health), phase, row0, nrows, item0, nitems, st);
 }
 
-// the layout that goes with p->inference and the schedule in force (resolve_schedule first)
-static void resolve_layout(m2t_plan* p, bool was_inference) {
-  if (p->inference) inference_layout(p);
-  else if (was_inference || p->health_laid) { p->lay.ws = p->train_ws; p->hd = p->train_hd; p->health_laid = false; }
-  if (!p->inference && p->health > 0) health_layout(p);
-}
+// the name table, the workspace handles and the health rows that go with the mode and the schedule in force (resolve_schedule first)
+static void resolve_layout(m2t_plan* p) { m2t_resolve_workspace(*p, p->sc, p->hd, p->lay.ws, p->ht); }
 static int refuse_inference(const m2t_plan* p, const char* who) {
   if (!p->inference) return 0;
   return m2t_set_error_at(M2T_ERR_STATE, who, "this is an inference plan (option \"inference\"): it keeps no activations and no seed");
@@ -451,9 +223,6 @@ extern "C" int m2t_plan_create(m2t_plan** out, int B, int H0, int W0, int scale,
   m2t_layout& lay = p->lay;
   m2t_plan_handles& hd = p->hd;
   hd = m2t_plan_handles{};
-  hd.xn = hd.lnsum = hd.norm_id = M2T_NO_REGION;
-  hd.health = hd.health_part = hd.health_descs = hd.health_work = M2T_NO_REGION;
-  hd.X.resize(n_blocks + 1);
   hd.blk.assign(n_blocks, m2t_block_handles{});
   auto param = [&](const std::string& n, long long cnt) { lay.add_param(n, cnt); return lay.poff[n]; };
   // ---- parameters: trainable tensors in the reference's registration order ----
@@ -507,12 +276,7 @@ extern "C" int m2t_plan_create(m2t_plan** out, int B, int H0, int W0, int scale,
     hd.t3 = p->add_pack("t3", "tail.3.weight", M2T_PACK_SHUF_ROWS, 256 * 64, 64, 4, 64);
     hd.t3T = p->add_pack("t3T", "tail.3.weight", M2T_PACK_SHUF_ROWS_T, 256 * 64, 64, 4, 64);
   }
-  // ---- workspace ----
-  const size_t es = p->esz;
-  const long long BP = (long long)B * p->P;
-  m2t_region& ws = lay.ws;
-  hd.zero_page = ws.add("zero_page", 256, 1);          // source of every out-of-image pixel the LDS-DMA kernels stage (k_conv.hip)
-  hd.pack_descs = ws.add("pack_descs", p->descs.size() * sizeof(m2t_pack_desc), 1);
+  // ---- the sizes the workspace takes from here (m2t_plan_geom): the pack tables, the ring buffer, the slab arena ----
   for (int group = 0; group < 3; ++group) {
     int nb_g = 0;
     for (size_t i = 0; i < p->descs.size(); ++i) {
@@ -523,56 +287,11 @@ extern "C" int m2t_plan_create(m2t_plan** out, int B, int H0, int W0, int scale,
     }
     (group == 0 ? p->pack_nb_base : (group == 1 ? p->pack_nb_copy : p->pack_nb_tr)) = nb_g;
   }
-  hd.pack_blocks = ws.add("pack_blocks", p->pack_blocks.size() * sizeof(int), 1);
-  hd.packed = ws.add("packed", lay.npacked, es);
-  for (int b = 0; b <= n_blocks; ++b) hd.X[b] = ws.add("X" + std::to_string(b), BP * 64, es);
-  for (int b = 0; b < n_blocks; ++b) {
-    m2t_block_handles& bh = hd.blk[b];
-    const std::string k = "b" + std::to_string(b) + ".";
-    bh.mean = ws.add(k + "mean", B * 64, 4);
-    bh.rstd = ws.add(k + "rstd", B * 64, 4);
-    bh.xc = ws.add(k + "xc", BP * 64, es);
-    for (int i = 0; i < 4; ++i) {
-      bh.d[i] = ws.add(k + "d" + std::to_string(i + 1), BP * 16, es);
-      bh.qkv[i] = ws.add(k + "qkv" + std::to_string(i + 1), BP * 48, es);
-    }
-  }
-  hd.xin = ws.add("xin", BP * 16, es);
-  ws.add("a", BP * 16, es);
-  hd.norm_part = ws.add("norm_part", (size_t)B * 8 * M2T_NORM_SPLIT * 64 * 3, 4);      // (the conv epilogue leaves up to 256 partials per image)
-  hd.norm_s = ws.add("norm_s", (size_t)B * 64 * 2, 4);
-  hd.vring = ws.add("vring", window_attn_fwd2_vring_elems(B, p->H / 4, p->W / 4), es);      // v rows of the ring keys (k_attn_fwd2.hip)
-  hd.norm_part0 = ws.add("norm_part0", (size_t)B * p->H * (p->W / 16) * 32, 4);      // per-tile plane-0 partials of the InstanceNorm backward (fused_norm_red)
-  // tail activations: gelu(t) and gelu'(t) of each expansion (the pre-activation t itself is never needed again)
-  hd.t1act = ws.add("t1act", BP * r0 * r0 * 64, es);
-  hd.t1der = ws.add("t1der", BP * r0 * r0 * 64, es);
-  if (s == 4) { hd.t2act = ws.add("t2act", BP * 16 * 64, es); hd.t2der = ws.add("t2der", BP * 16 * 64, es); }
-  hd.srpre = ws.add("srpre", (size_t)B * 3 * p->Hsp * p->Wsp, 4);
-  hd.loss_part = ws.add("loss_part", M2T_LOSS_BLOCKS, 4);
-  // backward
-  hd.gpre = ws.add("gpre", (size_t)B * 3 * p->Hsp * p->Wsp, 4);
-  if (s == 4) hd.g_t2pre = ws.add("g_t2pre", BP * 16 * 64, es);
-  hd.g_t1pre = ws.add("g_t1pre", BP * r0 * r0 * 64, es);
-  hd.gT = ws.add("gT", BP * 64, es);
-  hd.gA = ws.add("gA", BP * 64, es);
-  hd.gB = ws.add("gB", BP * 64, es);
-  hd.gxc = ws.add("gxc", BP * 64, es);
-  hd.gn = ws.add("gn", BP * 64, es);
-  ws.add("ga", BP * 16, es);
-  hd.gd = ws.add("gd", BP * 16, es);
-  hd.gd2 = ws.add("gd2", BP * 16, es);       // second set: a branch's attention backward reads the previous branch's rows while it writes its own (fused_prep_bwd)
-  hd.gdwin2 = ws.add("gdwin2", BP * 9, es);
-  hd.gdwin = ws.add("gdwin", BP * 9, es);      // ring rows of the fused projection data gradient: [windows][36][C], windows * C = BP / 4
-  hd.head_cols = ws.add("head_cols", BP * 32, es);
-  for (int i = 0; i < 4; ++i) {     // TWO sets per branch (even / odd blocks): the side stream may lag the main chain by two blocks, and
-    for (int set = 0; set < 2; ++set) {   // the main chain waits for it once per block instead of once per branch
-      const std::string sfx = std::to_string(i) + (set ? "b" : "");
-      hd.gqkv[set][i] = ws.add("gqkv" + sfx, BP * 48, es);
-      hd.win[set][i] = ws.add("win" + sfx, BP * 50, es);
-      hd.relw[set][i] = ws.add("relw" + sfx, (size_t)(BP / 64) * 10 * 16, 4);
-    }
-  }
-  ws.add("rel_part", 32 * 10 * 256, 4);
+  p->n_pack_descs = p->descs.size();
+  p->n_pack_block_ints = p->pack_blocks.size();
+  p->npacked = (size_t)lay.npacked;
+  p->nparams = (size_t)lay.nparams;
+  p->vring_elems = window_attn_fwd2_vring_elems(B, p->H / 4, p->W / 4);
   {
     // arena: every slab set of one backward pass (see m2t_backward); sized from the launchers' slab rules
     size_t per_block = (size_t)256 * 9 * 64 * 64 + (size_t)256 * 64;                 // conv wgrad + ff bias partials
@@ -580,11 +299,7 @@ extern "C" int m2t_plan_create(m2t_plan** out, int B, int H0, int W0, int scale,
     per_block += 4 * (size_t)32 * 2560;                                               // rel-pos partials
     size_t tail = 2 * (size_t)256 * (16384 + 36864) + (size_t)1024 * 2048 + 4 * (size_t)256 * 768 + (size_t)256 * 1728 * 2;
     p->arena_floats = per_block * n_blocks + tail + (size_t)512 * (64 * 32 + 64) + (1u << 20);
-    hd.arena = ws.add("arena", p->arena_floats, 4);
-    hd.red_descs = ws.add("red_descs", 512 * sizeof(m2t_red_desc), 1);
   }
-  ws.add("col_part", (size_t)256 * 768, 4);
-  ws.seal();
   {
     // gradient buckets in completion order (see m2t_backward): the tail, then the blocks in the groups the
     // deferred reductions are flushed in (after every even block index, walking from the last block to the first),
@@ -600,8 +315,7 @@ extern "C" int m2t_plan_create(m2t_plan** out, int B, int H0, int W0, int scale,
     p->buckets.push_back({0, hi});
   }
   resolve_schedule(p);
-  p->train_ws = lay.ws;
-  p->train_hd = hd;
+  resolve_layout(p);
   *out = p;
   return 0;
 }
@@ -650,11 +364,11 @@ extern "C" long long m2t_plan_query(const m2t_plan* p, const char* key) {
   }
   // the health record's rows (option "health"): names are resolved here, never by a pass
   if (k.rfind("health_", 0) == 0) {
-    const long long rows = p->health > 0 ? (long long)p->health_descs.size() : 0;
+    const long long rows = p->health > 0 ? (long long)p->ht.descs.size() : 0;
     if (k == "health_rows") return rows;
     if (k.rfind("health_row:", 0) == 0) {
       const std::string name = k.substr(11);
-      for (long long r = 0; r < rows; ++r) if (p->health_names[r] == name) return r;
+      for (long long r = 0; r < rows; ++r) if (p->ht.names[r] == name) return r;
       return -1;
     }
     if (k.rfind("health_phase:", 0) == 0 || k.rfind("health_name:", 0) == 0) {
@@ -662,9 +376,9 @@ extern "C" long long m2t_plan_query(const m2t_plan* p, const char* key) {
       char* end = nullptr;
       const long long r = strtoll(arg, &end, 10);
       if (end == arg || *end || r < 0 || r >= rows) return -1;
-      if (k[7] == 'p') return p->health_descs[r].phase;
-      g_err = p->health_names[r];                  // "health_name:<index>": the name goes where m2t_last_error_string() reads
-      return (long long)p->health_names[r].size();
+      if (k[7] == 'p') return p->ht.descs[r].phase;
+      g_err = p->ht.names[r];                  // "health_name:<index>": the name goes where m2t_last_error_string() reads
+      return (long long)p->ht.names[r].size();
     }
     return -1;
   }
@@ -696,10 +410,10 @@ extern "C" int m2t_plan_init_workspace(m2t_plan* p, void* workspace, void* strea
   std::vector<double> health_head;                   // (alive until the synchronisation below)
   if (p->health > 0 && p->hd.health != M2T_NO_REGION) {
     // the record: descriptor table and work list next to the other tables, every row zero, the header row "nothing recorded"
-    const size_t rows = p->health_descs.size();
-    e = hipMemcpyAsync(ws + p->hd.health_descs, p->health_descs.data(), rows * sizeof(m2t_health_desc), hipMemcpyHostToDevice, (hipStream_t)stream);
+    const size_t rows = p->ht.descs.size();
+    e = hipMemcpyAsync(ws + p->hd.health_descs, p->ht.descs.data(), rows * sizeof(m2t_health_desc), hipMemcpyHostToDevice, (hipStream_t)stream);
     if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
-    e = hipMemcpyAsync(ws + p->hd.health_work, p->health_work.data(), p->health_work.size() * sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream);
+    e = hipMemcpyAsync(ws + p->hd.health_work, p->ht.work.data(), p->ht.work.size() * sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream);
     if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
     e = hipMemsetAsync(ws + p->hd.health, 0, (1 + rows) * health_tile::SLOTS * sizeof(double), (hipStream_t)stream);
     if (e != hipSuccess) return m2t_set_hip_error(e, __FILE__, __LINE__);
@@ -1645,10 +1359,9 @@ extern "C" int m2t_set_option(m2t_plan* p, const char* key, long long value) {
       return m2t_set_error(M2T_ERR_STATE, "m2t_set_option: \"inference\" cannot be cleared while \"local_norm\" > 0 (local statistics exist on inference plans only: clear \"local_norm\" first)");
     if (value != 0 && p->health > 0)
       return m2t_set_error(M2T_ERR_STATE, "m2t_set_option: \"inference\" cannot be set while \"health\" > 0 (the health record exists on training plans only: clear \"health\" first)");
-    const bool was = p->inference != 0;
     p->inference = value != 0;
     p->have_acts = p->have_seed = p->l1_deferred = false;
-    resolve_layout(p, was);
+    resolve_layout(p);
     return 0;
   }
   if (k == "local_norm") {
@@ -1658,7 +1371,7 @@ extern "C" int m2t_set_option(m2t_plan* p, const char* key, long long value) {
     if (!p->inference)
       return m2t_set_error(M2T_ERR_STATE, "m2t_set_option: \"local_norm\" needs an inference plan: set \"inference\" to 1 first (the backward pass has no local statistics)");
     p->local_norm = (int)value;
-    resolve_layout(p, false);
+    resolve_layout(p);
     return 0;
   }
   if (k == "health") {
@@ -1668,7 +1381,7 @@ extern "C" int m2t_set_option(m2t_plan* p, const char* key, long long value) {
     if (p->inference)
       return m2t_set_error(M2T_ERR_STATE, "m2t_set_option: \"health\" needs a training plan: this is an inference plan (option \"inference\"), which stores no stage");
     p->health = (int)value;
-    resolve_layout(p, false);
+    resolve_layout(p);
     return 0;
   }
   if (k == "health_on") {
@@ -1684,7 +1397,7 @@ extern "C" int m2t_set_option(m2t_plan* p, const char* key, long long value) {
     return m2t_set_error(M2T_ERR_STATE, "m2t_set_option: the layout of an initialised inference plan is frozen (set options before m2t_plan_init_workspace)");
   p->red_uploaded = false;     // the deferred-reduction table depends on the schedule: rebuild it on the next backward
   for (auto& kv : p->mask_tables) kv.second.uploaded = false;
-  struct Resolve { m2t_plan* p; ~Resolve() { resolve_schedule(p); resolve_layout(p, false); } } resolve_on_return{p};     // whichever raw value changes below
+  struct Resolve { m2t_plan* p; ~Resolve() { resolve_schedule(p); resolve_layout(p); } } resolve_on_return{p};     // whichever raw value changes below
   if (k == "side_stream") { p->use_side = (value != 0); return 0; }
   if (k == "fork_on_kernel") { p->fork_on_kernel = value != 0; return 0; }
   if (k == "fused_prep_fwd") { p->use_fused_prep_fwd = value != 0; return 0; }
