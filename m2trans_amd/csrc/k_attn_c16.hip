@@ -35,23 +35,9 @@ struct __attribute__((aligned(16))) C16WaveLds {
 static_assert(sizeof(C16WaveLds) == 15360, "wave LDS layout");
 static_assert(sizeof(float) * 16 * 113 <= sizeof(bf16_t) * (112 + 64 + 64) * 16, "KA must fit over Kh | Qs | DOs");
 
-__device__ __forceinline__ void mma4(f32x4& acc, bf16x4 a, bf16x4 b) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, acc, 0, 0, 0);
-}
-// transposing read: the lane passes the address of ITS 8-byte piece (row r0 + (i >> 2), columns 4 (i & 3) ..)
-// and receives column i of rows r0 .. r0 + 3  (i = lane & 15; r0 may differ per 16-lane group)
-__device__ __forceinline__ bf16x4 tr4(const bf16_t* p) {
-  typedef bf16x4 __attribute__((address_space(3))) * lds_ptr;
-  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)p);
-}
+// (mma4, tr4, pack4 and zero4 are in m2t_common.h)
 __device__ __forceinline__ bf16x4 ld4(const bf16_t* p) { return *reinterpret_cast<const bf16x4*>(p); }
 __device__ __forceinline__ void st4(bf16_t* p, bf16x4 v) { *reinterpret_cast<bf16x4*>(p) = v; }
-__device__ __forceinline__ bf16x4 pack4(float a, float b, float c, float d) {
-  bf16x4 v;
-  v[0] = (bf16_t)a; v[1] = (bf16_t)b; v[2] = (bf16_t)c; v[3] = (bf16_t)d;
-  return v;
-}
-__device__ __forceinline__ bf16x4 zero4() { return pack4(0.f, 0.f, 0.f, 0.f); }
 __device__ __forceinline__ int lr_of(int lane) { return lane & 15; }
 __device__ __forceinline__ int g_of(int lane) { return lane >> 4; }
 // LDS operations of one wave execute in issue order, so a wave-private buffer needs no hardware wait between
@@ -93,10 +79,11 @@ __global__ void __launch_bounds__(256, 2) window_attn_bwd_c16_kernel(const bf16_
 #pragma unroll
       for (int t = 0; t < WA_KT; ++t) {
         const int key = min(16 * t + lr, WA_NK - 1);
-        const int kr = key / 10, kc = key - kr * 10;
+        int kr, kc;
+        key_rc(key, kr, kc);
         const int y = 8 * wy + kr - 1, x = 8 * wx + kc - 1;
         const bool in = (16 * t + lr < WA_NK) && y >= 0 && y < h && x >= 0 && x < w;
-        const int yc = min(max(y, 0), h - 1), xc = min(max(x, 0), w - 1);
+        const int yc = clamp_px(y, h), xc = clamp_px(x, w);
         const bf16x4 v = ld4(dsrc + (img + (long long)yc * w + xc) * C16 + 4 * g);
         xk[t] = in ? v : zero4();
       }
@@ -109,7 +96,8 @@ __global__ void __launch_bounds__(256, 2) window_attn_bwd_c16_kernel(const bf16_
 #pragma unroll
     for (int t = 0; t < WA_KT; ++t) {
       const int key = 16 * t + lr;
-      const int kr = key / 10, kc = key - kr * 10;
+      int kr, kc;
+      key_rc(key, kr, kc);
       const int y = 8 * wy + kr - 1, x = 8 * wx + kc - 1;
       kraw[t] = zero4();
       vA[t] = zero4();
@@ -133,8 +121,8 @@ __global__ void __launch_bounds__(256, 2) window_attn_bwd_c16_kernel(const bf16_
         f32x4 ak = (f32x4){0.f, 0.f, 0.f, 0.f}, av = (f32x4){0.f, 0.f, 0.f, 0.f};
         mma4(ak, wA[1], xk[t]);
         mma4(av, wA[2], xk[t]);
-        kraw[t] = pack4(ak[0], ak[1], ak[2], ak[3]);
-        vA[t] = pack4(av[0], av[1], av[2], av[3]);
+        kraw[t] = pack4(ak);
+        vA[t] = pack4(av);
       }
     }
 #pragma unroll
@@ -145,7 +133,7 @@ __global__ void __launch_bounds__(256, 2) window_attn_bwd_c16_kernel(const bf16_
       if (dsrc) {
         f32x4 a = (f32x4){0.f, 0.f, 0.f, 0.f};
         mma4(a, wA[0], xq[qt]);
-        qv = pack4(a[0], a[1], a[2], a[3]);
+        qv = pack4(a);
       } else {
         qv = ld4(qkv + qpix * (3 * C16) + 4 * g);
       }
@@ -228,8 +216,8 @@ __global__ void __launch_bounds__(256, 2) window_attn_bwd_c16_kernel(const bf16_
 #pragma unroll
     for (int t = 0; t < WA_KT; ++t) {
       const f32x4 d4 = s[t] * (dp[t] - DEL);
-      const bf16x4 pb = pack4(s[t][0], s[t][1], s[t][2], s[t][3]);
-      const bf16x4 db = pack4(d4[0], d4[1], d4[2], d4[3]);
+      const bf16x4 pb = pack4(s[t]);
+      const bf16x4 db = pack4(d4);
       st4(&L.Pq[lr][16 * t + 4 * g], pb);
       st4(&L.Dq[lr][16 * t + 4 * g], db);
       mma4(o, kT[t], db);
@@ -238,7 +226,7 @@ __global__ void __launch_bounds__(256, 2) window_attn_bwd_c16_kernel(const bf16_
     {
       const int q = 16 * qt + lr;
       const long long qpix = img + (long long)(8 * wy + (q >> 3)) * w + 8 * wx + (q & 7);
-      st4(gqkv + qpix * (3 * C16) + 4 * g, pack4(o[0], o[1], o[2], o[3]));
+      st4(gqkv + qpix * (3 * C16) + 4 * g, pack4(o));
     }
     wave_sync();
     // dV^T [c][key] += dO^T P ; dK^^T [c][key] += q^T dS   (contraction over this tile's 16 queries)
@@ -258,8 +246,8 @@ __global__ void __launch_bounds__(256, 2) window_attn_bwd_c16_kernel(const bf16_
     const int key = 16 * t + lr;
     if (key < WA_NK) {
       bf16_t* wp = dkv_row(gqkv, win, (long long)wi, b, wy, wx, h, w, C16, key) + 4 * g;
-      st4(wp, pack4(dkT[t][0], dkT[t][1], dkT[t][2], dkT[t][3]));
-      st4(wp + C16, pack4(dvT[t][0], dvT[t][1], dvT[t][2], dvT[t][3]));
+      st4(wp, pack4(dkT[t]));
+      st4(wp + C16, pack4(dvT[t]));
     }
   }
   // ---- rel-pos gradient: dK^ summed over key columns (c < 8) / key rows (c >= 8), phantom keys included ----
@@ -318,7 +306,8 @@ __global__ void __launch_bounds__(256, 4) window_attn_fwd_c16_kernel(const bf16_
 #pragma unroll
     for (int t = 0; t < WA_KT; ++t) {
       const int key = 16 * t + lr;
-      const int kr = key / 10, kc = key - kr * 10;
+      int kr, kc;
+      key_rc(key, kr, kc);
       const int y = 8 * wy + kr - 1, x = 8 * wx + kc - 1;
       kraw[t] = zero4();
       vraw[t] = zero4();
@@ -384,14 +373,14 @@ __global__ void __launch_bounds__(256, 4) window_attn_fwd_c16_kernel(const bf16_
 #pragma unroll
     for (int t = 0; t < WA_KT; ++t) {
       const f32x4 pv = s[t] * INV;
-      mma4(o, vT[t], pack4(pv[0], pv[1], pv[2], pv[3]));
+      mma4(o, vT[t], pack4(pv));
     }
     if (res) {
       const bf16x4 rv = rraw[qt];
 #pragma unroll
       for (int r = 0; r < 4; ++r) o[r] += (float)rv[r];
     }
-    st4(out + qpix * ldo + oc0 + 4 * g, pack4(o[0], o[1], o[2], o[3]));
+    st4(out + qpix * ldo + oc0 + 4 * g, pack4(o));
   }
 }
 
@@ -444,10 +433,11 @@ __global__ void __launch_bounds__(256, 4) window_attn_fused_c16_fwd_kernel(const
 #pragma unroll
   for (int t = 0; t < WA_KT; ++t) {
     const int key = min(16 * t + lr, WA_NK - 1);
-    const int kr = key / 10, kc = key - kr * 10;
+    int kr, kc;
+    key_rc(key, kr, kc);
     const int y = 8 * wy + kr - 1, xx = 8 * wx + kc - 1;
     inb[t] = (16 * t + lr < WA_NK) && y >= 0 && y < h && xx >= 0 && xx < w;
-    const int yc = min(max(y, 0), h - 1), xc = min(max(xx, 0), w - 1);
+    const int yc = clamp_px(y, h), xc = clamp_px(xx, w);
     xk[t] = ld4(x + (img + (long long)yc * w + xc) * C16 + 4 * g);
   }
   {
@@ -474,7 +464,7 @@ __global__ void __launch_bounds__(256, 4) window_attn_fused_c16_fwd_kernel(const
     st4(&Xr[q][4 * g], xn);
     f32x4 a = (f32x4){0.f, 0.f, 0.f, 0.f};
     mma4(a, wA[0], xn);
-    const bf16x4 qr = pack4(a[0], a[1], a[2], a[3]);
+    const bf16x4 qr = pack4(a);
     if (qkv) st4(qkv + qpix * (3 * C16) + 4 * g, qr);         // (qkv == nullptr: the backward kernel recomputes q | k | v from d)
     st4(&Qs[q][4 * g], qr);
   }
@@ -485,15 +475,17 @@ __global__ void __launch_bounds__(256, 4) window_attn_fused_c16_fwd_kernel(const
     f32x4 ak = (f32x4){0.f, 0.f, 0.f, 0.f}, av = (f32x4){0.f, 0.f, 0.f, 0.f};
     mma4(ak, wA[1], xn);
     mma4(av, wA[2], xn);
-    const bf16x4 kraw = pack4(ak[0], ak[1], ak[2], ak[3]), vraw = pack4(av[0], av[1], av[2], av[3]);
+    const bf16x4 kraw = pack4(ak), vraw = pack4(av);
     const int key = 16 * t + lr;
-    const int kr = key / 10, kc = key - kr * 10;
+    int kr, kc;
+    key_rc(key, kr, kc);
     if (qkv && key < WA_NK && kr >= 1 && kr <= 8 && kc >= 1 && kc <= 8) {   // the window's own pixels: saved for the backward pass
       bf16_t* pk = qkv + (img + (long long)(8 * wy + kr - 1) * w + 8 * wx + kc - 1) * (3 * C16) + 4 * g;
       st4(pk + C16, kraw);
       st4(pk + 2 * C16, vraw);
     }
-    const int kk = min(key, WA_NK - 1), kr2 = kk / 10, kc2 = kk - kr2 * 10;
+    int kr2, kc2;
+    key_rc(min(key, WA_NK - 1), kr2, kc2);
     const f32x4 rel = *reinterpret_cast<const f32x4*>(&RelS[(g < 2) ? kr2 * 8 + 4 * g : 80 + kc2 * 8 + 4 * g - 8]);
     kA[t] = (key < WA_NK) ? pack4((float)kraw[0] + rel[0], (float)kraw[1] + rel[1], (float)kraw[2] + rel[2], (float)kraw[3] + rel[3])
                           : zero4();
@@ -543,12 +535,12 @@ __global__ void __launch_bounds__(256, 4) window_attn_fused_c16_fwd_kernel(const
 #pragma unroll
     for (int t = 0; t < WA_KT; ++t) {
       const f32x4 pv = s[t] * INV;
-      mma4(o, vT[t], pack4(pv[0], pv[1], pv[2], pv[3]));
+      mma4(o, vT[t], pack4(pv));
     }
     const bf16x4 rv = ld4(&Xr[q][4 * g]);                      // residual = the normalised input itself (:139)
 #pragma unroll
     for (int r = 0; r < 4; ++r) o[r] += (float)rv[r];
-    st4(out + qpix * ldo + oc0 + 4 * g, pack4(o[0], o[1], o[2], o[3]));
+    st4(out + qpix * ldo + oc0 + 4 * g, pack4(o));
   }
 }
 

@@ -51,16 +51,7 @@
 
 namespace {
 
-// key order of this kernel: 0..63 the window's own pixels (= query order), 64..99 the ring in ring_index order.
-// Branch-free (selects): the callers issue loads whose addresses depend on the result.
-__device__ __forceinline__ void fused_key_rc(int k, int& kr, int& kc) {
-  const int r = k - 64;
-  const int kr_ring = (r < 10) ? 0 : ((r < 20) ? 9 : ((r < 28) ? r - 19 : r - 27));
-  const int kc_ring = (r < 10) ? r : ((r < 20) ? r - 10 : ((r < 28) ? 0 : 9));
-  kr = (k < 64) ? (k >> 3) + 1 : kr_ring;
-  kc = (k < 64) ? (k & 7) + 1 : kc_ring;
-}
-
+// key order of this kernel: own pixels first (own_first_key_rc, m2t_window.h)
 template <int C> struct FusedCfg {
   static constexpr int LD = C + 8;          // bf16 rows of Xs|Vs / Kh / Qs
   // P [query][key].  C = 256 (8 waves, two key halves, one workgroup per CU): keys 0..127 in a region of its own, which the rel-pos table
@@ -88,23 +79,6 @@ template <int C> struct FusedCfg {
   static_assert(P_OVER_K || szRel <= szP, "the rel-pos table borrows P's region");
   static_assert(szX % 16 == 0 && szQ % 16 == 0 && szP % 16 == 0, "16-byte carve offsets");
 };
-
-__device__ __forceinline__ Frag8<bf16_t> tr8z(const bf16_t* base, int ld, int row_lo_base, int row_hi_base, int col0, int lane,
-                                              int zero_row) {
-  const int i = lane & 15, qq = i >> 2, pp = i & 3;
-  typedef bf16x4 __attribute__((address_space(3))) * lds_ptr;
-  const int rlo = min(row_lo_base + qq, zero_row), rhi = min(row_hi_base + qq, zero_row);
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)(base + rlo * ld + col0 + 4 * pp));
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)(base + rhi * ld + col0 + 4 * pp));
-  Frag8<bf16_t> f;
-  f.v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return f;
-}
-
-__device__ __forceinline__ bf16x4 pack4(const f32x4& a) {
-  bf16x4 r = {(bf16_t)a[0], (bf16_t)a[1], (bf16_t)a[2], (bf16_t)a[3]};
-  return r;
-}
 
 // PREP: branch_prep of this branch (models/M2Trans_network.py:141-158: xin = (norm(x)[chunk k] + xc[chunk k - 1]) / 2, d = DWT^L(xin))
 // runs inside phase 0 instead of in its own launch in front of this kernel: the window computes xin for the (2^L)^2 pixel blocks
@@ -192,7 +166,7 @@ __global__ void __launch_bounds__(NW * 64, (C == 64) ? 4 : 1) window_attn_fused_
       const int px = (i >> 1) % S, kx = (i / (2 * S)) % 10, py = (i / (20 * S)) % S, ky = i / (20 * NPX);
       const int yy = 8 * gm.wy + ky - 1, xx = 8 * gm.wx + kx - 1;
       ok[it] = yy >= 0 && yy < h && xx >= 0 && xx < w;
-      const int Y = S * min(max(yy, 0), h - 1) + py, X = S * min(max(xx, 0), w - 1) + px;     // clamped: the loads are unconditional
+      const int Y = S * clamp_px(yy, h) + py, X = S * clamp_px(xx, w) + px;                   // clamped: the loads are unconditional
       const long long o = (((long long)gm.b * H + Y) * W + X) * 16 + half * 8;
       xf[it] = load8(pa.xn + o);
       pf[it] = load8(pa.xprev + o);
@@ -274,10 +248,10 @@ __global__ void __launch_bounds__(NW * 64, (C == 64) ? 4 : 1) window_attn_fused_
       const int idx = tid + it * NTHR;
       const int key = min(idx / VEC, 100), cv = idx % VEC;
       int kr, kc;
-      fused_key_rc(min(key, 99), kr, kc);
+      own_first_key_rc(min(key, 99), kr, kc);
       const int yy = 8 * gm.wy + kr - 1, xx = 8 * gm.wx + kc - 1;
       ok[it] = (key < 100) && yy >= 0 && yy < h && xx >= 0 && xx < w;
-      const int yc = min(max(yy, 0), h - 1), xc = min(max(xx, 0), w - 1);
+      const int yc = clamp_px(yy, h), xc = clamp_px(xx, w);
       xf[it] = load8(x + (((long long)gm.b * h + yc) * w + xc) * C + cv * 8);
     }
 #pragma unroll
@@ -412,7 +386,7 @@ __global__ void __launch_bounds__(NW * 64, (C == 64) ? 4 : 1) window_attn_fused_
     const int key = 16 * t + lr;
     if (key < WA_NK) {
       int kr, kc;
-      fused_key_rc(key, kr, kc);
+      own_first_key_rc(key, kr, kc);
       const long long qp = (key < 64) ? gm.query_pixel(key) : 0;
 #pragma unroll
       for (int m = 0; m < TPW; ++m) {
@@ -532,7 +506,7 @@ __global__ void __launch_bounds__(NW * 64, (C == 64) ? 4 : 1) window_attn_fused_
     for (int c4 = 0; c4 < 4; ++c4) {
       Frag8<T> a[TPW];
 #pragma unroll
-      for (int m = 0; m < TPW; ++m) a[m] = tr8z(&Xs[0][0], LD, 32 * c4 + 8 * g, 32 * c4 + 8 * g + 4, 16 * (wv * TPW + m), lane, ZR);
+      for (int m = 0; m < TPW; ++m) a[m] = load8_tr_z(&Xs[0][0], LD, 32 * c4 + 8 * g, 32 * c4 + 8 * g + 4, 16 * (wv * TPW + m), lane, ZR);
 #pragma unroll
       for (int qt = 0; qt < 4; ++qt) {
         // (P rows of 112 keys: the contraction padding 112..127 of the last k-step is read from the zero row of Xs | Vs instead)

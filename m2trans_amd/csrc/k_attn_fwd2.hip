@@ -94,41 +94,7 @@ struct Fwd2Args {
   int stagger;             // TW = 1: workgroups of the odd rounds of 256 (the second workgroup of each CU) start this many x 8 k cycles late
 };
 
-// key order: 0..63 the window's own pixels (= query order), 64..99 the ring in ring_index order (branch-free)
-__device__ __forceinline__ void f2_key_rc(int k, int& kr, int& kc) {
-  const int r = k - 64;
-  const int kr_ring = (r < 10) ? 0 : ((r < 20) ? 9 : ((r < 28) ? r - 19 : r - 27));
-  const int kc_ring = (r < 10) ? r : ((r < 20) ? r - 10 : ((r < 28) ? 0 : 9));
-  kr = (k < 64) ? (k >> 3) + 1 : kr_ring;
-  kc = (k < 64) ? (k & 7) + 1 : kc_ring;
-}
-__device__ __forceinline__ bf16x4 f2_pack4(const f32x4& a) {
-  bf16x4 r = {(bf16_t)a[0], (bf16_t)a[1], (bf16_t)a[2], (bf16_t)a[3]};
-  return r;
-}
-// transposed 8-element operand out of a [row][channel] tile: elements 0..3 = rows lo + 0..3, 4..7 = rows hi + 0..3 at column
-// col0 + (lane & 15); rows >= zero_row alias the zero row
-__device__ __forceinline__ Frag8<bf16_t> f2_tr8(const bf16_t* base, int ld, int lo, int hi, int col0, int lane, int zero_row) {
-  const int i = lane & 15, qq = i >> 2, pp = i & 3;
-  typedef bf16x4 __attribute__((address_space(3))) * lds_ptr;
-  const int rlo = min(lo + qq, zero_row), rhi = min(hi + qq, zero_row);
-  const bf16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)(base + rlo * ld + col0 + 4 * pp));
-  const bf16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)(base + rhi * ld + col0 + 4 * pp));
-  Frag8<bf16_t> f;
-  f.v = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-  return f;
-}
-// window `wi` (logical index) of an h x w map
-__device__ __forceinline__ WinGeom f2_geom(int h, int w, int wi) {
-  WinGeom g;
-  g.h = h; g.w = w; g.nw = w / 8; g.nh = h / 8;
-  g.wi = wi;
-  g.wx = wi % g.nw;
-  const int q = wi / g.nw;
-  g.wy = q % g.nh;
-  g.b = q / g.nh;
-  return g;
-}
+// key order: own pixels first (own_first_key_rc, m2t_window.h)
 
 // pointers that KEEP their address space through laundering asm statements and hand-made offsets (a generic pointer turns every
 // access into a FLAT one, which counts in vmcnt AND lgkmcnt: each wait then drains both queues)
@@ -159,7 +125,7 @@ __global__ void __launch_bounds__(256 * TW, 2) window_attn_fwd2_kernel(Fwd2Args 
   const int h = pa.h, w = pa.w;
   const int wi0 = TW * xcd_block_index();                               // the workgroup's first window (TW = 2: windows wi0, wi0 + 1)
   const int mywin = wv >> 2, qt = wv & 3;                               // attention role of the wave: (window, query tile)
-  const WinGeom gm = f2_geom(h, w, wi0 + mywin);
+  const WinGeom gm = make_geom(h, w, wi0 + mywin);
   // fragment (projection p: 0 = q, 1 = k, 2 = v; channel tile NW c + wv; k-step ks): one contiguous 1 KB per wave at a wave-uniform
   // address -- a scalar base (the wave's tile 0 of q) plus COMPILE-TIME offsets, the lane's 16 bytes as the only vector part (left to
   // itself hipcc kept a 64-bit vector address per load alive from one chunk to the next: 32 registers, all spilled)
@@ -198,11 +164,11 @@ __global__ void __launch_bounds__(256 * TW, 2) window_attn_fwd2_kernel(Fwd2Args 
     for (int it = 0; it < PIT; ++it) {
       const int ii = min(tid + it * NTHR, NITEM - 1);
       const int win = ii / NITEM1, i = ii - win * NITEM1;
-      const WinGeom gw = f2_geom(h, w, wi0 + win);
+      const WinGeom gw = make_geom(h, w, wi0 + win);
       const int px = (i >> 1) % S, kx = (i / (2 * S)) % 10, py = (i / (20 * S)) % S, ky = i / (20 * NPX);
       const int yy = 8 * gw.wy + ky - 1, xx = 8 * gw.wx + kx - 1;
       ok[it] = yy >= 0 && yy < h && xx >= 0 && xx < w;
-      const int Y = S * min(max(yy, 0), h - 1) + py, X = S * min(max(xx, 0), w - 1) + px;     // clamped: the loads are unconditional
+      const int Y = S * clamp_px(yy, h) + py, X = S * clamp_px(xx, w) + px;                   // clamped: the loads are unconditional
       const long long o = (((long long)gw.b * H + Y) * W + X) * 16 + half * 8;
       xf[it].v = f2_nt_load(reinterpret_cast<const bf16x8*>(pa.xn + o));
       pf[it].v = f2_nt_load(reinterpret_cast<const bf16x8*>(pa.xprev + o));
@@ -213,7 +179,7 @@ __global__ void __launch_bounds__(256 * TW, 2) window_attn_fwd2_kernel(Fwd2Args 
       const int ii = tid + it * NTHR;
       const int iic = min(ii, NITEM - 1);
       const int win = iic / NITEM1, ic = iic - win * NITEM1;
-      const WinGeom gw = f2_geom(h, w, wi0 + win);
+      const WinGeom gw = make_geom(h, w, wi0 + win);
       const int px = (ic >> 1) % S, kx = (ic / (2 * S)) % 10, py = (ic / (20 * S)) % S, ky = ic / (20 * NPX);
       const bool own = ky >= 1 && ky <= 8 && kx >= 1 && kx <= 8;
       const int row = own ? (ky - 1) * 8 + (kx - 1) : 64 + ring_index(ky, kx);
@@ -347,10 +313,10 @@ __global__ void __launch_bounds__(256 * TW, 2) window_attn_fwd2_kernel(Fwd2Args 
     for (int t = 0; t < WA_KT; ++t) {
       const int key = 16 * t + lre;
       if (key < WA_NK) {
-        const bf16x4 kb4 = f2_pack4(ak[t]);
-        const bf16x4 vb = f2_pack4(av[t]);
+        const bf16x4 kb4 = pack4(ak[t]);
+        const bf16x4 vb = pack4(av[t]);
         int kr, kc;
-        f2_key_rc(key, kr, kc);
+        own_first_key_rc(key, kr, kc);
         const f32x4 r4 = *reinterpret_cast<const f32x4*>(&RelC[(cc < 2) ? kr : kc][chl]);
         float kh[4] = {(float)kb4[0] + r4[0], (float)kb4[1] + r4[1], (float)kb4[2] + r4[2], (float)kb4[3] + r4[3]};
         store4(&Kc[mywin][key][chl], kh);                              // K^ = bf16(bf16(k) + rel): the rounding points of the unfused kernels
@@ -358,7 +324,7 @@ __global__ void __launch_bounds__(256 * TW, 2) window_attn_fwd2_kernel(Fwd2Args 
           const unsigned qo = ((unsigned)gm.query_pixel(key) * (3 * C) + ch) * 2u;
           f2_nt_store(reinterpret_cast<bf16x4 __attribute__((address_space(1)))*>(qkv_b + qo + 2u * C), kb4);
           *reinterpret_cast<bf16x4 __attribute__((address_space(1)))*>(qkv_b + qo + 4u * C) = vb;
-          const bf16x4 qb = f2_pack4(aq[t < 4 ? t : 0]);
+          const bf16x4 qb = pack4(aq[t < 4 ? t : 0]);
           *reinterpret_cast<bf16x4*>(&Qc[mywin][key][chl]) = qb;
           f2_nt_store(reinterpret_cast<bf16x4 __attribute__((address_space(1)))*>(qkv_b + qo), qb);
         } else {
@@ -394,7 +360,7 @@ __global__ void __launch_bounds__(256 * TW, 2) window_attn_fwd2_kernel(Fwd2Args 
       for (int u = 0; u < 4; ++u) {
         const int idx = tid + (it + u) * NTHR;
         const int win = idx / (64 * VEC), r = idx - win * (64 * VEC);
-        f2_nt_store(reinterpret_cast<bf16x8*>(pa.d + f2_geom(h, w, wi0 + win).query_pixel(r / VEC) * C + (r % VEC) * 8), dr[u].v);
+        f2_nt_store(reinterpret_cast<bf16x8*>(pa.d + make_geom(h, w, wi0 + win).query_pixel(r / VEC) * C + (r % VEC) * 8), dr[u].v);
       }
     }
   }
@@ -416,7 +382,7 @@ __global__ void __launch_bounds__(256 * TW, 2) window_attn_fwd2_kernel(Fwd2Args 
       const int idx = min(tid + it * NTHR, TW * 800 - 1);
       const int win = idx / 800, r = idx - win * 800;
       const int row = r >> 3, cv = r & 7;
-      const WinGeom gw = f2_geom(h, w, wi0 + win);
+      const WinGeom gw = make_geom(h, w, wi0 + win);
       const T* own = pa.qkv + gw.query_pixel(min(row, 63)) * (3 * C) + 2 * C;
       const T* rng = pa.vring + ((long long)gw.wi * WA_RING + max(row - 64, 0)) * C;
       vpre[it] = load8((row < 64 ? own : rng) + 64 * vc + 8 * cv);
@@ -493,7 +459,7 @@ __global__ void __launch_bounds__(256 * TW, 2) window_attn_fwd2_kernel(Fwd2Args 
     for (int c4 = 0; c4 < 4; ++c4)
 #pragma unroll
       for (int m = 0; m < 4; ++m)
-        mma16(o[4 * vc + m], f2_tr8(&Kc[mywin][0][0], CLD, 32 * c4 + 4 * g, 32 * c4 + 16 + 4 * g, 16 * m, lane, ZR), pfr[c4]);
+        mma16(o[4 * vc + m], load8_tr_z(&Kc[mywin][0][0], CLD, 32 * c4 + 4 * g, 32 * c4 + 16 + 4 * g, 16 * m, lane, ZR), pfr[c4]);
     if (vc + 1 < 4) lds_barrier();
   }
   M2T_FWD2_STAMP(6);

@@ -48,37 +48,8 @@ template <int C> struct ResCfg {
   static constexpr size_t total = offRED + sizeof(float) * 3 * 2 * 64;
 };
 
-// transposed 8-element operand: elements 0..3 = rows row_lo_base + 0..3, 4..7 = rows row_hi_base + 0..3 at
-// column col0 + (lane & 15); rows >= zero_row alias the zero row.  (see load8_tr in m2t_common.h)
-__device__ __forceinline__ Frag8<bf16_t> tr8(const bf16_t* base, int ld, int row_lo_base, int row_hi_base, int col0,
-                                             int lane, int zero_row) {
-  const int i = lane & 15, qq = i >> 2, pp = i & 3;
-  typedef bf16x4 __attribute__((address_space(3))) * lds_ptr;
-  const int rlo = min(row_lo_base + qq, zero_row), rhi = min(row_hi_base + qq, zero_row);
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)(base + rlo * ld + col0 + 4 * pp));
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)(base + rhi * ld + col0 + 4 * pp));
-  Frag8<bf16_t> f;
-  f.v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return f;
-}
-
-// Key `key` (0..99) of the window as a 32-bit element offset of its pixel row in a [pixel][row_elems] tensor, relative to the first key
-// row of the window (key_row0), clamped into the image (the loads are unconditional), and whether the key lies inside the image.
-// 24-bit multiplies on purpose: a 64-bit pixel index per lane and load costs two v_mad_u64_u32 and two v_mul_lo_u32, quarter-rate
-// instructions, and phase 0 of these kernels is bound by exactly that integer work (profiles/r06_attn_phase0_integer_work.txt).
-struct KeyAddr { unsigned off; bool ok; int kr, kc; };
-__device__ __forceinline__ int key_row0(const WinGeom& gm) { return max(8 * gm.wy - 1, 0); }
-__device__ __forceinline__ KeyAddr key_addr(const WinGeom& gm, int h, int w, int key, int row_elems) {
-  KeyAddr a;
-  a.kr = (int)(__umul24((unsigned)key, 205u) >> 11);                             // key / 10 for key < 1024
-  a.kc = key - 10 * a.kr;
-  const int yy = 8 * gm.wy + a.kr - 1, xx = 8 * gm.wx + a.kc - 1;
-  a.ok = yy >= 0 && yy < h && xx >= 0 && xx < w;
-  const unsigned pix = __umul24((unsigned)(min(max(yy, 0), h - 1) - key_row0(gm)), (unsigned)w) + (unsigned)min(max(xx, 0), w - 1);
-  a.off = __umul24(pix, (unsigned)row_elems);
-  return a;
-}
-
+// (the transposed operands whose padding rows alias the zero row come through load8_tr_z, m2t_common.h; the 32-bit key addresses
+// of phase 0 -- KeyAddr, key_row0, key_addr -- are in m2t_window.h)
 // dO rows for the whole window: DOs[q][c], c over all C channels.
 // L = 0: plain rows of go (ld, channel offset coff).  L = 1, 2: go is the full-resolution g_xc tensor and the
 // branch gradient is DWT^L of its 16-channel slice: thread (q, 4-channel group) reads its (2^L)^2 pixel block
@@ -344,7 +315,8 @@ __global__ void __launch_bounds__(NW * 64, (C == 64) ? 2 : 1) window_attn_bwd_re
     for (int t = 0; t < WA_KT; ++t) {
       const int key = 16 * t + lr;
       if (key < WA_NK) {
-        const int kr = key / 10, kc = key - kr * 10;
+        int kr, kc;
+        key_rc(key, kr, kc);
 #pragma unroll
         for (int m = 0; m < TPW; ++m) {
           const int ch = 16 * (wv * TPW + m) + 4 * g;
@@ -443,7 +415,8 @@ __global__ void __launch_bounds__(NW * 64, (C == 64) ? 2 : 1) window_attn_bwd_re
       const int idx = t2 + it * 256;
       const int cv = idx % VEC, key = idx / VEC;
       if (it * 256 + 255 < WA_NK * VEC || key < WA_NK) {                          // (a branch in the last iteration only)
-        const int kr = (int)(__umul24((unsigned)key, 205u) >> 11), kc = key - 10 * kr;
+        int kr, kc;
+        key_rc_fast(key, kr, kc);
         const bool ok = kok[it];
         const int cc = cv * 8;
         const f32x4 ra = *reinterpret_cast<const f32x4*>(&RelS[(cc < C / 2) ? kr : kc][cc]);
@@ -775,10 +748,10 @@ __global__ void __launch_bounds__(NW * 64, (C == 64) ? 2 : 1) window_attn_bwd_re
   for (int kc = 0; kc < 2; ++kc) {
     Frag8<T> a[TPW];
 #pragma unroll
-    for (int m = 0; m < TPW; ++m) a[m] = tr8(&DOs[0][0], LD, 32 * kc + 8 * g, 32 * kc + 8 * g + 4, 16 * (mt0 + m), lane, 64);
+    for (int m = 0; m < TPW; ++m) a[m] = load8_tr_z(&DOs[0][0], LD, 32 * kc + 8 * g, 32 * kc + 8 * g + 4, 16 * (mt0 + m), lane, 64);
 #pragma unroll
     for (int t = 0; t < WA_KT; ++t) {
-      const Frag8<T> b = tr8(&Pq[0][0], PLD, 32 * kc + 8 * g, 32 * kc + 8 * g + 4, 16 * t, lane, 64);
+      const Frag8<T> b = load8_tr_z(&Pq[0][0], PLD, 32 * kc + 8 * g, 32 * kc + 8 * g + 4, 16 * t, lane, 64);
 #pragma unroll
       for (int m = 0; m < TPW; ++m) mma16(av[m][t], a[m], b);
     }
@@ -787,17 +760,17 @@ __global__ void __launch_bounds__(NW * 64, (C == 64) ? 2 : 1) window_attn_bwd_re
   for (int kc = 0; kc < 2; ++kc) {
     Frag8<T> a[TPW];
 #pragma unroll
-    for (int m = 0; m < TPW; ++m) a[m] = tr8(&Qs[0][0], LD, 32 * kc + 8 * g, 32 * kc + 8 * g + 4, 16 * (mt0 + m), lane, 64);
+    for (int m = 0; m < TPW; ++m) a[m] = load8_tr_z(&Qs[0][0], LD, 32 * kc + 8 * g, 32 * kc + 8 * g + 4, 16 * (mt0 + m), lane, 64);
 #pragma unroll
     for (int t = 0; t < WA_KT; ++t) {
-      const Frag8<T> b = tr8(&Dq[0][0], DLD, 32 * kc + 8 * g, 32 * kc + 8 * g + 4, 16 * t, lane, 64);
+      const Frag8<T> b = load8_tr_z(&Dq[0][0], DLD, 32 * kc + 8 * g, 32 * kc + 8 * g + 4, 16 * t, lane, 64);
 #pragma unroll
       for (int m = 0; m < TPW; ++m) mma16(ak[m][t], a[m], b);
     }
 #pragma unroll
     for (int m = 0; m < TPW; ++m) {
       const int col0 = (16 * (mt0 + m) < C / 2) ? 128 : 144;
-      const Frag8<T> b = tr8(&Dq[0][0], DLD, 32 * kc + 8 * g, 32 * kc + 8 * g + 4, col0, lane, 64);
+      const Frag8<T> b = load8_tr_z(&Dq[0][0], DLD, 32 * kc + 8 * g, 32 * kc + 8 * g + 4, col0, lane, 64);
       mma16(ak[m][WA_KT], a[m], b);
     }
   }
@@ -844,7 +817,7 @@ __global__ void __launch_bounds__(NW * 64, (C == 64) ? 2 : 1) window_attn_bwd_re
   for (int c4 = 0; c4 < 4; ++c4) {
     Frag8<T> a[TPW];
 #pragma unroll
-    for (int m = 0; m < TPW; ++m) a[m] = tr8(&Kh[0][0], LD, 32 * c4 + 8 * g, 32 * c4 + 8 * g + 4, 16 * (mt0 + m), lane, ZR);
+    for (int m = 0; m < TPW; ++m) a[m] = load8_tr_z(&Kh[0][0], LD, 32 * c4 + 8 * g, 32 * c4 + 8 * g + 4, 16 * (mt0 + m), lane, ZR);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const Frag8<T> b = load8(&Dq[16 * t + lr][32 * c4 + 8 * g]);
@@ -1118,7 +1091,7 @@ __global__ void __launch_bounds__(256) window_attn_fwd_res_kernel(const bf16_t* 
 #pragma unroll
   for (int c4 = 0; c4 < 4; ++c4)
 #pragma unroll
-    for (int mt = 0; mt < NT; ++mt) mma16(o[mt], tr8(&Vs[0][0], LD, 32 * c4 + 4 * g, 32 * c4 + 16 + 4 * g, 16 * mt, lane, ZR), pf[c4]);
+    for (int mt = 0; mt < NT; ++mt) mma16(o[mt], load8_tr_z(&Vs[0][0], LD, 32 * c4 + 4 * g, 32 * c4 + 16 + 4 * g, 16 * mt, lane, ZR), pf[c4]);
   if constexpr (L == 0) {
 #pragma unroll
     for (int mt = 0; mt < NT; ++mt) {

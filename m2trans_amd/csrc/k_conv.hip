@@ -883,12 +883,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_c64_rows_kernel(const bf16_t* 
 __device__ __forceinline__ Frag8<bf16_t> c3b_tr(const unsigned char* p) {
   // p = this lane's address (see c3b_tr_lane): elements 0..3 = pixels +0..3, 4..7 = pixels +16..19 of the fragment's first pixel,
   // channel (lane & 15) of the plane
-  typedef bf16x4 __attribute__((address_space(3))) * lds_ptr;
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)p);
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)(p + 16 * 32));
-  Frag8<bf16_t> f;
-  f.v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return f;
+  return tr8(reinterpret_cast<const bf16_t*>(p), reinterpret_cast<const bf16_t*>(p + 16 * 32));
 }
 __device__ __forceinline__ int c3b_tr_lane(int lane) {        // lane's byte offset inside the 4-pixel x 16-channel block it helps transpose
   const int i = lane & 15;

@@ -60,15 +60,6 @@ struct TailBwdArgs {
   float lparam, lf0, lf1;
 };
 
-__device__ __forceinline__ Frag8<bf16_t> tr_rows(const bf16_t* lo, const bf16_t* hi) {
-  // lo / hi: THIS lane's 8-byte pieces (row r + (i >> 2), columns c0 + 4 (i & 3) ..) of the two 4-row groups
-  typedef bf16x4 __attribute__((address_space(3))) * lds_ptr;
-  const bf16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)lo);
-  const bf16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)hi);
-  Frag8<bf16_t> f;
-  f.v = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-  return f;
-}
 // HR tile row of (mid pixel m = my*8 + mx, sub = i*2 + j)
 __device__ __forceinline__ int hr_row(int m, int sub) { return (2 * (m >> 3) + (sub >> 1)) * TB_T + 2 * (m & 7) + (sub & 1); }
 
@@ -357,8 +348,8 @@ __global__ void __launch_bounds__(512) tail_bwd_fused_kernel(TailBwdArgs a) {
 #pragma unroll
       for (int ks = 0; ks < 8; ++ks) {
         const int r0 = 32 * ks + 8 * g + qq;
-        const Frag8<T> ga = tr_rows(&Ge[r0][16 * (w8 >> 2) + 4 * pp], &Ge[r0 + 4][16 * (w8 >> 2) + 4 * pp]);
-        const Frag8<T> ab = tr_rows(&A2[r0][16 * (w8 & 3) + 4 * pp], &A2[r0 + 4][16 * (w8 & 3) + 4 * pp]);
+        const Frag8<T> ga = tr8(&Ge[r0][16 * (w8 >> 2) + 4 * pp], &Ge[r0 + 4][16 * (w8 >> 2) + 4 * pp]);
+        const Frag8<T> ab = tr8(&A2[r0][16 * (w8 & 3) + 4 * pp], &A2[r0 + 4][16 * (w8 & 3) + 4 * pp]);
         mma16(accF, ga, ab);
       }
     }
@@ -399,11 +390,11 @@ __global__ void __launch_bounds__(512) tail_bwd_fused_kernel(TailBwdArgs a) {
         const int m0 = 32 * ks + 8 * g + qq;                  // this lane's mid pixel in the two 4-row groups: m0, m0 + 4
         Frag8<T> af[4];
 #pragma unroll
-        for (int k2 = 0; k2 < 4; ++k2) af[k2] = tr_rows(&A1[m0][16 * k2 + 4 * pp], &A1[m0 + 4][16 * k2 + 4 * pp]);
+        for (int k2 = 0; k2 < 4; ++k2) af[k2] = tr8(&A1[m0][16 * k2 + 4 * pp], &A1[m0 + 4][16 * k2 + 4 * pp]);
 #pragma unroll
         for (int o = 0; o < 2; ++o) {
           const int nt = 2 * w8 + o, sub = nt >> 2, ct = nt & 3;
-          const Frag8<T> gf = tr_rows(&Gz[hr_row(m0, sub)][16 * ct + 4 * pp], &Gz[hr_row(m0 + 4, sub)][16 * ct + 4 * pp]);
+          const Frag8<T> gf = tr8(&Gz[hr_row(m0, sub)][16 * ct + 4 * pp], &Gz[hr_row(m0 + 4, sub)][16 * ct + 4 * pp]);
 #pragma unroll
           for (int k2 = 0; k2 < 4; ++k2) mma16(accW[o][k2], gf, af[k2]);
           mma16(accB[o], gf, ones);
@@ -545,22 +536,12 @@ template <int Q, int NQ> __device__ __forceinline__ void tb16_geff_part(const fl
   const int lane##sfx = tid##sfx & 63;                                                 \
   (void)lane##sfx
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ void mma32(f32x16& acc, const Frag8<bf16_t>& a, const Frag8<bf16_t>& b) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v, b.v, acc, 0, 0, 0);
-}
-// 32x32x16 operand from a CONTRACTION-major LDS image X[k][row | col] (ld elements per k row): lane (r = lane & 31, h = lane >> 5) receives
-// X[k0 + 8 h + j][c0 + r], j = 0..7 (two transposing reads of a 4 x 16 block per 16-lane group).  EXEC must be all ones.
+// 32x32x16 operand (mma32) from a CONTRACTION-major LDS image X[k][row | col] (ld elements per k row): lane (r = lane & 31, h = lane >> 5)
+// receives X[k0 + 8 h + j][c0 + r], j = 0..7 (two transposing reads of a 4 x 16 block per 16-lane group: tr8).
 __device__ __forceinline__ Frag8<bf16_t> load8_tr32(const bf16_t* x, int ld, int k0, int c0, int lane) {
   const int i = lane & 15, q = i >> 2, pp = i & 3, gs = (lane >> 4) & 1, h = lane >> 5;
-  typedef bf16x4 __attribute__((address_space(3))) * lds_ptr;
   const bf16_t* p = x + (k0 + 8 * h + q) * ld + c0 + 16 * gs + 4 * pp;
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)p);
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)(p + 4 * ld));
-  Frag8<bf16_t> f;
-  f.v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return f;
+  return tr8(p, p + 4 * ld);
 }
 // accumulator register t of a 32x32 tile: row (t & 3) + 8 (t >> 2) + 4 h, column lane & 31
 __device__ __forceinline__ constexpr int acc32_row(int t) { return (t & 3) + 8 * (t >> 2); }

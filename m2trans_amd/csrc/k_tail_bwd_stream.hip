@@ -76,14 +76,6 @@ struct BSArgs {
   int nstrip, nseg, rows, ntask;      // rows per segment: a multiple of 4 that divides Hi
 };
 
-__device__ __forceinline__ void bs_mma4(f32x4& acc, bf16x4 a, bf16x4 b) { acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, acc, 0, 0, 0); }
-// transposing read: the lane passes the address of ITS 8-byte piece (row r0 + (i >> 2), columns c0 + 4 (i & 3) ..) and receives
-// column c0 + i of rows r0 .. r0 + 3 (i = lane & 15)
-__device__ __forceinline__ bf16x4 bs_tr4(const bf16_t* p) {
-  typedef bf16x4 __attribute__((address_space(3))) * lds_ptr;
-  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)p);
-}
-
 template <int R, bool TAIL0>
 __global__ void __launch_bounds__(BSCfg<R>::NTHR, (R == 2 ? 2 : 4)) tail_bwd_stream_kernel(BSArgs p) {
   using T = bf16_t;
@@ -152,14 +144,14 @@ __global__ void __launch_bounds__(BSCfg<R>::NTHR, (R == 2 ? 2 : 4)) tail_bwd_str
           lds_barrier();                                          // phase A of the producers is complete
           bf16x4 bk[4];
 #pragma unroll
-          for (int kp = 0; kp < 4; ++kp) bk[kp] = bs_tr4(&A1[4 * g + tq][16 * kp + 4 * tp]);
+          for (int kp = 0; kp < 4; ++kp) bk[kp] = tr4(&A1[4 * g + tq][16 * kp + 4 * tp]);
 #pragma unroll
           for (int i = 0; i < NTW; ++i) {
             const int Tn = h + 7 * i;                             // n' tile: position Tn >> 2, channel tile Tn & 3
             if (Tn < 4 * NW) {
-              const bf16x4 an = bs_tr4(&G[Tn >> 2][4 * g + tq][16 * (Tn & 3) + 4 * tp]);
+              const bf16x4 an = tr4(&G[Tn >> 2][4 * g + tq][16 * (Tn & 3) + 4 * tp]);
 #pragma unroll
-              for (int kp = 0; kp < 4; ++kp) bs_mma4(aW[i][kp], an, bk[kp]);
+              for (int kp = 0; kp < 4; ++kp) mma4(aW[i][kp], an, bk[kp]);
             }
           }
           if (h < 4) {
@@ -399,9 +391,7 @@ __global__ void __launch_bounds__(BSCfg<R>::NTHR, (R == 2 ? 2 : 4)) tail_bwd_str
             // (q, pp) fetches row 32 ki + 8 g (+ 4) + q, columns 32 kc + 8 pp + 4 hf .. + 3, whose four values go to lanes 4 pp + 0 .. 3
             // (32 registers of resident fragments do not fit beside the accumulator registers)
             const T* wp0 = &W3s[32 * ki + 8 * g + tq][64 * wv + 32 * kc + 8 * tp + 4 * hf];
-            Frag8<T> wa;
-            wa.v = __builtin_shufflevector(bs_tr4(wp0), bs_tr4(wp0 + 4 * LDW3), 0, 1, 2, 3, 4, 5, 6, 7);
-            mma16(acc[hf], wa, cur[ki]);
+            mma16(acc[hf], tr8(wp0, wp0 + 4 * LDW3), cur[ki]);
           }
         }
         Frag8<T> fg, f2;
@@ -438,17 +428,17 @@ __global__ void __launch_bounds__(BSCfg<R>::NTHR, (R == 2 ? 2 : 4)) tail_bwd_str
       if constexpr (!HELP) {
         bf16x4 bk[4];
 #pragma unroll
-        for (int kp = 0; kp < 4; ++kp) bk[kp] = bs_tr4(&A1[4 * g + tq][16 * kp + 4 * tp]);
+        for (int kp = 0; kp < 4; ++kp) bk[kp] = tr4(&A1[4 * g + tq][16 * kp + 4 * tp]);
 #pragma unroll
         for (int tau = 0; tau < 4; ++tau) {
-          const bf16x4 an = bs_tr4(&G[wv][4 * g + tq][16 * tau + 4 * tp]);
+          const bf16x4 an = tr4(&G[wv][4 * g + tq][16 * tau + 4 * tp]);
 #pragma unroll
-          for (int kp = 0; kp < 4; ++kp) bs_mma4(accW[tau][kp], an, bk[kp]);
-          bs_mma4(accB[tau], an, ones4);
+          for (int kp = 0; kp < 4; ++kp) mma4(accW[tau][kp], an, bk[kp]);
+          mma4(accB[tau], an, ones4);
         }
       } else {
 #pragma unroll
-        for (int tau = 0; tau < 4; ++tau) bs_mma4(accB[tau], bs_tr4(&G[wv][4 * g + tq][16 * tau + 4 * tp]), ones4);
+        for (int tau = 0; tau < 4; ++tau) mma4(accB[tau], tr4(&G[wv][4 * g + tq][16 * tau + 4 * tp]), ones4);
       }
       BS_STAMP(5);
       // dWf: wave w owns ((tap, oc) tile, channel tile) = R = 2: (0, w), (1, w); R = 3: (w >> 2, w & 3) for w < 8.  Contraction over
@@ -458,11 +448,11 @@ __global__ void __launch_bounds__(BSCfg<R>::NTHR, (R == 2 ? 2 : 4)) tail_bwd_str
         constexpr int UNR_F = (NW == 4) ? 4 : 1;
 #pragma unroll UNR_F
         for (int sb = 0; sb < NW; ++sb) {                         // (R = 3: rolled -- 27 hoisted LDS reads do not fit 128 registers)
-          const bf16x4 bc = bs_tr4(&A2[sb][4 * g + tq][16 * ct + 4 * tp]);
+          const bf16x4 bc = tr4(&A2[sb][4 * g + tq][16 * ct + 4 * tp]);
 #pragma unroll
           for (int f = 0; f < FT; ++f) {
             const int nt = (NW == 4) ? f : (wv >> 2);
-            bs_mma4(accF[f], bs_tr4(&GE[sb][4 * g + tq][16 * nt + 4 * tp]), bc);
+            mma4(accF[f], tr4(&GE[sb][4 * g + tq][16 * nt + 4 * tp]), bc);
           }
         }
       }

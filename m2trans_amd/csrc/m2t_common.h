@@ -136,6 +136,28 @@ __device__ __forceinline__ void mma16(f32x4& acc, const Frag8<float>& a, const F
   for (int j = 0; j < 8; ++j)
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.v[j], b.v[j], acc, 0, 0, 0);
 }
+// 16x16x16 (bf16): lane l supplies 4 consecutive k = 4*(l>>4) + 0..3 of row | col l&15; D as above
+__device__ __forceinline__ void mma4(f32x4& acc, bf16x4 a, bf16x4 b) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, acc, 0, 0, 0);
+}
+// 32x32x16 (bf16): lane l supplies 8 consecutive k = 8*(l>>5) + 0..7 of row | col l&31;
+// lane l receives D[i = (t&3) + 8*(t>>2) + 4*(l>>5)][j = l&31] in acc[t], t = 0..15
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ void mma32(f32x16& acc, const Frag8<bf16_t>& a, const Frag8<bf16_t>& b) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v, b.v, acc, 0, 0, 0);
+}
+
+// four fp32 values rounded to a bf16x4 (one accumulator tile's registers of a lane)
+__device__ __forceinline__ bf16x4 pack4(const f32x4& a) {
+  bf16x4 r = {(bf16_t)a[0], (bf16_t)a[1], (bf16_t)a[2], (bf16_t)a[3]};
+  return r;
+}
+__device__ __forceinline__ bf16x4 pack4(float a, float b, float c, float d) {
+  bf16x4 v;
+  v[0] = (bf16_t)a; v[1] = (bf16_t)b; v[2] = (bf16_t)c; v[3] = (bf16_t)d;
+  return v;
+}
+__device__ __forceinline__ bf16x4 zero4() { return pack4(0.f, 0.f, 0.f, 0.f); }
 
 // ---------------------------------------------------------------------------------------
 // misc math
@@ -337,17 +359,37 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {   // torch 'reflect' 
 // copied from HBM with 16-byte vectors); the hardware hands lane (i = lane&15, g = lane>>4)
 // the column i of four consecutive LDS rows.  Two reads give the 8-element operand:
 //   elements 0..3 = rows r0 + 0..3, elements 4..7 = rows r1 + 0..3, all at column c0 + i.
-// p0 / p1 point at &tile[r0][c0] / &tile[r1][c0]; ld = row stride in elements (multiple of 4).
 // EXEC must be all ones (every lane of the wave calls this).
+//
+// The primitives take the address of THIS lane's 8-byte piece, which the lane has computed:
+// row r0 + (i >> 2), columns c0 + 4 (i & 3) ..; the lane receives column c0 + i of rows
+// r0 .. r0 + 3 (r0 and c0 may differ per 16-lane group).  Every layout below is address
+// arithmetic in front of them.
 // ---------------------------------------------------------------------------------------
+__device__ __forceinline__ bf16x4 tr4(const bf16_t* p) {
+  typedef bf16x4 __attribute__((address_space(3))) * lds_ptr;
+  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)p);
+}
+// two of them: elements 0..3 from the 4-row group of lo, 4..7 from that of hi
+__device__ __forceinline__ Frag8<bf16_t> tr8(const bf16_t* lo, const bf16_t* hi) {
+  const bf16x4 a = tr4(lo);
+  const bf16x4 b = tr4(hi);
+  Frag8<bf16_t> f;
+  f.v = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+  return f;
+}
+// p0 / p1 point at &tile[r0][c0] / &tile[r1][c0]; ld = row stride in elements (multiple of 4).
 __device__ __forceinline__ Frag8<bf16_t> load8_tr(const bf16_t* p0, const bf16_t* p1, int ld, int lane) {
   const int i = lane & 15, q = i >> 2, pp = i & 3;
-  typedef bf16x4 __attribute__((address_space(3))) * lds_ptr;
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)(p0 + q * ld + 4 * pp));
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)(p1 + q * ld + 4 * pp));
-  Frag8<bf16_t> f;
-  f.v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return f;
+  return tr8(p0 + q * ld + 4 * pp, p1 + q * ld + 4 * pp);
+}
+// The same out of a [row][channel] tile whose padding rows alias ONE zero row: elements 0..3 = rows row_lo_base + 0..3,
+// 4..7 = rows row_hi_base + 0..3 at column col0 + (lane & 15); rows >= zero_row read row zero_row.
+__device__ __forceinline__ Frag8<bf16_t> load8_tr_z(const bf16_t* base, int ld, int row_lo_base, int row_hi_base, int col0,
+                                                    int lane, int zero_row) {
+  const int i = lane & 15, qq = i >> 2, pp = i & 3;
+  const int rlo = min(row_lo_base + qq, zero_row), rhi = min(row_hi_base + qq, zero_row);
+  return tr8(base + rlo * ld + col0 + 4 * pp, base + rhi * ld + col0 + 4 * pp);
 }
 // fp32 has no transposing read: gather the 8 elements one by one (parity mode only)
 __device__ __forceinline__ Frag8<float> load8_tr(const float* p0, const float* p1, int ld, int lane) {

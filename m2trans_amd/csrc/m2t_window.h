@@ -8,12 +8,43 @@
 #define WA_KR 128        // key rows staged (4 contraction chunks of 32)
 #define WA_QP 72         // 64 queries + 8 pad
 
+// A key coordinate clamped into an image axis of n pixels: where the kernels whose loads are unconditional read for a key
+// outside the image (the value is then zeroed by a select).
+__device__ __forceinline__ int clamp_px(int v, int n) { return min(max(v, 0), n - 1); }
+// Raster key order: key = 10 kr + kc, (kr, kc) the position in the 10x10 neighbourhood (0 and 9: the ring).
+// (dkv_row and three kernel sites keep the division written out: hipcc folds their range tests on kr into the division
+// before it inlines anything, and through a call it generates other code.)
+__device__ __forceinline__ void key_rc(int key, int& kr, int& kc) {
+  kr = key / 10;
+  kc = key - kr * 10;
+}
+// The same for key < 1024 (205 / 2^11 = 1 / 9.99..: exact up to 1023) with a 24-bit multiply.  On purpose: the kernels that use it
+// compute one address per lane and load from it, a 32-bit multiply or a 64-bit pixel index per lane costs v_mul_lo_u32 /
+// v_mad_u64_u32, quarter-rate instructions, and phase 0 of those kernels is bound by exactly that integer work
+// (profiles/r06_attn_phase0_integer_work.txt).
+__device__ __forceinline__ void key_rc_fast(int key, int& kr, int& kc) {
+  kr = (int)(__umul24((unsigned)key, 205u) >> 11);
+  kc = key - 10 * kr;
+}
+// Own-pixels-first key order of the fused forward kernels: 0..63 the window's own pixels (= query order, so the first four 16-row
+// tiles serve the q projection too), 64..99 the ring, where key 64 + r is the ring key with ring_index(kr, kc) == r (below).
+// Branch-free (selects): the callers issue loads whose addresses depend on the result.
+__device__ __forceinline__ void own_first_key_rc(int k, int& kr, int& kc) {
+  const int r = k - 64;
+  const int kr_ring = (r < 10) ? 0 : ((r < 20) ? 9 : ((r < 28) ? r - 19 : r - 27));
+  const int kc_ring = (r < 10) ? r : ((r < 20) ? r - 10 : ((r < 28) ? 0 : 9));
+  kr = (k < 64) ? (k >> 3) + 1 : kr_ring;
+  kc = (k < 64) ? (k & 7) + 1 : kc_ring;
+}
+
 struct WinGeom {
   int h, w, nw, nh;
   int b, wy, wx;
   int wi;                 // logical window index (XCD-aware, see xcd_block_index)
+  // pixel of raster key `key`; false: outside the image (ring keys of border windows: zero padding)
   __device__ __forceinline__ bool key_pixel(int key, long long& pix) const {
-    const int kr = key / 10, kc = key - kr * 10;
+    int kr, kc;
+    key_rc(key, kr, kc);
     const int y = 8 * wy + kr - 1, x = 8 * wx + kc - 1;
     pix = ((long long)b * h + y) * w + x;
     return (y >= 0 && y < h && x >= 0 && x < w);
@@ -62,14 +93,10 @@ __device__ __forceinline__ int halo_sources(int b, int y, int x, int nh, int nw,
   return (hasx ? 1 : 0) + (hasy ? 1 : 0) + ((hasx && hasy) ? 1 : 0);
 }
 
-__device__ __forceinline__ WinGeom make_geom(int h, int w) {
+// window `wi` (logical index) of an h x w map
+__device__ __forceinline__ WinGeom make_geom(int h, int w, int wi) {
   WinGeom g;
   g.h = h; g.w = w; g.nw = w / 8; g.nh = h / 8;
-#ifdef M2T_WIN_HOT       // scratch/bench_*.hip knock-out (results WRONG): every workgroup works on one of M2T_WIN_HOT windows -- the kernel's
-  const int wi = xcd_block_index() % (M2T_WIN_HOT);      // loads and stores hit L2, its HBM traffic all but disappears, its instruction stream stays
-#else
-  const int wi = xcd_block_index();
-#endif
   g.wi = wi;
   g.wx = wi % g.nw;
   const int q = wi / g.nw;
@@ -77,4 +104,27 @@ __device__ __forceinline__ WinGeom make_geom(int h, int w) {
   g.b = q / g.nh;
   return g;
 }
+// the workgroup's own window (one workgroup per window)
+__device__ __forceinline__ WinGeom make_geom(int h, int w) {
+#ifdef M2T_WIN_HOT       // scratch/bench_*.hip knock-out (results WRONG): every workgroup works on one of M2T_WIN_HOT windows -- the kernel's
+  const int wi = xcd_block_index() % (M2T_WIN_HOT);      // loads and stores hit L2, its HBM traffic all but disappears, its instruction stream stays
+#else
+  const int wi = xcd_block_index();
+#endif
+  return make_geom(h, w, wi);
+}
 
+// Key `key` (0..99) of the window as a 32-bit element offset of its pixel row in a [pixel][row_elems] tensor, relative to the first key
+// row of the window (key_row0), clamped into the image (the loads are unconditional), and whether the key lies inside the image.
+// 24-bit multiplies throughout, for the reason given at key_rc_fast.
+struct KeyAddr { unsigned off; bool ok; int kr, kc; };
+__device__ __forceinline__ int key_row0(const WinGeom& gm) { return max(8 * gm.wy - 1, 0); }
+__device__ __forceinline__ KeyAddr key_addr(const WinGeom& gm, int h, int w, int key, int row_elems) {
+  KeyAddr a;
+  key_rc_fast(key, a.kr, a.kc);
+  const int yy = 8 * gm.wy + a.kr - 1, xx = 8 * gm.wx + a.kc - 1;
+  a.ok = yy >= 0 && yy < h && xx >= 0 && xx < w;
+  const unsigned pix = __umul24((unsigned)(clamp_px(yy, h) - key_row0(gm)), (unsigned)w) + (unsigned)clamp_px(xx, w);
+  a.off = __umul24(pix, (unsigned)row_elems);
+  return a;
+}
